@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- online refinement steps/sec of the MI355X hot path (DESIGN.md "Measurement").
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload seq|warp] [--odom gt|icp|gradicp] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload seq|warp] [--odom gt|icp|gradicp] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--no-roofline]]
+
+A plain run sets up, warms up, times the K steps, writes the last timed step's outputs (--dump-outputs) and prints the JSON
+line.  --full adds the figures that take runs or measurements of their own: the per-kernel roofline pass, the CPU baseline,
+the odometry comparison with the oracle (--odom icp|gradicp) and the whole-pass figure read from profiles/.
 
 Default workload = BASELINE.json configs[2]: a synthetic 640x480 RGB-D sequence of seq_len = 60 run through the build's
 online_adaption.SLAM with the keyframe schedule (every frame of the synthetic orbit is a keyframe), 3 refinement steps per
@@ -70,8 +75,12 @@ def parse_args(argv=None):
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--odom", default="gt", choices=["gt", "icp", "gradicp"], help="MODEL.odom of the map step (gradicp: reports the ATE)")
     ap.add_argument("--tum", action="store_true", help="TUM-shaped sequence (fx = fy = 525, 10 %% zero-depth holes, threshold 0.12): configs[3]")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true", help="skip the per-kernel event-timing pass")
+    ap.add_argument("--full", action="store_true", help="also the per-kernel roofline pass, the CPU baseline, the odometry comparison with the oracle "
+                                                        "and the whole-pass figure (a plain run measures the timed steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, a seeded sample of the large arrays)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="[--full] skip the CPU baseline and the odometry comparison")
+    ap.add_argument("--no-roofline", action="store_true", help="[--full] skip the per-kernel event-timing pass")
     ap.add_argument("--dry", action="store_true", help="CPU rehearsal of the multi-process path (gloo, no GPU, no kernels): launch / exchange / gather only")
     ap.add_argument("--print-stamp", action="store_true", help="print source_stamp() and exit (tools/bench_pmc.sh)")
     ap.add_argument("--same-sequence", action="store_true", help="[N > 1] every rank refines the SAME sequence (seed 1234): the averaged update must then "
@@ -154,6 +163,53 @@ def cpu_baseline_seq(H, W, tum=False):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# --dump-outputs: what the last timed step computed, for output-by-output comparison of two builds
+# ---------------------------------------------------------------------------------------------------------------------
+DUMP_SAMPLE = 1 << 20          # network parameters written: a fixed, seeded sample of the 14.3 M
+DUMP_MAP_ROWS = 1 << 18        # map rows written: a fixed, seeded sample once the map holds more
+
+
+def _sample_rows(n, k, seed):
+    """Sorted indices of a fixed, seeded sample of k of n rows (all rows when n <= k)."""
+    import torch
+    if n <= k:
+        return torch.arange(n)
+    return torch.randperm(n, generator=torch.Generator().manual_seed(seed))[:k].sort().values
+
+
+def write_outputs(out_dir, arrays):
+    """arrays: name -> tensor / array, written as out_dir/<name>.npy in float32 (float64 stays float64)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
+        a = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+        total += a.nbytes
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    assert total <= 64 << 20, f"--dump-outputs wrote {total} bytes (limit 64 MB)"
+
+
+def seq_outputs(slam):
+    """The refinement step's results as its caller finds them after the last timed step: the loss terms and median ratio of that
+    step, the median-scaled depths of the pair predicted by the refined network (the map update's input), the network parameters
+    and the global map (fixed seeded samples of both)."""
+    import torch
+    sp = slam.step_plan
+    lp, lr, l3 = sp.losses()
+    flat = slam.optimizer.flat.data
+    M = int(slam.map.M)
+    pts, nrm, col, cnt = slam.map.live()
+    rows = _sample_rows(M, DUMP_MAP_ROWS, 1).to(pts.device)
+    return {"losses": torch.stack([lp.reshape(()), lr.reshape(()), l3.reshape(()), sp.ratio.reshape(())]).double(),
+            "depth": sp.depth,
+            "parameters_sample": flat[_sample_rows(flat.numel(), DUMP_SAMPLE, 0).to(flat.device)],
+            "parameter_sum": flat.double().sum().reshape(1),
+            "map_size": torch.tensor([M], dtype=torch.float64),
+            "map_points_sample": pts[rows], "map_normals_sample": nrm[rows], "map_colors_sample": col[rows], "map_counts_sample": cnt[rows]}
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # default workload: BASELINE configs[2]
 # ---------------------------------------------------------------------------------------------------------------------
 def seq_bench(a, rank, world, dev):
@@ -215,6 +271,8 @@ def seq_bench(a, rank, world, dev):
     el = time.perf_counter() - t0
     barrier()
     assert slam.refinement_steps_done - done0 == K
+    if a.dump_outputs and rank == 0:                    # before anything else runs a step
+        write_outputs(a.dump_outputs, seq_outputs(slam))
     timed = state["visited"][v0:]
     covered = {"first": {"pass": timed[0][0], "keyframe": timed[0][1] + 1, "map_points_before": int(timed[0][2])},
                "last": {"pass": timed[-1][0], "keyframe": timed[-1][1] + 1, "map_points_before": int(timed[-1][2])},
@@ -243,7 +301,7 @@ def seq_bench(a, rank, world, dev):
 
     # ---- per-kernel durations of ONE more keyframe, measured live with HIP events on the launch streams --------------
     roof = {}
-    if not a.no_roofline:
+    if a.full and not a.no_roofline:
         overlap, slam.overlap_wgrad = slam.overlap_wgrad, False     # one stream: a kernel's duration is its own, not a shared GPU's
         with KernelTimer() as kt:
             run_steps(spk)
@@ -319,7 +377,7 @@ def seq_bench(a, rank, world, dev):
     # pose) are snapshotted, the oracle (oracle/icp.py on the host cores) registers the same frame against the same map, and both poses
     # are scored against the dataset pose -- two trajectory errors over one prefix, plus the largest difference between the two estimates
     odom_parity = None
-    if a.odom != "gt" and world == 1 and not a.no_cpu_baseline:
+    if a.full and a.odom != "gt" and world == 1 and not a.no_cpu_baseline:
         from oracle import icp as oicp
         rows = []
         for _ in range(3):
@@ -382,7 +440,7 @@ def seq_bench(a, rank, world, dev):
         out["source_stamp"] = source_stamp()
         # the default timed region (20 steps from keyframe 3, a small map) reads faster than a whole pass of the 60-frame sequence: the
         # whole-pass figure travels with this line, with the build it was measured on (tools/evidence.sh runs it first)
-        if world == 1 and a.workload == "seq" and os.path.isfile(WHOLE_PASS):
+        if a.full and world == 1 and a.workload == "seq" and os.path.isfile(WHOLE_PASS):
             try:
                 with open(WHOLE_PASS) as f:
                     wp = json.loads([l for l in f.read().splitlines() if l.startswith("{")][-1])
@@ -392,7 +450,7 @@ def seq_bench(a, rank, world, dev):
                                            "file": os.path.relpath(WHOLE_PASS, ROOT), "command": "python3 bench.py --gpus 1 --steps 177 --warmup 6 --no-cpu-baseline"}
             except Exception as e:                      # a malformed record must not cost the bench line
                 out["value_whole_pass"] = {"error": repr(e)}
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline_seq(H, W, a.tum)
         print(json.dumps(out))
     if world > 1:
@@ -505,35 +563,45 @@ def warp_bench(a, rank, world, dev):
             tt = torch.tensor([el], device=dev, dtype=torch.float64)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             el = float(tt.item())
-        # the dominant kernel alone: a captured run of 20 back-to-back launches between ONE event pair (one pair per eager launch
-        # over-reports an 11 us kernel by ~2 us); rocprofv3's average agrees with this figure
-        RUN = 20
-        gk = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(gk, stream=side):
-            for _ in range(RUN):
-                plan.step(want_loss=False)
-        ts = []
-        for _ in range(60):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(side)
-            gk.replay()
-            e1.record(side)
-            side.synchronize()
-            ts.append(e0.elapsed_time(e1) / RUN)
-        ts.sort()
-        dom_ms = sum(ts[6:-6]) / len(ts[6:-6])
+        if a.dump_outputs and rank == 0:                # the last timed step's loss [photometric, regulariser] and d loss / d depth
+            last_loss = step_losses[G - 1] if (graph_g is not None and steps % G == 0) else plan.loss
+            outs = {"losses": last_loss.double(), "g_depth_tgt": plan.g_depth_tgt}
+            if plan.reg:
+                outs["g_depth_src"] = plan.g_depth_src
+            write_outputs(a.dump_outputs, outs)
+        dom_ms = None
+        if a.full:
+            # the dominant kernel alone: a captured run of 20 back-to-back launches between ONE event pair (one pair per eager launch
+            # over-reports an 11 us kernel by ~2 us); rocprofv3's average agrees with this figure
+            RUN = 20
+            gk = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(gk, stream=side):
+                for _ in range(RUN):
+                    plan.step(want_loss=False)
+            ts = []
+            for _ in range(60):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(side)
+                gk.replay()
+                e1.record(side)
+                side.synchronize()
+                ts.append(e0.elapsed_time(e1) / RUN)
+            ts.sort()
+            dom_ms = sum(ts[6:-6]) / len(ts[6:-6])
     N = B * H * W
-    achieved = 48 * N / (dom_ms * 1e-3) / 1e9
     if rank == 0:
-        print(json.dumps({
+        out = {
             "metric": "online refinement steps/sec @640x480", "value": world * steps * B / el, "unit": "steps/s", "n_gpus": world, "steps": steps,
             "warmup": warm, "ms_per_step": 1e3 * el / steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
             "data": "synthetic",
             "config": {"workload": "BASELINE configs[1]: synthetic 640x480 RGB-D pair, warp+photometric(+l2 depth-reg) fwd+bwd kernels only",
                        "pairs_per_launch": B, "height": H, "width": W,
-                       "launch": "eager" if graph is None else f"hipGraph replay, {G} step(s) per replay" + (", chained launches" if G > 1 else "")},
-            "roofline": {"bound": "hbm", "kernel": "k_warp_photo_lossgrad", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": None, "avg_launch_us": 1e3 * dom_ms, "algorithmic_bytes_per_launch": 48 * N}}))
+                       "launch": "eager" if graph is None else f"hipGraph replay, {G} step(s) per replay" + (", chained launches" if G > 1 else "")}}
+        if dom_ms is not None:
+            achieved = 48 * N / (dom_ms * 1e-3) / 1e9
+            out["roofline"] = {"bound": "hbm", "kernel": "k_warp_photo_lossgrad", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": achieved / HBM_PEAK_GBS, "traffic": None, "avg_launch_us": 1e3 * dom_ms, "algorithmic_bytes_per_launch": 48 * N}
+        print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()
 

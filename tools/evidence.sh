@@ -1,6 +1,6 @@
 #!/bin/bash
 # usage: tools/evidence.sh <tag>  -- the measured evidence of a round, under gpurun_out/evidence_<tag>/ (copy what is to be judged to profiles/):
-#   bench_default.json          python3 bench.py --gpus 1 --steps 20 --warmup 5                      (the driver's command)
+#   bench_default.json          python3 bench.py --gpus 1 --steps 20 --warmup 5 --full               (the driver's command + roofline, CPU baseline)
 #   bench_fullpass.json         ... --steps 177 --warmup 6: one whole pass of the 60-frame sequence (59 keyframes x 3 steps)
 #   bench_tum.json              ... --tum: BASELINE configs[3] (TUM intrinsics, 10 % depth holes, threshold 0.12)
 #   bench_gradicp.json          ... --odom gradicp: frame-to-model GradICP odometry in the map step, reports the ATE
@@ -25,12 +25,12 @@ cp gpurun_out/benchpmc_$TAG/traffic.txt $OUT/pmc_traffic.txt; cp gpurun_out/benc
 cp gpurun_out/benchpmc_$TAG/traffic.json profiles/r04_bench_pmc_traffic.json
 echo "pmc done" > $OUT/progress.txt
 # whole pass BEFORE the default line: the default line embeds it (value_whole_pass) with the stamp of the build it was measured on
-python3 bench.py --gpus 1 --steps 177 --warmup 6 --no-cpu-baseline > $OUT/bench_fullpass.json 2> $OUT/bench_fullpass.err; echo "fullpass $?" >> $OUT/progress.txt
+python3 bench.py --gpus 1 --steps 177 --warmup 6 --full --no-cpu-baseline > $OUT/bench_fullpass.json 2> $OUT/bench_fullpass.err; echo "fullpass $?" >> $OUT/progress.txt
 cp $OUT/bench_fullpass.json profiles/r04_bench_seq_fullpass.json
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "default $?" >> $OUT/progress.txt
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "default $?" >> $OUT/progress.txt
 python3 bench.py --gpus 1 --steps 20 --warmup 5 --tum --no-cpu-baseline --no-roofline > $OUT/bench_tum.json 2> $OUT/bench_tum.err; echo "tum $?" >> $OUT/progress.txt
 E2E_WGRAD_OVERLAP=1 python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-roofline > $OUT/bench_overlap.json 2> $OUT/bench_overlap.err; echo "overlap $?" >> $OUT/progress.txt
-timeout -k 10 400 python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-roofline --odom gradicp > $OUT/bench_gradicp.json 2> $OUT/bench_gradicp.err; echo "gradicp $?" >> $OUT/progress.txt
+timeout -k 10 400 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --no-roofline --odom gradicp > $OUT/bench_gradicp.json 2> $OUT/bench_gradicp.err; echo "gradicp $?" >> $OUT/progress.txt
 rocprofv3 --kernel-trace --stats -d /tmp/ev_$TAG -o full --output-format csv -- python3 bench.py --gpus 1 --steps 60 --warmup 5 --no-cpu-baseline --no-roofline > $OUT/bench_under_rocprof.json 2> $OUT/rocprof.err
 echo "rocprof $?" >> $OUT/progress.txt
 f=$(find /tmp/ev_$TAG -name "*kernel_stats.csv" | head -1); cp "$f" $OUT/kernel_stats.csv

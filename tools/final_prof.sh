@@ -5,9 +5,9 @@ export TMPDIR=/tmp
 TAG=$1
 OUT=$GRAFT_REPO_ROOT/gpurun_out/final_$TAG; mkdir -p $OUT
 cd $GRAFT_REPO_ROOT
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench.json 2> $OUT/bench.err
 echo "bench done" > $OUT/progress.txt
-rocprofv3 --kernel-trace --stats -d /tmp/fin_$TAG -o full --output-format csv -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/rocprof.err
+rocprofv3 --kernel-trace --stats -d /tmp/fin_$TAG -o full --output-format csv -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/rocprof.err
 echo "rocprof done" >> $OUT/progress.txt
 f=$(find /tmp/fin_$TAG -name "*kernel_stats.csv" | head -1); cp "$f" $OUT/kernel_stats.csv
 t=$(find /tmp/fin_$TAG -name "*kernel_trace.csv" | head -1)
@@ -16,7 +16,7 @@ python3 - "$f" > $OUT/kernel_stats.txt <<'PY'
 import csv,sys
 rows=list(csv.DictReader(open(sys.argv[1])))
 tot=sum(float(r['TotalDurationNs']) for r in rows)
-print(f"rocprofv3 --kernel-trace --stats -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline ; total kernel time {tot/1e6:.1f} ms")
+print(f"rocprofv3 --kernel-trace --stats -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline ; total kernel time {tot/1e6:.1f} ms")
 for r in rows[:60]:
     print(f"{r['Name'][:90]:90s} calls {r['Calls']:>6s} avg_us {float(r['AverageNs'])/1e3:9.1f} total_ms {float(r['TotalDurationNs'])/1e6:9.2f} {100*float(r['TotalDurationNs'])/tot:5.1f}%")
 PY

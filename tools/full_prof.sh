@@ -4,7 +4,7 @@ export TMPDIR=/tmp
 TAG=$1; shift
 OUT=$GRAFT_REPO_ROOT/gpurun_out/fullprof_$TAG; mkdir -p $OUT
 cd $GRAFT_REPO_ROOT
-rocprofv3 --kernel-trace --stats -d /tmp/fp_$TAG -o full --output-format csv -- python3 bench.py --no-cpu-baseline "$@" > $OUT/bench.log 2>&1
+rocprofv3 --kernel-trace --stats -d /tmp/fp_$TAG -o full --output-format csv -- python3 bench.py --full --no-cpu-baseline "$@" > $OUT/bench.log 2>&1
 f=$(find /tmp/fp_$TAG -name "*kernel_stats.csv" | head -1)
 cp "$f" $OUT/kernel_stats.csv
 t=$(find /tmp/fp_$TAG -name "*kernel_trace.csv" | head -1)
