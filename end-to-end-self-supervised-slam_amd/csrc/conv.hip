@@ -307,17 +307,42 @@ __device__ __forceinline__ void set_wave_priority(unsigned linear_block_id) {
     else if (p == 3) __builtin_amdgcn_s_setprio(3);
 }
 
+// The workgroup a GEMM body works on, passed in explicitly: the hardware's own ids for a standalone launch (HwIds: read where they are
+// used, as the kernels did before they had bodies -- the standalone kernels compile to the same code), a VIRTUAL id inside a grid that
+// carries two tile sets (PartIds, k_conv_bwd_pair).  Everything that depends on launch order -- the XCD-contiguous remap, the static wave
+// priority, the parity-class decode, the diagnostic stamps -- reads these, never blockIdx / gridDim.
+struct HwIds {
+    __device__ __forceinline__ unsigned x() const { return blockIdx.x; }
+    __device__ __forceinline__ unsigned y() const { return blockIdx.y; }
+    __device__ __forceinline__ unsigned z() const { return blockIdx.z; }
+    __device__ __forceinline__ unsigned gx() const { return gridDim.x; }
+    __device__ __forceinline__ unsigned gy() const { return gridDim.y; }
+    __device__ __forceinline__ unsigned gz() const { return gridDim.z; }
+    __device__ __forceinline__ unsigned lin() const { return blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z); }
+};
+// local id `l` of one part of a 1-D grid, whose tile set is laid out as the (gx, gy, gz) grid of its own launch
+struct PartIds {
+    unsigned l, gx_, gy_, gz_;
+    __device__ __forceinline__ unsigned x() const { return l % gx_; }
+    __device__ __forceinline__ unsigned y() const { return (l / gx_) % gy_; }
+    __device__ __forceinline__ unsigned z() const { return l / (gx_ * gy_); }
+    __device__ __forceinline__ unsigned gx() const { return gx_; }
+    __device__ __forceinline__ unsigned gy() const { return gy_; }
+    __device__ __forceinline__ unsigned gz() const { return gz_; }
+    __device__ __forceinline__ unsigned lin() const { return l; }
+};
+
 #ifdef E2E_CONV_STAMPS          // diagnostic build only (scratch/conv_stamps.py): s_memtime / s_memrealtime stamps of every workgroup's phases
 __device__ unsigned long long g_stamps[8192 * 8];
-#define STAMP(i) do { if (threadIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && blockIdx.x < 8192) g_stamps[blockIdx.x * 8 + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
+#define STAMP(i) do { if (threadIdx.x == 0 && wg.y() == 0 && wg.z() == 0 && wg.x() < 8192) g_stamps[wg.x() * 8 + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
 __device__ unsigned long long g_stamps2[8192 * 4];      // finer stamps inside the prologue of k_conv_gemm
-#define STAMP2(i) do { if (threadIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && blockIdx.x < 8192) g_stamps2[blockIdx.x * 4 + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
+#define STAMP2(i) do { if (threadIdx.x == 0 && wg.y() == 0 && wg.z() == 0 && wg.x() < 8192) g_stamps2[wg.x() * 4 + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
 // shader-clock time spent in the phases of the K loop (wave 0 of every workgroup, summed over its chunks).  The scheduling barriers pin
 // the phases, so this build runs a slightly different (more serial) schedule than the product: it locates the stalls, it is not the product's timing
 __device__ unsigned long long g_phases[8192 * 8];
 #define PHASE_DECL unsigned long long ph_last = __builtin_amdgcn_s_memtime(), ph_acc[6] = {0, 0, 0, 0, 0, 0}
 #define PHASE(i) do { __builtin_amdgcn_sched_barrier(0); const unsigned long long t_ = __builtin_amdgcn_s_memtime(); ph_acc[i] += t_ - ph_last; ph_last = t_; __builtin_amdgcn_sched_barrier(0); } while (0)
-#define PHASE_WRITE do { if (threadIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && blockIdx.x < 8192) for (int i_ = 0; i_ < 6; ++i_) g_phases[blockIdx.x * 8 + i_] = ph_acc[i_]; } while (0)
+#define PHASE_WRITE do { if (threadIdx.x == 0 && wg.y() == 0 && wg.z() == 0 && wg.x() < 8192) for (int i_ = 0; i_ < 6; ++i_) g_phases[wg.x() * 8 + i_] = ph_acc[i_]; } while (0)
 #else
 #define STAMP(i) do { } while (0)
 #define STAMP2(i) do { } while (0)
@@ -326,25 +351,33 @@ __device__ unsigned long long g_phases[8192 * 8];
 #define PHASE_WRITE do { } while (0)
 #endif
 
-template <int WM, int WN, int TM, int TN, int VEC, bool TRANSPOSED, int CB>
-__global__ __launch_bounds__(64 * WM * WN) void k_conv_gemm(ConvArgs a) {
+// LDS tiles of k_conv_gemm: double-buffered A (k-major, row stride padded for the VEC == 4 loader's transposing stores) and B
+template <int WM, int WN, int TM, int TN, int VEC, int CB>
+struct ConvGemmLds {
+    static constexpr int BM = 32 * WM * TM, BN = 32 * TN * WN, APAD = (VEC == 4) ? 1 : 0;
+    float As[2][CB][BM + APAD];
+    float Bs[2][CB][BN];
+};
+
+// the body of k_conv_gemm: workgroup `wg` of the launch described by `a`, LDS tiles As / Bs (the kernel's own static arrays, or a
+// share of k_conv_bwd_pair's union)
+template <int WM, int WN, int TM, int TN, int VEC, bool TRANSPOSED, int CB, class Ids>
+__device__ __forceinline__ void conv_gemm_body(const ConvArgs& a, const Ids& wg, float (*As)[CB][ConvGemmLds<WM, WN, TM, TN, VEC, CB>::BM + ConvGemmLds<WM, WN, TM, TN, VEC, CB>::APAD],
+                                               float (*Bs)[CB][ConvGemmLds<WM, WN, TM, TN, VEC, CB>::BN]) {
     constexpr int BM = 32 * WM * TM, BN = 32 * TN * WN, NT = 64 * WM * WN;
     constexpr int KQ = CB / VEC;                           // k-groups (of VEC) per chunk
     constexpr int A_CNT = BM * KQ;                         // (row, k-group) elements of the A tile
     constexpr int A_PER = (A_CNT + NT - 1) / NT;
     constexpr int B_CNT = CB * (BN / 4);                   // float4 loads of the B tile
     constexpr int B_PER = (B_CNT + NT - 1) / NT;
-    constexpr int APAD = (VEC == 4) ? 1 : 0;
     static_assert(NT % KQ == 0 && NT % BM == 0, "tile / thread-count mismatch");
-    __shared__ float As[2][CB][BM + APAD];
-    __shared__ float Bs[2][CB][BN];
     STAMP(0);
-    set_wave_priority(blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z));
+    set_wave_priority(wg.lin());
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave % WM, wn = wave / WM;
     // parity-class form (transposed gather, stride 2): this workgroup's class, its pixel sub-lattice and its tap subset
     const bool CLS = TRANSPOSED && VEC == 4 && a.cls != 0;
-    const int py = CLS ? (int)((blockIdx.x >> 1) & 1) : 0, px = CLS ? (int)(blockIdx.x & 1) : 0;
+    const int py = CLS ? (int)((wg.x() >> 1) & 1) : 0, px = CLS ? (int)(wg.x() & 1) : 0;
     const int Hc = CLS ? (a.Hd - py + 1) / 2 : a.Hd, Wc = CLS ? (a.Wd - px + 1) / 2 : a.Wd;
     const int kh0 = CLS ? ((py + a.off) & 1) : 0, kw0 = CLS ? ((px + a.off) & 1) : 0, kstep = CLS ? 2 : 1;
     const int nkh = CLS ? (a.KH - kh0 + 1) / 2 : a.KH, nkw = CLS ? (a.KW - kw0 + 1) / 2 : a.KW;
@@ -354,14 +387,14 @@ __global__ __launch_bounds__(64 * WM * WN) void k_conv_gemm(ConvArgs a) {
     // slowest: an XCD's contiguous range then covers one or two K slices, i.e. that part of the WEIGHT matrix only -- with the row tile
     // slowest (the first form) every XCD's L2 fetched the whole matrix, eight times per launch in total (the bulk of FETCH_SIZE on the
     // deep layers, profiles/r03_gemm_k_order_and_fetch.txt); the column tiles of a row tile, which share its input rows, stay neighbours
-    unsigned bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
+    unsigned bx = wg.x(), by = wg.y(), bz = wg.z();
     if (!CLS) {
-        const unsigned nxy = gridDim.x * gridDim.y;
-        const unsigned lin = xcd_contiguous(blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z), nxy * gridDim.z);
+        const unsigned nxy = wg.gx() * wg.gy();
+        const unsigned lin = xcd_contiguous(wg.lin(), nxy * wg.gz());
         bz = lin / nxy;
         const unsigned rem = lin - bz * nxy;
-        bx = rem / gridDim.y;
-        by = rem - bx * gridDim.y;
+        bx = rem / wg.gy();
+        by = rem - bx * wg.gy();
     }
     const int64_t n0 = (int64_t)(CLS ? (bx >> 2) : bx) * BM;
     if (CLS && (n0 >= Ntot || nkh <= 0 || nkw <= 0)) return;        // classes are sized by the largest one; empty tap sets write nothing (output pre-zeroed by the host for KH < 2)
@@ -704,13 +737,13 @@ __global__ __launch_bounds__(64 * WM * WN) void k_conv_gemm(ConvArgs a) {
 #ifdef E2E_CONV_STAMPS
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         STAMP(5);
-        if (threadIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && blockIdx.x < 8192) {
+        if (threadIdx.x == 0 && wg.y() == 0 && wg.z() == 0 && wg.x() < 8192) {
             unsigned hw;
             asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
             unsigned xcc;
             asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-            g_stamps[blockIdx.x * 8 + 6] = hw;
-            g_stamps[blockIdx.x * 8 + 7] = xcc;
+            g_stamps[wg.x() * 8 + 6] = hw;
+            g_stamps[wg.x() * 8 + 7] = xcc;
         }
 #endif
         return;
@@ -740,6 +773,14 @@ __global__ __launch_bounds__(64 * WM * WN) void k_conv_gemm(ConvArgs a) {
                 a.out[orow * a.Ncols + col] = apply_act(v, a.act);
             }
         }
+}
+
+template <int WM, int WN, int TM, int TN, int VEC, bool TRANSPOSED, int CB>
+__global__ __launch_bounds__(64 * WM * WN) void k_conv_gemm(ConvArgs a) {
+    using Lds = ConvGemmLds<WM, WN, TM, TN, VEC, CB>;
+    __shared__ float As[2][CB][Lds::BM + Lds::APAD];
+    __shared__ float Bs[2][CB][Lds::BN];
+    conv_gemm_body<WM, WN, TM, TN, VEC, TRANSPOSED, CB>(a, HwIds{}, As, Bs);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -783,6 +824,9 @@ __global__ __launch_bounds__(256, 2) void k_conv_gemm_sk(ConvArgs a, SkArgs s) {
     __shared__ float As[2][CB][BM + 1];
     __shared__ float Bs[2][CB][BN];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave & 1, wn = wave >> 1;
+#ifdef E2E_CONV_STAMPS
+    const HwIds wg{};
+#endif
     set_wave_priority(blockIdx.x);
     STAMP(0);
     int stamp_piece = 0;
@@ -972,7 +1016,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_gemm_sk(ConvArgs a, SkArgs s) {
 #ifdef E2E_CONV_STAMPS
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     STAMP(6);
-    if (threadIdx.x == 0) g_stamps[blockIdx.x * 8 + 7] = (unsigned long long)stamp_piece;
+    if (threadIdx.x == 0) g_stamps[wg.x() * 8 + 7] = (unsigned long long)stamp_piece;
 #endif
 }
 
@@ -1389,17 +1433,30 @@ __global__ __launch_bounds__(256) void k_wgrad_gemm(WgradArgs a) {
 // out-of-range offsets), no integer divisions in the chunk loop, CB pixels per chunk.  A concat layer reads its two
 // sources through two resources: lanes of one load instruction span columns on both sides of the split, and a
 // resource is wave-uniform, so each slot issues one load per source with the foreign lanes out of range.
-template <int WM, int WN, int CB, bool TWO>
-__global__ __launch_bounds__(256) void k_wgrad_gemm4(WgradArgs a) {
+template <int WM, int WN, int CB>
+struct WgradGemm4Lds {
+    float As[2][CB][32 * WM];
+    float Bs[2][CB][32 * WN];
+};
+
+// the body of k_wgrad_gemm4: workgroup `wg` (see HwIds / PartIds), LDS tiles As / Bs
+template <int WM, int WN, int CB, bool TWO, class Ids>
+__device__ __forceinline__ void wgrad_gemm4_body(const WgradArgs& a, const Ids& wg, float (*As)[CB][32 * WM], float (*Bs)[CB][32 * WN]) {
     constexpr int BM = 32 * WM, BN = 32 * WN, NT = 256;     // WM x WN = 4 waves, one 32x32 accumulator each
     constexpr int A_CNT = CB * (BM / 4), B_CNT = CB * (BN / 4);
     constexpr int A_PER = A_CNT / NT, B_PER = B_CNT / NT;
     static_assert(A_CNT % NT == 0 && B_CNT % NT == 0, "tile / thread-count mismatch");
-    __shared__ float As[2][CB][BM];
-    __shared__ float Bs[2][CB][BN];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave % WM, wn = wave / WM;
-    WGRAD_BLOCK_IDS
+    unsigned bx, by, bz;                                     // (WGRAD_BLOCK_IDS on the workgroup `wg`)
+    set_wave_priority(wg.lin());
+    {
+        const unsigned lin = xcd_contiguous(wg.lin(), wg.gx() * wg.gy() * wg.gz());
+        bx = lin % wg.gx();
+        const unsigned t_ = lin / wg.gx();
+        by = t_ % wg.gy();
+        bz = t_ / wg.gy();
+    }
     const int m0 = by * BM, nn0 = bx * BN;
     const int P = a.B * a.Ho * a.Wo;                          // < 2^24 (host): pixel indices are exact in fp32
     const int p0 = (int)((int64_t)bz * a.pix_per_slice);
@@ -1609,6 +1666,46 @@ __global__ __launch_bounds__(256) void k_wgrad_gemm4(WgradArgs a) {
             const float v = acc[r];                          // (a scalar copy first: __builtin_bit_cast applied to the vector ELEMENT stored element 0 sixteen times)
             __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rsl, (dr < rows_left) ? voff : OOB, dr * a.Npad * 4, 0);
         }
+    }
+}
+
+template <int WM, int WN, int CB, bool TWO>
+__global__ __launch_bounds__(256) void k_wgrad_gemm4(WgradArgs a) {
+    __shared__ float As[2][CB][32 * WM];
+    __shared__ float Bs[2][CB][32 * WN];
+    wgrad_gemm4_body<WM, WN, CB, TWO>(a, HwIds{}, As, Bs);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// A layer's backward-data GEMM and its backward-weight GEMM in ONE launch.  Both read the layer's dZ and neither reads what the other
+// writes; run one after the other, each launch pays its own tile-quantisation tail, its own prologue / epilogue phase and its own lone
+// last workgroup.  Here a 1-D grid carries both tile sets: the first part (rounded up to a multiple of 8, so that the second part's local
+// ids fall on the same XCDs as in a standalone launch), then the second.  Every workgroup runs exactly the tile it would run in its own
+// launch -- same virtual ids (XCD-contiguous order, wave priority, parity class), same arithmetic -- so the results are bit-identical;
+// what changes is that the dispatcher hands CUs that run out of one part's work the other part's workgroups.  The two parts share ONE
+// LDS allocation (a union: two static tile sets would add up to 73 KB and allow only 2 workgroups per CU).
+// ---------------------------------------------------------------------------------------------------------------------
+struct PairGrid {
+    unsigned dgx, dgy, dgz;    // the backward-data tile set, laid out as in its own launch
+    unsigned wgx, wgy, wgz;    // the backward-weight tile set
+    unsigned first;            // workgroups of the first part, a multiple of 8
+    int wgrad_first;           // 1: the backward-weight tiles form the first part
+};
+
+template <int DWM, int DWN, bool TWO>
+__global__ __launch_bounds__(256) void k_conv_bwd_pair(ConvArgs d, WgradArgs w, PairGrid pg) {
+    using DL = ConvGemmLds<DWM, DWN, 1, 1, 4, 32>;
+    using WL = WgradGemm4Lds<2, 2, 32>;
+    static_assert(64 * DWM * DWN == 256, "both parts run 256 threads");
+    __shared__ union { DL d; WL w; } lds;
+    const bool in_first = blockIdx.x < pg.first;
+    const unsigned l = in_first ? blockIdx.x : blockIdx.x - pg.first;
+    if (in_first == (pg.wgrad_first != 0)) {
+        if (l >= pg.wgx * pg.wgy * pg.wgz) return;           // the padding of the first part
+        wgrad_gemm4_body<2, 2, 32, TWO>(w, PartIds{l, pg.wgx, pg.wgy, pg.wgz}, lds.w.As, lds.w.Bs);
+    } else {
+        if (l >= pg.dgx * pg.dgy * pg.dgz) return;
+        conv_gemm_body<DWM, DWN, 1, 1, 4, true, 32>(d, PartIds{l, pg.dgx, pg.dgy, pg.dgz}, lds.d.As, lds.d.Bs);
     }
 }
 
@@ -2628,8 +2725,16 @@ static void launch_streamk(ConvArgs& a, int cb, int G, float* workspace, hipStre
     else hipLaunchKernelGGL((k_conv_gemm_sk<TR, 16>), dim3(G), dim3(256), 0, st, a, s);
 }
 
+// One launch sequence of the implicit GEMM: the main launch (scalar-loader tiles, stream-K, or tiles of shape c on grid g at chunk depth
+// cb) and the epilogue launch that follows a split-K main launch.  plan_gemm decides it and fills the ConvArgs it needs; the standalone
+// entry points and the paired backward (e2e_conv2d_bwd_pair_deferred) both go through it.
+enum GemmKind { GK_SCALAR, GK_STREAMK, GK_TILE };
+enum GemmTail { GT_NONE, GT_SPLITK4, GT_SPLITK, GT_CLS };
+struct GemmLaunch { GemmKind kind; GemmTail tail; GemmCfg c; int cb; dim3 g; int G; };
+
 template <bool TR>
-static void launch_gemm(ConvArgs a, int vec, float* workspace_all, GemmCfg force, hipStream_t st) {
+static GemmLaunch plan_gemm(ConvArgs& a, int vec, float* workspace_all, GemmCfg force) {
+    GemmLaunch p{GK_TILE, GT_NONE, GemmCfg{0, 0, 0}, 16, dim3(1), 0};
     const int64_t Ntot = (int64_t)a.B * a.Hd * a.Wd;
     const int K = a.KH * a.KW * a.Cin;
     const int cb = (vec == 4 && a.Cin % 32 == 0 && (a.C1 == a.Cin || a.C1 % 32 == 0)) ? 32 : 16;
@@ -2638,10 +2743,11 @@ static void launch_gemm(ConvArgs a, int vec, float* workspace_all, GemmCfg force
     a.bytes0 = (int64_t)a.B * (a.Hs / a.up) * (a.Ws / a.up) * a.C1 * 4;
     a.bytes1 = (int64_t)a.B * a.Hs * a.Ws * (a.Cin - a.C1) * 4;
     a.bytesw = (int64_t)K * a.ldw * 4;
+    p.cb = cb;
     if (vec == 1) {
-        dim3 g((unsigned)((Ntot + 127) / 128), (unsigned)((a.Ncols + 63) / 64));
-        hipLaunchKernelGGL((k_conv_gemm<4, 1, 1, 2, 1, TR, 16>), g, dim3(256), 0, st, a);
-        return;
+        p.kind = GK_SCALAR;
+        p.g = dim3((unsigned)((Ntot + 127) / 128), (unsigned)((a.Ncols + 63) / 64));
+        return p;
     }
     if (TR && a.cls) {
         // 4 parity classes x the tiles of the largest class (ceil(Hd/2) x ceil(Wd/2) pixels per image); blockIdx.x & 3 = class.
@@ -2649,6 +2755,7 @@ static void launch_gemm(ConvArgs a, int vec, float* workspace_all, GemmCfg force
         const int64_t Nc = (int64_t)a.B * ((a.Hd + 1) / 2) * ((a.Wd + 1) / 2);
         GemmCfg c = choose_cfg(Nc * 4, a.Ncols, (K * 9 / 16 + cb - 1) / cb * cb, cb, false, force.S < 0 ? GemmCfg{0, 0, 0} : force);
         if (c.bm == 128 && c.bn == 128) c.bn = 64;
+        p.c = c;
         // The classes of a 3x3 kernel carry 4, 2, 2 and 1 taps: with so few workgroups the launch lasts as long as a 4-tap one
         // (l4.0.conv1: 57 us against 26 us for the forward).  Slice every class by TAP: equal work per workgroup, partial sums in
         // per-(tap, class) slabs, added in tap order by the class epilogue.
@@ -2657,20 +2764,19 @@ static void launch_gemm(ConvArgs a, int vec, float* workspace_all, GemmCfg force
         if (workspace && cls_wgs < 500 && a.KH == 3 && a.KW == 3 && a.Cin % cb == 0 && a.Ncols % 4 == 0 && total < (1ll << 31) && !a.scale && !a.shift &&
             a.act == ACT_NONE) {
             a.ksplit = 4; a.cps = a.Cin / cb; a.cls_rows = Nc;
-            dim3 g((unsigned)(4 * ((Nc + c.bm - 1) / c.bm)), (unsigned)((a.Ncols + c.bn - 1) / c.bn), 4u);
-            launch_tile<TR>(a, cb, c, g, st);
-            hipLaunchKernelGGL(k_conv_splitk_epilogue_cls, dim3(egrid(total / 4)), dim3(256), 0, st, workspace, Nc, a.B, a.Hd, a.Wd, a.Ncols, a.KH, a.KW, a.off,
-                               a.res, a.out, a.xin, a.dact, a.pre);
-            return;
+            p.g = dim3((unsigned)(4 * ((Nc + c.bm - 1) / c.bm)), (unsigned)((a.Ncols + c.bn - 1) / c.bn), 4u);
+            p.tail = GT_CLS;
+            return p;
         }
-        dim3 g((unsigned)(4 * ((Nc + c.bm - 1) / c.bm)), (unsigned)((a.Ncols + c.bn - 1) / c.bn));
-        launch_tile<TR>(a, cb, c, g, st);
-        return;
+        p.g = dim3((unsigned)(4 * ((Nc + c.bm - 1) / c.bm)), (unsigned)((a.Ncols + c.bn - 1) / c.bn));
+        return p;
     }
     const GemmCfg c = choose_cfg(Ntot, a.Ncols, K, cb, workspace != nullptr, force);
+    p.c = c;
     if (c.S < 0 && workspace && vec == 4 && K % cb == 0 && a.Cin % cb == 0) {      // stream-K (64x64 tiles)
-        launch_streamk<TR>(a, cb, -c.S, workspace_all, st);
-        return;
+        p.kind = GK_STREAMK;
+        p.G = -c.S;
+        return p;
     }
     if (c.S > 1) {
         const int nchunks = (K + cb - 1) / cb;
@@ -2678,20 +2784,43 @@ static void launch_gemm(ConvArgs a, int vec, float* workspace_all, GemmCfg force
         const int Sz = (nchunks + a.cps - 1) / a.cps;
         a.ksplit = Sz;
         if (Sz > 1) {
-            dim3 g((unsigned)((Ntot + c.bm - 1) / c.bm), (unsigned)((a.Ncols + c.bn - 1) / c.bn), (unsigned)Sz);
-            launch_tile<TR>(a, cb, c, g, st);
+            p.g = dim3((unsigned)((Ntot + c.bm - 1) / c.bm), (unsigned)((a.Ncols + c.bn - 1) / c.bn), (unsigned)Sz);
             const int64_t total = Ntot * a.Ncols;
-            if (a.Ncols % 4 == 0 && total < (1ll << 31))
-                hipLaunchKernelGGL(k_conv_splitk_epilogue4, dim3(egrid(total / 4)), dim3(256), 0, st, workspace, Sz, (unsigned)(total / 4), a.Ncols, a.scale, a.shift,
-                                   a.res, a.out, a.act, a.xin, a.dact, a.pre);
-            else
-                hipLaunchKernelGGL(k_conv_splitk_epilogue, dim3(egrid(total)), dim3(256), 0, st, workspace, Sz, total, a.Ncols, a.scale, a.shift, a.res, a.out, a.act, a.xin, a.dact, a.pre);
-            return;
+            p.tail = (a.Ncols % 4 == 0 && total < (1ll << 31)) ? GT_SPLITK4 : GT_SPLITK;
+            return p;
         }
         a.ksplit = 1; a.cps = 0;
     }
-    dim3 g((unsigned)((Ntot + c.bm - 1) / c.bm), (unsigned)((a.Ncols + c.bn - 1) / c.bn));
-    launch_tile<TR>(a, cb, c, g, st);
+    p.g = dim3((unsigned)((Ntot + c.bm - 1) / c.bm), (unsigned)((a.Ncols + c.bn - 1) / c.bn));
+    return p;
+}
+
+template <bool TR>
+static void launch_gemm_main(ConvArgs& a, const GemmLaunch& p, float* workspace_all, hipStream_t st) {
+    if (p.kind == GK_SCALAR) hipLaunchKernelGGL((k_conv_gemm<4, 1, 1, 2, 1, TR, 16>), p.g, dim3(256), 0, st, a);
+    else if (p.kind == GK_STREAMK) launch_streamk<TR>(a, p.cb, p.G, workspace_all, st);
+    else launch_tile<TR>(a, p.cb, p.c, p.g, st);
+}
+
+// the epilogue of a split-K main launch: adds the slices (slabs at a.slab) in order
+static void launch_gemm_tail(const ConvArgs& a, const GemmLaunch& p, hipStream_t st) {
+    const int64_t total = (int64_t)a.B * a.Hd * a.Wd * a.Ncols;
+    if (p.tail == GT_CLS)
+        hipLaunchKernelGGL(k_conv_splitk_epilogue_cls, dim3(egrid(total / 4)), dim3(256), 0, st, a.slab, a.cls_rows, a.B, a.Hd, a.Wd, a.Ncols, a.KH, a.KW, a.off,
+                           a.res, a.out, a.xin, a.dact, a.pre);
+    else if (p.tail == GT_SPLITK4)
+        hipLaunchKernelGGL(k_conv_splitk_epilogue4, dim3(egrid(total / 4)), dim3(256), 0, st, a.slab, a.ksplit, (unsigned)(total / 4), a.Ncols, a.scale, a.shift,
+                           a.res, a.out, a.act, a.xin, a.dact, a.pre);
+    else if (p.tail == GT_SPLITK)
+        hipLaunchKernelGGL(k_conv_splitk_epilogue, dim3(egrid(total)), dim3(256), 0, st, a.slab, a.ksplit, total, a.Ncols, a.scale, a.shift, a.res, a.out, a.act,
+                           a.xin, a.dact, a.pre);
+}
+
+template <bool TR>
+static void launch_gemm(ConvArgs a, int vec, float* workspace_all, GemmCfg force, hipStream_t st) {
+    const GemmLaunch p = plan_gemm<TR>(a, vec, workspace_all, force);
+    launch_gemm_main<TR>(a, p, workspace_all, st);
+    launch_gemm_tail(a, p, st);
 }
 
 extern "C" {
@@ -2821,9 +2950,12 @@ int e2e_conv2d_fwd_tuned(const float* src0, const float* src1, int C1, int up, c
                          workspace, GemmCfg{tile_m, tile_n, ksplit}, stream);
 }
 
-static int bwd_data_impl(const float* dz, const float* w_bwd, int ld_bwd, float* dxp, int B, int Hs, int Ws, int Cin, int Cout, int Ho, int Wo,
-                         int KH, int KW, int stride, int pad, int pad_mode, int accumulate, const float* x_in, int in_act, const float* pre_add,
-                         float* workspace, void* stream, GemmCfg force = GemmCfg{0, 0, 0}) {
+// backward-data up to its GEMM: checks the arguments, serves the 16 -> 16 reflection-padded layer with its patch kernel (*done = true), or
+// fills the GEMM's ConvArgs (and zeroes the classes a 1x1 stride-2 kernel does not reach).  Shared by bwd_data_impl and the paired backward.
+static int bwd_data_setup(const float* dz, const float* w_bwd, int ld_bwd, float* dxp, int B, int Hs, int Ws, int Cin, int Cout, int Ho, int Wo,
+                          int KH, int KW, int stride, int pad, int pad_mode, int accumulate, const float* x_in, int in_act, const float* pre_add,
+                          GemmCfg force, hipStream_t stream, ConvArgs& a, bool& done) {
+    done = false;
     E2E_REQUIRE(pre_add == nullptr || pad_mode == 0, E2E_ERR_ARG, "e2e_conv2d_bwd_data: the pre-activation addend takes a zero-padded layer");
     E2E_REQUIRE(in_act == 0 || (x_in && (in_act == ACT_RELU || in_act == ACT_ELU) && pad_mode == 0), E2E_ERR_ARG,
                 "e2e_conv2d_bwd_data: the fused input-activation derivative takes ReLU / ELU, the activation's output and a zero-padded layer");
@@ -2834,11 +2966,11 @@ static int bwd_data_impl(const float* dz, const float* w_bwd, int ld_bwd, float*
     // 16 -> 16 channels on the padded grid of a reflection-padded layer (upconv(0,1)): dXp[q] = sum_t dZ[q - t] Wb[t], patch kernel
     if (!force.bm && KH == 3 && KW == 3 && stride == 1 && pad == 1 && pad_mode == 1 && Cin == 16 && Cout == 16 && !accumulate && !in_act && !pre_add && ld_bwd >= 16) {
         ThinArgs t{dz, w_bwd, nullptr, dxp, B, Ho, Wo, Hs + 2, Ws + 2, ld_bwd, ACT_NONE, 2, 1};
-        hipLaunchKernelGGL((k_conv3x3_thin<16, 1, false, 8>), dim3((Ws + 2 + 63) / 64, (Hs + 2 + 7) / 8, B), dim3(256), 0, (hipStream_t)stream, t);
-        E2E_LAUNCH_CHECK("e2e_conv2d_bwd_data");
+        hipLaunchKernelGGL((k_conv3x3_thin<16, 1, false, 8>), dim3((Ws + 2 + 63) / 64, (Hs + 2 + 7) / 8, B), dim3(256), 0, stream, t);
+        done = true;
         return E2E_OK;
     }
-    ConvArgs a{};
+    a = ConvArgs{};
     a.src0 = dz; a.src1 = nullptr; a.w = w_bwd; a.out = dxp;
     a.B = B; a.Hs = Ho; a.Ws = Wo; a.Cin = Cout; a.C1 = Cout; a.up = 1;
     const int pp = pad_mode == 1 ? pad : 0;                // reflect: produce the whole padded domain, folded afterwards
@@ -2849,11 +2981,22 @@ static int bwd_data_impl(const float* dz, const float* w_bwd, int ld_bwd, float*
     // (class lattices of 2^24 rows or more take the plain transposed form: the class epilogue decodes its rows in fp32)
     a.cls = (stride == 2 && (int64_t)B * ((a.Hd + 1) / 2) * ((a.Wd + 1) / 2) < (1 << 24)) ? 1 : 0;
     if (a.cls && (KH < 2 || KW < 2) && !accumulate)
-        (void)hipMemsetAsync(dxp, 0, (size_t)B * a.Hd * a.Wd * Cin * sizeof(float), (hipStream_t)stream);
+        (void)hipMemsetAsync(dxp, 0, (size_t)B * a.Hd * a.Wd * Cin * sizeof(float), stream);
     // accumulate: dxp += result -- the epilogue's residual input reads the element it is about to overwrite (same thread)
     if (accumulate) a.res = dxp;
     a.xin = in_act ? x_in : nullptr; a.dact = in_act; a.pre = pre_add;
-    launch_gemm<true>(a, 4, workspace, force, (hipStream_t)stream);
+    return E2E_OK;
+}
+
+static int bwd_data_impl(const float* dz, const float* w_bwd, int ld_bwd, float* dxp, int B, int Hs, int Ws, int Cin, int Cout, int Ho, int Wo,
+                         int KH, int KW, int stride, int pad, int pad_mode, int accumulate, const float* x_in, int in_act, const float* pre_add,
+                         float* workspace, void* stream, GemmCfg force = GemmCfg{0, 0, 0}) {
+    ConvArgs a;
+    bool done;
+    const int rc = bwd_data_setup(dz, w_bwd, ld_bwd, dxp, B, Hs, Ws, Cin, Cout, Ho, Wo, KH, KW, stride, pad, pad_mode, accumulate, x_in, in_act, pre_add,
+                                  force, (hipStream_t)stream, a, done);
+    if (rc != E2E_OK) return rc;
+    if (!done) launch_gemm<true>(a, 4, workspace, force, (hipStream_t)stream);
     E2E_LAUNCH_CHECK("e2e_conv2d_bwd_data");
     return E2E_OK;
 }
@@ -3041,45 +3184,54 @@ int64_t e2e_conv2d_wgrad_workspace_floats(int B, int Ho, int Wo, int Cin, int Co
     return n;
 }
 
-static int bwd_weight_impl(const float* dz, const float* src0, const float* src1, int C1, int up, float* dw, float* dbias, float* workspace, int B,
-                           int Hs, int Ws, int Cin, int Cout, int Ho, int Wo, int KH, int KW, int stride, int pad, int pad_mode, int accumulate,
-                           float in_sub, float in_mul, const float* out_scale, void* stream, int wg_target = 0, e2e_wgrad_reduce_desc* defer = nullptr) {
+// where a backward-weight call's result goes: the slab reduction that ends every path is launched, or -- defer -- described for
+// e2e_wgrad_reduce_batched
+struct WgradOut { float* dw; float* dbias; const float* out_scale; int accumulate; e2e_wgrad_reduce_desc* defer; };
+
+static void wgrad_reduce(const WgradArgs& a, const WgradOut& o, int S, int Mpad, int Npad, int zl, hipStream_t st) {
+    if (o.defer) {
+        *o.defer = e2e_wgrad_reduce_desc{a.slabs, o.dw, o.dbias, o.out_scale, S, Mpad, Npad, a.Cout, a.Cin, a.KH, a.KW, a.has_bias, o.accumulate, zl, 0};
+        return;
+    }
+    const int64_t tq = (int64_t)a.Cout * ((a.Ngemm + 3) / 4);
+    if (zl == 8)
+        hipLaunchKernelGGL((k_wgrad_reduce<8>), dim3(egrid(tq * 4)), dim3(512), 0, st, a.slabs, S, Mpad, Npad, a.Cout, a.Cin, a.KH, a.KW, a.has_bias, o.dw,
+                           o.dbias, o.accumulate, o.out_scale);
+    else
+        hipLaunchKernelGGL((k_wgrad_reduce<2>), dim3(egrid(tq * 4)), dim3(128), 0, st, a.slabs, S, Mpad, Npad, a.Cout, a.Cin, a.KH, a.KW, a.has_bias, o.dw,
+                           o.dbias, o.accumulate, o.out_scale);
+}
+
+// the implicit-GEMM kernel of a backward-weight call (WK_DONE: a patch kernel served it, reduction included) on grid g of Sz pixel slices
+enum WgradKernel { WK_DONE, WK_GEMM16, WK_GEMM4_32, WK_GEMM4_64, WK_GEMM_32, WK_GEMM_64 };
+struct WgradLaunch { WgradKernel k; dim3 g; int Sz; };
+
+// backward-weight up to its GEMM: checks the arguments, serves the stem / thin / tap layers with their patch kernels and reductions
+// (L.k = WK_DONE), or fills the GEMM's WgradArgs and decomposition.  Shared by bwd_weight_impl and the paired backward.
+static int wgrad_setup(const float* dz, const float* src0, const float* src1, int C1, int up, float* workspace, int B, int Hs, int Ws, int Cin,
+                       int Cout, int Ho, int Wo, int KH, int KW, int stride, int pad, int pad_mode, float in_sub, float in_mul, int wg_target,
+                       const WgradOut& o, hipStream_t st, WgradArgs& a, WgradLaunch& L) {
     const bool tuned = wg_target != 0;
     if (!tuned) wg_target = WGRAD_TARGET;
-    E2E_REQUIRE(dz && src0 && dw && workspace && B > 0 && Cin > 0 && Cout > 0, E2E_ERR_ARG, "e2e_conv2d_bwd_weight: bad argument");
+    L = WgradLaunch{WK_DONE, dim3(1), 0};
+    E2E_REQUIRE(dz && src0 && o.dw && workspace && B > 0 && Cin > 0 && Cout > 0, E2E_ERR_ARG, "e2e_conv2d_bwd_weight: bad argument");
     const int vec = (Cin % 4 == 0 && C1 % 4 == 0) ? 4 : 1;
     E2E_REQUIRE(vec == 4 || (C1 == Cin && up == 1 && pad_mode == 0), E2E_ERR_ARG, "e2e_conv2d_bwd_weight: scalar path takes one full-resolution zero-padded source");
-    WgradArgs a{};
+    a = WgradArgs{};
     a.dz = dz; a.src0 = src0; a.src1 = src1; a.slabs = workspace;
     a.B = B; a.Hs = Hs; a.Ws = Ws; a.Cin = Cin; a.C1 = C1; a.up = up; a.Ho = Ho; a.Wo = Wo; a.Cout = Cout;
-    a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad; a.pad_mode = pad_mode; a.has_bias = dbias ? 1 : 0;
+    a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad; a.pad_mode = pad_mode; a.has_bias = o.dbias ? 1 : 0;
     a.Ngemm = KH * KW * Cin + a.has_bias;
     const int64_t P = (int64_t)B * Ho * Wo;
     // lean VEC-4 kernel: 32 pixels per chunk; needs Cout % 4 == 0, 32-bit offsets and image rows of at least 8 pixels
     const bool lean = vec == 4 && Cout % 4 == 0 && Wo >= 8 && (int64_t)B * Hs * Ws * Cin * 4 < (1ll << 31) && P * Cout * 4 < (1ll << 31) && P < (1ll << 24);
-    hipStream_t st = (hipStream_t)stream;
-    // the slab reduction that ends every path: launched here, or -- `defer` -- described for e2e_wgrad_reduce_batched
-    auto reduce = [&](int S, int Mpad, int Npad, int zl) {
-        if (defer) {
-            *defer = e2e_wgrad_reduce_desc{workspace, dw, dbias, out_scale, S, Mpad, Npad, Cout, Cin, KH, KW, a.has_bias, accumulate, zl, 0};
-            return;
-        }
-        const int64_t tq = (int64_t)Cout * ((a.Ngemm + 3) / 4);
-        if (zl == 8)
-            hipLaunchKernelGGL((k_wgrad_reduce<8>), dim3(egrid(tq * 4)), dim3(512), 0, st, workspace, S, Mpad, Npad, Cout, Cin, KH, KW, a.has_bias, dw, dbias,
-                               accumulate, out_scale);
-        else
-            hipLaunchKernelGGL((k_wgrad_reduce<2>), dim3(egrid(tq * 4)), dim3(128), 0, st, workspace, S, Mpad, Npad, Cout, Cin, KH, KW, a.has_bias, dw, dbias,
-                               accumulate, out_scale);
-    };
     // the RGB stem: patch kernel + the common slab reduction
-    if (KH == 7 && KW == 7 && stride == 2 && pad == 3 && pad_mode == 0 && Cin == 3 && Cout == 64 && C1 == Cin && up == 1 && !dbias &&
+    if (KH == 7 && KW == 7 && stride == 2 && pad == 3 && pad_mode == 0 && Cin == 3 && Cout == 64 && C1 == Cin && up == 1 && !o.dbias &&
         Ho == (Hs + 6 - 7) / 2 + 1 && Wo == (Ws + 6 - 7) / 2 + 1) {
         const int nxg = ((Wo + 31) / 32 + 1) / 2, ny = (Ho + 3) / 4;
         StemWgradArgs ta{dz, src0, workspace, B, Hs, Ws, Ho, Wo, 2, nxg, in_sub, in_mul};
         hipLaunchKernelGGL(k_wgrad7x7_stem, dim3(nxg, ny, B), dim3(256), 0, st, ta);
-        reduce(B * ny * nxg, 64, 148, 8);
-        E2E_LAUNCH_CHECK("e2e_conv2d_bwd_weight");
+        wgrad_reduce(a, o, B * ny * nxg, 64, 148, 8, st);
         return E2E_OK;
     }
     // the thin 3x3 layers of the decoder's last two levels (reflection pad, 16 / 32 output channels): patch kernel + the common slab reduction
@@ -3090,8 +3242,7 @@ static int bwd_weight_impl(const float* dz, const float* src0, const float* src1
         const dim3 tg((unsigned)t.nxg, (unsigned)t.ny, (unsigned)(B * (Cin / 16)));
         if (Cout == 32) hipLaunchKernelGGL((k_wgrad3x3_thin<2>), tg, dim3(256), 0, st, ta);
         else hipLaunchKernelGGL((k_wgrad3x3_thin<1>), tg, dim3(256), 0, st, ta);
-        reduce((int)t.S, Cout, t.npad, 8);
-        E2E_LAUNCH_CHECK("e2e_conv2d_bwd_weight");
+        wgrad_reduce(a, o, (int)t.S, Cout, t.npad, 8, st);
         return E2E_OK;
     }
     // the 32-channel-tile 3x3 layers (encoder stages, decoder upconv(k, 0) and the concat layers whose two sources are multiples of 32 wide):
@@ -3105,8 +3256,7 @@ static int bwd_weight_impl(const float* dz, const float* src0, const float* src1
         const dim3 tg((unsigned)(Cin / 32), (unsigned)(Cout / 32), (unsigned)t.S);
         if (a.has_bias) hipLaunchKernelGGL(k_wgrad3x3_taps<true>, tg, dim3(TAP_NT), 0, st, ta);
         else hipLaunchKernelGGL(k_wgrad3x3_taps<false>, tg, dim3(TAP_NT), 0, st, ta);
-        reduce(t.S, Cout, t.Npad, t.S >= 8 ? 8 : 2);
-        E2E_LAUNCH_CHECK("e2e_conv2d_bwd_weight");
+        wgrad_reduce(a, o, t.S, Cout, t.Npad, t.S >= 8 ? 8 : 2, st);
         return E2E_OK;
     }
     const bool use16 = lean && Cout == 16;
@@ -3117,26 +3267,45 @@ static int bwd_weight_impl(const float* dz, const float* src0, const float* src1
     const int64_t S = wp.S;
     const int cbp = lean ? 32 : CBK;
     a.pix_per_slice = ((P + S - 1) / S + cbp - 1) / cbp * cbp;
-    const int Sz = (int)((P + a.pix_per_slice - 1) / a.pix_per_slice);
-    dim3 g((unsigned)(a.Npad / tn), (unsigned)(a.Mpad / tm), (unsigned)Sz);
-    if (use16) {
+    L.Sz = (int)((P + a.pix_per_slice - 1) / a.pix_per_slice);
+    L.g = dim3((unsigned)(a.Npad / tn), (unsigned)(a.Mpad / tm), (unsigned)L.Sz);
+    L.k = use16 ? WK_GEMM16 : lean ? (tm == 32 ? WK_GEMM4_32 : WK_GEMM4_64) : (tm == 32 ? WK_GEMM_32 : WK_GEMM_64);
+    return E2E_OK;
+}
+
+static void wgrad_launch_gemm(const WgradArgs& a, const WgradLaunch& L, hipStream_t st) {
+    const dim3 g = L.g;
+    const bool two = a.src1 != nullptr;
+    if (L.k == WK_GEMM16) {
         hipLaunchKernelGGL((k_wgrad_gemm16<10, 32>), g, dim3(256), 0, st, a);
-    } else if (lean) {
-        if (tm == 32) {
-            if (src1) hipLaunchKernelGGL((k_wgrad_gemm4<1, 4, 32, true>), g, dim3(256), 0, st, a);
-            else hipLaunchKernelGGL((k_wgrad_gemm4<1, 4, 32, false>), g, dim3(256), 0, st, a);
-        } else {
-            if (src1) hipLaunchKernelGGL((k_wgrad_gemm4<2, 2, 32, true>), g, dim3(256), 0, st, a);
-            else hipLaunchKernelGGL((k_wgrad_gemm4<2, 2, 32, false>), g, dim3(256), 0, st, a);
-        }
-    } else if (tm == 32) {
-        if (vec == 4) hipLaunchKernelGGL((k_wgrad_gemm<1, 4, 4>), g, dim3(256), 0, st, a);
+    } else if (L.k == WK_GEMM4_32) {
+        if (two) hipLaunchKernelGGL((k_wgrad_gemm4<1, 4, 32, true>), g, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((k_wgrad_gemm4<1, 4, 32, false>), g, dim3(256), 0, st, a);
+    } else if (L.k == WK_GEMM4_64) {
+        if (two) hipLaunchKernelGGL((k_wgrad_gemm4<2, 2, 32, true>), g, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((k_wgrad_gemm4<2, 2, 32, false>), g, dim3(256), 0, st, a);
+    } else if (L.k == WK_GEMM_32) {
+        if (a.vec == 4) hipLaunchKernelGGL((k_wgrad_gemm<1, 4, 4>), g, dim3(256), 0, st, a);
         else hipLaunchKernelGGL((k_wgrad_gemm<1, 4, 1>), g, dim3(256), 0, st, a);
-    } else {
-        if (vec == 4) hipLaunchKernelGGL((k_wgrad_gemm<2, 2, 4>), g, dim3(256), 0, st, a);
+    } else if (L.k == WK_GEMM_64) {
+        if (a.vec == 4) hipLaunchKernelGGL((k_wgrad_gemm<2, 2, 4>), g, dim3(256), 0, st, a);
         else hipLaunchKernelGGL((k_wgrad_gemm<2, 2, 1>), g, dim3(256), 0, st, a);
     }
-    reduce(Sz, a.Mpad, a.Npad, Sz >= 8 ? 8 : 2);
+}
+
+static int bwd_weight_impl(const float* dz, const float* src0, const float* src1, int C1, int up, float* dw, float* dbias, float* workspace, int B,
+                           int Hs, int Ws, int Cin, int Cout, int Ho, int Wo, int KH, int KW, int stride, int pad, int pad_mode, int accumulate,
+                           float in_sub, float in_mul, const float* out_scale, void* stream, int wg_target = 0, e2e_wgrad_reduce_desc* defer = nullptr) {
+    const hipStream_t st = (hipStream_t)stream;
+    const WgradOut o{dw, dbias, out_scale, accumulate, defer};
+    WgradArgs a;
+    WgradLaunch L;
+    const int rc = wgrad_setup(dz, src0, src1, C1, up, workspace, B, Hs, Ws, Cin, Cout, Ho, Wo, KH, KW, stride, pad, pad_mode, in_sub, in_mul, wg_target, o, st, a, L);
+    if (rc != E2E_OK) return rc;
+    if (L.k != WK_DONE) {
+        wgrad_launch_gemm(a, L, st);
+        wgrad_reduce(a, o, L.Sz, a.Mpad, a.Npad, L.Sz >= 8 ? 8 : 2, st);
+    }
     E2E_LAUNCH_CHECK("e2e_conv2d_bwd_weight");
     return E2E_OK;
 }
@@ -3166,6 +3335,58 @@ int e2e_conv2d_bwd_weight_scaled_deferred(const float* da, const float* out_scal
     E2E_REQUIRE(desc_out, E2E_ERR_ARG, "e2e_conv2d_bwd_weight_scaled_deferred: desc_out is NULL");
     return bwd_weight_impl(da, src0, src1, C1, up, dw, dbias, workspace, B, Hs, Ws, Cin, Cout, Ho, Wo, KH, KW, stride, pad, pad_mode, accumulate,
                            in_sub, in_mul, out_scale, stream, 0, desc_out);
+}
+
+/* A layer's backward-data (e2e_conv2d_bwd_data_fused; accumulate = 0, x_in = pre_add = NULL, in_act = 0 is e2e_conv2d_bwd_data) and its
+ * backward-weight (e2e_conv2d_bwd_weight_scaled_deferred) on the same gradient `da`.  Each half takes the decomposition its own entry point
+ * takes; where both main GEMM launches are ones k_conv_bwd_pair carries, they run as ONE launch (wgrad_first: which tile set comes first
+ * in its grid), followed by the backward-data split-K epilogue, if any.  Every other combination runs the two launch sequences one after
+ * the other.  Bit-identical to the two separate calls either way. */
+int e2e_conv2d_bwd_pair_deferred(const float* da, const float* w_bwd, int ld_bwd, float* dxp, int B, int Hs, int Ws, int Cin, int Cout, int Ho, int Wo,
+                                 int KH, int KW, int stride, int pad, int pad_mode, int accumulate, const float* x_in, int in_act, const float* pre_add,
+                                 float* workspace, const float* out_scale, const float* src0, const float* src1, int C1, int up, float* dw, float* dbias,
+                                 float* workspace_w, int accumulate_w, float in_sub, float in_mul, e2e_wgrad_reduce_desc* desc_out, int wgrad_first,
+                                 void* stream) {
+    E2E_REQUIRE(desc_out, E2E_ERR_ARG, "e2e_conv2d_bwd_pair_deferred: desc_out is NULL");
+    const hipStream_t st = (hipStream_t)stream;
+    ConvArgs ad;
+    bool data_done;
+    int rc = bwd_data_setup(da, w_bwd, ld_bwd, dxp, B, Hs, Ws, Cin, Cout, Ho, Wo, KH, KW, stride, pad, pad_mode, accumulate, x_in, in_act, pre_add,
+                            GemmCfg{0, 0, 0}, st, ad, data_done);
+    if (rc != E2E_OK) return rc;
+    const WgradOut o{dw, dbias, out_scale, accumulate_w, desc_out};
+    WgradArgs aw;
+    WgradLaunch lw;
+    rc = wgrad_setup(da, src0, src1, C1, up, workspace_w, B, Hs, Ws, Cin, Cout, Ho, Wo, KH, KW, stride, pad, pad_mode, in_sub, in_mul, 0, o, st, aw, lw);
+    if (rc != E2E_OK) return rc;
+    GemmLaunch pd{};
+    if (!data_done) pd = plan_gemm<true>(ad, 4, workspace, GemmCfg{0, 0, 0});
+    const bool d14 = pd.c.bm == 32 && pd.c.bn == 128, d22 = pd.c.bm == 64 && pd.c.bn == 64;
+    const bool paired = !data_done && pd.kind == GK_TILE && pd.cb == 32 && (d14 || d22) && lw.k == WK_GEMM4_64;
+    if (paired) {
+        PairGrid pg;
+        pg.dgx = pd.g.x; pg.dgy = pd.g.y; pg.dgz = pd.g.z;
+        pg.wgx = lw.g.x; pg.wgy = lw.g.y; pg.wgz = lw.g.z;
+        const unsigned nd = pg.dgx * pg.dgy * pg.dgz, nw = pg.wgx * pg.wgy * pg.wgz;
+        pg.wgrad_first = wgrad_first ? 1 : 0;
+        pg.first = ((wgrad_first ? nw : nd) + 7u) / 8u * 8u;
+        const dim3 g(pg.first + (wgrad_first ? nd : nw));
+        const bool two = aw.src1 != nullptr;
+        if (d14) {
+            if (two) hipLaunchKernelGGL((k_conv_bwd_pair<1, 4, true>), g, dim3(256), 0, st, ad, aw, pg);
+            else hipLaunchKernelGGL((k_conv_bwd_pair<1, 4, false>), g, dim3(256), 0, st, ad, aw, pg);
+        } else {
+            if (two) hipLaunchKernelGGL((k_conv_bwd_pair<2, 2, true>), g, dim3(256), 0, st, ad, aw, pg);
+            else hipLaunchKernelGGL((k_conv_bwd_pair<2, 2, false>), g, dim3(256), 0, st, ad, aw, pg);
+        }
+    } else {
+        if (!data_done) launch_gemm_main<true>(ad, pd, workspace, st);
+        if (lw.k != WK_DONE) wgrad_launch_gemm(aw, lw, st);
+    }
+    if (!data_done) launch_gemm_tail(ad, pd, st);
+    if (lw.k != WK_DONE) wgrad_reduce(aw, o, lw.Sz, aw.Mpad, aw.Npad, lw.Sz >= 8 ? 8 : 2, st);
+    E2E_LAUNCH_CHECK("e2e_conv2d_bwd_pair_deferred");
+    return E2E_OK;
 }
 
 /* fills first_item of n descriptors in HOST memory (running total of work items); returns the total, or -1 on a malformed descriptor */

@@ -131,6 +131,8 @@ SIGNATURES = {
     "e2e_conv2d_gather_adjoint_act": [c_fp] + [c_int] * 7 + [c_fp, c_fp, c_int, c_int, c_fp, c_int, c_fp, c_int, c_fp],
     "e2e_conv2d_bwd_weight_scaled": [c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_fp, c_fp, c_fp] + [c_int] * 13 + [c_f32, c_f32, c_fp],
     "e2e_conv2d_bwd_weight_scaled_deferred": [c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_fp, c_fp, c_fp] + [c_int] * 13 + [c_f32, c_f32, ctypes.POINTER(WgradReduceDesc), c_fp],
+    "e2e_conv2d_bwd_pair_deferred": [c_fp, c_fp, c_int, c_fp] + [c_int] * 13 + [c_fp, c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_fp, c_fp, c_fp,
+                                     c_int, c_f32, c_f32, ctypes.POINTER(WgradReduceDesc), c_int, c_fp],
     "e2e_wgrad_reduce_batch_prepare": [ctypes.POINTER(WgradReduceDesc), c_int],
     "e2e_wgrad_reduce_batched": [c_fp, c_int, ctypes.c_longlong, c_fp],
     "e2e_copy_batch_prepare": [ctypes.POINTER(CopyDesc), c_int],

@@ -24,6 +24,7 @@ Backward conventions
     `overlap=True` it goes to a second stream (fork / join inside the captured graph).
 """
 import ctypes
+import os
 
 import torch
 
@@ -31,6 +32,9 @@ from . import _lib as L
 from .conv import ACT, _ld, epoch_sum
 
 _f32 = torch.float32
+# the paired backward (e2e_conv2d_bwd_pair_deferred) puts the backward-data tiles first in its grid: 6.5 % against 4.3 % for the other
+# order over the backward GEMMs of a pass (tools/bwd_pair_ab.py, profiles/r05_bwd_pair_ab.txt)
+PAIR_WGRAD_FIRST = 0
 
 
 class Buf:
@@ -128,6 +132,19 @@ class _Conv:
             # residual branch: its tensor's pre-activation gradient (+)= g * act_res'(.)
             L.call("e2e_conv2d_act_bwd_acc", L.ptr(g), L.ptr(s.res.t), None, L.ptr(s.res.g), n, s.Cout, s.res.act, 1 if s.res.written else 0, st)
             s.res.written = True
+        if s.need_dx and plan.paired and not plan.overlap:
+            # backward-data and backward-weight of this layer as one launch (e2e_conv2d_bwd_pair_deferred: bit-identical to the two calls below)
+            pre = s.pre_from.out.g if (s.direct and s.pre_from is not None) else None
+            L.call("e2e_conv2d_bwd_pair_deferred", L.ptr(g), L.ptr(s.wb), s.ldb, L.ptr(s.src0.g if s.direct else s.dxp), B, s.Hs, s.Ws, s.Cin, s.Cout,
+                   s.Ho, s.Wo, s.KH, s.KW, s.stride, s.pad, s.pm, (1 if s.src0.written else 0) if s.direct else 0, L.ptr(s.src0.t) if s.direct else None,
+                   s.src0.act if s.direct else 0, L.ptr(pre), L.ptr(s.ws_b), L.ptr(s.scale), L.ptr(s.src0.t), L.ptr(s.src1.t) if s.src1 is not None else None,
+                   s.C1, s.up, L.ptr(plan.sink(s.weight)), L.ptr(plan.sink(s.bias)) if s.bias is not None else None, L.ptr(s.ws_w), 0, float(s.isub),
+                   float(s.imul), ctypes.byref(s.reduce_desc), PAIR_WGRAD_FIRST, st)
+            if s.direct:
+                s.src0.written = True
+            else:
+                self._gather_adjoint(st)
+            return
         if s.need_dx:
             if s.direct:
                 pre = s.pre_from.out.g if s.pre_from is not None else None       # the block's residual gradient: same tensor, same act'
@@ -137,19 +154,23 @@ class _Conv:
             else:
                 L.call("e2e_conv2d_bwd_data", L.ptr(g), L.ptr(s.wb), s.ldb, L.ptr(s.dxp), B, s.Hs, s.Ws, s.Cin, s.Cout, s.Ho, s.Wo, s.KH, s.KW, s.stride,
                        s.pad, s.pm, L.ptr(s.ws_b), st)
-                s1 = s.src1
-                L.call("e2e_conv2d_gather_adjoint_act", L.ptr(s.dxp), B, s.Hs, s.Ws, s.Cin, s.C1, s.up, 1 if s.pp else 0, L.ptr(s.src0.g),
-                       L.ptr(s1.g) if s1 is not None else None, 1 if s.src0.written else 0, 1 if (s1 is not None and s1.written) else 0,
-                       L.ptr(s.src0.t), s.src0.act, L.ptr(s1.t) if s1 is not None else None, s1.act if s1 is not None else 0, st)
-                s.src0.written = True
-                if s1 is not None:
-                    s1.written = True
+                self._gather_adjoint(st)
         st_w = plan.fork(st)
         # the GEMM leaves its partial slabs in this layer's own workspace; the ~30 slab reductions of a pass are ONE launch at its end
         # (NetPlan._reduce_weight_gradients): each was 5 - 15 us of launch latency on an almost empty GPU
         L.call("e2e_conv2d_bwd_weight_scaled_deferred", L.ptr(g), L.ptr(s.scale), L.ptr(s.src0.t), L.ptr(s.src1.t) if s.src1 is not None else None, s.C1, s.up,
                L.ptr(plan.sink(s.weight)), L.ptr(plan.sink(s.bias)) if s.bias is not None else None, L.ptr(s.ws_w), B, s.Hs, s.Ws, s.Cin, s.Cout, s.Ho,
                s.Wo, s.KH, s.KW, s.stride, s.pad, s.pm, 0, float(s.isub), float(s.imul), ctypes.byref(s.reduce_desc), st_w)
+
+    def _gather_adjoint(self, st):
+        """dxp (the padded / upsampled / concatenated input domain) -> the gradients of the layer's sources."""
+        s, s1 = self, self.src1
+        L.call("e2e_conv2d_gather_adjoint_act", L.ptr(s.dxp), s.src0.B, s.Hs, s.Ws, s.Cin, s.C1, s.up, 1 if s.pp else 0, L.ptr(s.src0.g),
+               L.ptr(s1.g) if s1 is not None else None, 1 if s.src0.written else 0, 1 if (s1 is not None and s1.written) else 0,
+               L.ptr(s.src0.t), s.src0.act, L.ptr(s1.t) if s1 is not None else None, s1.act if s1 is not None else 0, st)
+        s.src0.written = True
+        if s1 is not None:
+            s1.written = True
 
 
 class _Head:
@@ -228,6 +249,9 @@ class NetPlan:
         frozen or -- the downsample ones -- with a trainable affine).  Input: (B,H,W,3) NHWC frames in [0,1]."""
         from depth_estimation.networks import BasicBlock
         self.model, self.dev, self.overlap = model, torch.device(device), overlap
+        # one-stream plan: each layer's backward-data and backward-weight GEMMs run as one launch; E2E_PAIRED_BWD=0 issues them separately
+        # (A/B comparison, bisecting -- results are bit-identical either way)
+        self.paired = os.environ.get("E2E_PAIRED_BWD", "1") != "0"
         self.B, self.H, self.W = B, H, W
         if H % 32 or W % 32:
             raise ValueError(f"launch plan: the encoder halves the image five times and the decoder doubles it back before every skip "

@@ -543,6 +543,18 @@ int e2e_conv2d_bwd_weight_scaled_deferred(const float* da, const float* out_scal
                                           int Wo, int KH, int KW, int stride, int pad, int pad_mode,
                                           int accumulate, float in_sub, float in_mul,
                                           e2e_wgrad_reduce_desc* desc_out_host, void* stream);
+/* A layer's backward-data (the arguments of e2e_conv2d_bwd_data_fused; accumulate = 0, x_in = pre_add = NULL, in_act = 0 give
+ * e2e_conv2d_bwd_data) and its backward-weight (those of e2e_conv2d_bwd_weight_scaled_deferred) on the same gradient `da`, as ONE GEMM
+ * launch where the decompositions both entry points choose allow it (wgrad_first: the backward-weight tiles come first in the grid),
+ * otherwise as the two launch sequences.  Results are bit-identical to the two separate calls. */
+int e2e_conv2d_bwd_pair_deferred(const float* da, const float* w_bwd, int ld_bwd, float* dxp, int B, int Hs,
+                                 int Ws, int Cin, int Cout, int Ho, int Wo, int KH, int KW, int stride,
+                                 int pad, int pad_mode, int accumulate, const float* x_in, int in_act,
+                                 const float* pre_add, float* workspace, const float* out_scale,
+                                 const float* src0, const float* src1, int C1, int up, float* dw,
+                                 float* dbias, float* workspace_w, int accumulate_w, float in_sub,
+                                 float in_mul, e2e_wgrad_reduce_desc* desc_out_host, int wgrad_first,
+                                 void* stream);
 long long e2e_wgrad_reduce_batch_prepare(e2e_wgrad_reduce_desc* descs_host, int n);
 int e2e_wgrad_reduce_batched(const e2e_wgrad_reduce_desc* descs_dev, int n, long long total_items, void* stream);
 
