@@ -397,8 +397,29 @@ __device__ __forceinline__ void conv_gemm_body(const ConvArgs& a, const Ids& wg,
         by = rem - bx * wg.gy();
     }
     const int64_t n0 = (int64_t)(CLS ? (bx >> 2) : bx) * BM;
-    if (CLS && (n0 >= Ntot || nkh <= 0 || nkw <= 0)) return;        // classes are sized by the largest one; empty tap sets write nothing (output pre-zeroed by the host for KH < 2)
     const int c0 = by * BN;
+    if (CLS && n0 >= Ntot) return;                                  // classes are sized by the largest one
+    if (CLS && (nkh <= 0 || nkw <= 0)) {
+        // a class no tap reaches (1x1 kernels): the GEMM term is zero there -- the host pre-zeroes dxp unless it accumulates -- but with a
+        // pre-activation addend the contract still gives dxp (+)= pre_add * act'(x_in) at these pixels
+        if (a.pre) {
+            const int hw_c = Hc * Wc;
+            const float inv_hw_c = 1.0f / (float)hw_c, inv_w_c = 1.0f / (float)Wc;
+            for (int i = tid; i < BM * BN; i += NT) {
+                const int64_t n = n0 + i / BN;
+                const int col = c0 + i % BN;
+                if (n >= Ntot || col >= a.Ncols) continue;
+                int b, yc, xc;
+                decode_row((int)n, hw_c, Wc, inv_hw_c, inv_w_c, b, yc, xc);
+                const int64_t e = (((int64_t)b * a.Hd + 2 * yc + py) * a.Wd + 2 * xc + px) * a.Ncols + col;
+                float v = a.pre[e];
+                if (a.dact) v *= act_deriv(a.xin[e], a.dact);
+                if (a.res) v += a.res[e];
+                a.out[e] = v;
+            }
+        }
+        return;
+    }
     const int K = CLS ? nkh * nkw * a.Cin : a.KH * a.KW * a.Cin;
     const int nchunks_all = (K + CB - 1) / CB;
     const int cbeg = (a.ksplit > 1) ? bz * a.cps : 0;
@@ -2227,14 +2248,15 @@ __device__ __forceinline__ void wgrad_reduce_group(const float* __restrict__ sla
         f4v t = part[0][e];
 #pragma unroll
         for (int j = 1; j < ZL; ++j) t += part[j][e];
-        if (scale) t *= scale[m];
+        const float sc = scale ? scale[m] : 1.f;          // the weight gradient only: the bias rides in the forward's shift, d bias = sum dA
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const int nn = n + k;
             if (nn < Kconv) {
                 const int tap = nn / Cin, ci = nn - tap * Cin, kh = tap / KW, kw = tap - kh * KW;
                 float* d = dw + (((int64_t)m * Cin + ci) * KH + kh) * KW + kw;
-                *d = accumulate ? *d + t[k] : t[k];
+                const float v = scale ? t[k] * sc : t[k];
+                *d = accumulate ? *d + v : v;
             } else if (nn == Kconv && dbias) {
                 dbias[m] = accumulate ? dbias[m] + t[k] : t[k];
             }
@@ -3225,8 +3247,9 @@ static int wgrad_setup(const float* dz, const float* src0, const float* src1, in
     const int64_t P = (int64_t)B * Ho * Wo;
     // lean VEC-4 kernel: 32 pixels per chunk; needs Cout % 4 == 0, 32-bit offsets and image rows of at least 8 pixels
     const bool lean = vec == 4 && Cout % 4 == 0 && Wo >= 8 && (int64_t)B * Hs * Ws * Cin * 4 < (1ll << 31) && P * Cout * 4 < (1ll << 31) && P < (1ll << 24);
-    // the RGB stem: patch kernel + the common slab reduction
-    if (KH == 7 && KW == 7 && stride == 2 && pad == 3 && pad_mode == 0 && Cin == 3 && Cout == 64 && C1 == Cin && up == 1 && !o.dbias &&
+    // the RGB stem: patch kernel + the common slab reduction (untuned calls only: a tuned call runs the implicit GEMM, and its workspace query
+    // does not cover the stem's slabs)
+    if (!tuned && KH == 7 && KW == 7 && stride == 2 && pad == 3 && pad_mode == 0 && Cin == 3 && Cout == 64 && C1 == Cin && up == 1 && !o.dbias &&
         Ho == (Hs + 6 - 7) / 2 + 1 && Wo == (Ws + 6 - 7) / 2 + 1) {
         const int nxg = ((Wo + 31) / 32 + 1) / 2, ny = (Ho + 3) / 4;
         StemWgradArgs ta{dz, src0, workspace, B, Hs, Ws, Ho, Wo, 2, nxg, in_sub, in_mul};

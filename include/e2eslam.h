@@ -519,7 +519,8 @@ int e2e_conv2d_bwd_weight(const float* dz, const float* src0, const float* src1,
                           int pad_mode, int accumulate, float in_sub, float in_mul, void* stream);
 
 /* the same on `da` = the gradient BEFORE a folded BatchNorm scale: dW[co] = out_scale[co] * sum_p da[p,co] x[p,...] (the scale is
- * applied once per output element in the slab reduction instead of once per pixel in a separate pass); out_scale may be NULL. */
+ * applied once per output element in the slab reduction instead of once per pixel in a separate pass); out_scale may be NULL.
+ * dbias[co] = sum_p da[p,co], without the scale: the forward is out_scale * conv + shift, and the bias travels in the shift. */
 int e2e_conv2d_bwd_weight_scaled(const float* da, const float* out_scale, const float* src0,
                                  const float* src1, int C1, int up, float* dw, float* dbias,
                                  float* workspace, int B, int Hs, int Ws, int Cin, int Cout, int Ho,
