@@ -460,6 +460,131 @@ __global__ __launch_bounds__(PF_T) void k_pf_append(int64_t N, int64_t M, const 
         }
 }
 
+// ---------------------------------------------------------------------------------------------
+// K14a: aggregation map step (gradslam update_map_aggregate: ICPSLAM._map).  Every pixel with depth != 0 becomes one map row
+// {global vertex, global normal, colour, alpha}, in row-major pixel order, behind the live rows.  ONE kernel computes the row from
+// depth / K / pose and writes it: the (H,W,3) vertex and normal maps and alpha of k_vertex_normal_maps (28 B per pixel written, then
+// read back by k_pf_append) never exist.  The expressions are those of k_vertex_normal_maps for a valid pixel, in its order, so a row
+// is bit-identical to the one k_vertex_normal_maps + k_pf_append produce (tests/test_gpu_frame_append.py); keep the two in step.
+//
+// Ordered compaction, CP_BLOCK pixels per workgroup, lane = pixel (coalesced rows of depth / rgb), FA_ROUNDS rounds:
+//   k_fa_count  : valid pixels per workgroup                                        -> counts[nb]
+//   k_fa_append : every workgroup sums counts[0 .. blockIdx) itself (nb <= a few hundred words out of L2; nobody waits on anybody),
+//                 orders its own pixels with wave ballots, computes and writes the rows below `cap`
+//   k_fa_commit : needed = M + sum(counts); the commit of k_pf_commit
+// ---------------------------------------------------------------------------------------------
+#define FA_ROUNDS CP_ITEMS
+
+__global__ __launch_bounds__(PF_T) void k_fa_count(const float* __restrict__ depth, int64_t N, unsigned int* __restrict__ counts) {
+    __shared__ unsigned int sh[PF_T / 64];
+    const int64_t base = (int64_t)blockIdx.x * CP_BLOCK + threadIdx.x;
+    unsigned int c = 0;
+#pragma unroll
+    for (int r = 0; r < FA_ROUNDS; ++r) {
+        const int64_t i = base + r * PF_T;
+        if (i < N && depth[i] != 0.f) ++c;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) counts[blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
+}
+
+__global__ __launch_bounds__(PF_T) void k_fa_append(const float* __restrict__ depth, const float* __restrict__ rgb,
+                                                    const float* __restrict__ K, const float* __restrict__ pose, float alpha_den,
+                                                    const unsigned int* __restrict__ counts, float* __restrict__ pts,
+                                                    float* __restrict__ nrm, float* __restrict__ col, float* __restrict__ cc,
+                                                    const long long* __restrict__ Mp, int64_t cap, int H, int W) {
+    __shared__ unsigned int sh_before[PF_T / 64];
+    __shared__ unsigned int sh_wave[FA_ROUNDS * (PF_T / 64)];
+    const int64_t N = (int64_t)H * W;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    // rows of the workgroups before this one
+    unsigned int before = 0;
+    for (int j = threadIdx.x; j < (int)blockIdx.x; j += PF_T) before += counts[j];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) before += __shfl_down(before, o, 64);
+    if (lane == 0) sh_before[wave] = before;
+    // this workgroup's pixels: round r, wave w, lane l = pixel blockIdx * CP_BLOCK + r * PF_T + w * 64 + l
+    const int64_t base = (int64_t)blockIdx.x * CP_BLOCK + threadIdx.x;
+    float d[FA_ROUNDS];
+    unsigned int rank[FA_ROUNDS];
+#pragma unroll
+    for (int r = 0; r < FA_ROUNDS; ++r) {
+        const int64_t i = base + r * PF_T;
+        d[r] = (i < N) ? depth[i] : 0.f;
+        const unsigned long long m = __ballot(d[r] != 0.f);
+        rank[r] = (unsigned int)__popcll(m & ((1ull << lane) - 1ull));
+        if (lane == 0) sh_wave[r * (PF_T / 64) + wave] = (unsigned int)__popcll(m);
+    }
+    __syncthreads();
+    int64_t row = (int64_t)*Mp + ((sh_before[0] + sh_before[1]) + (sh_before[2] + sh_before[3]));
+
+    const float fx = K[0], fy = K[5], cx = K[2], cy = K[6];
+    const float kx = 1.0f / fx, ky = 1.0f / fy, kxc = -cx / fx, kyc = -cy / fy;     // oracle intrinsics_inverse
+    const Pose P = load_pose(pose);
+#pragma unroll
+    for (int r = 0; r < FA_ROUNDS; ++r) {
+        unsigned int woff = 0;
+        for (int w = 0; w < wave; ++w) woff += sh_wave[r * (PF_T / 64) + w];
+        const int64_t dst = row + woff + rank[r];
+#pragma unroll
+        for (int w = 0; w < PF_T / 64; ++w) row += sh_wave[r * (PF_T / 64) + w];
+        if (d[r] == 0.f || dst >= cap) continue;        // (d == 0 covers i >= N)
+        const int i = (int)(base + r * PF_T);
+        const int h = i / W, w = i - h * W;
+        float v0[3], vr[3], vd[3];
+        local_vertex(d[r], kx, kxc, ky, kyc, w, h, v0);
+        float dh[3] = {0.f, 0.f, 0.f}, dv[3] = {0.f, 0.f, 0.f};
+        if (w + 1 < W) {
+            local_vertex(depth[i + 1], kx, kxc, ky, kyc, w + 1, h, vr);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) dh[c] = vr[c] - v0[c];
+        }
+        if (h + 1 < H) {
+            local_vertex(depth[i + W], kx, kxc, ky, kyc, w, h + 1, vd);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) dv[c] = vd[c] - v0[c];
+        }
+        float n[3];
+        n[0] = dh[1] * dv[2] - dh[2] * dv[1];
+        n[1] = dh[2] * dv[0] - dh[0] * dv[2];
+        n[2] = dh[0] * dv[1] - dh[1] * dv[0];
+        const float len = sqrt_rn((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]);
+        const float den = (len == 0.f) ? 1.f : len;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) n[c] = n[c] / den;
+        float vg[3], ng[3];
+        rot(P.R, v0, vg);
+        rot(P.R, n, ng);
+        const float s = (v0[0] * v0[0] + v0[1] * v0[1]) + v0[2] * v0[2];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            pts[dst * 3 + c] = vg[c] + P.t[c];
+            nrm[dst * 3 + c] = ng[c];
+            col[dst * 3 + c] = rgb[(int64_t)i * 3 + c];
+        }
+        cc[dst] = expf(-s / alpha_den);
+    }
+}
+
+__global__ __launch_bounds__(PF_T) void k_fa_commit(const unsigned int* __restrict__ counts, int nb, long long* __restrict__ count, long long cap) {
+    __shared__ unsigned int sh[PF_T / 64];
+    unsigned int c = 0;
+    for (int j = threadIdx.x; j < nb; j += PF_T) c += counts[j];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const long long m = count[0] + (long long)((sh[0] + sh[1]) + (sh[2] + sh[3]));
+        count[1] = m;
+        if (m > cap) count[2] = m;
+        count[0] = m > cap ? cap : m;
+    }
+}
+
 __global__ void k_fill_u32(unsigned int* p, int64_t n, unsigned int v) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) p[i] = v;
 }
@@ -741,6 +866,26 @@ int e2e_pf_fuse_append_dev(float* map_points, float* map_normals, float* map_col
                        map_normals, map_colors, map_ccounts, map_capacity, (const long long*)map_count_dev);
     hipLaunchKernelGGL(k_pf_commit, dim3(1), dim3(1), 0, st, map_count_dev, (long long)map_capacity);
     E2E_LAUNCH_CHECK("e2e_pf_fuse_append_dev");
+    return E2E_OK;
+}
+
+/* Aggregation map step on a RESIDENT map (gradslam update_map_aggregate): every pixel of the frame with depth != 0 is appended, no
+ * association, no fusion.  map_count_dev as in e2e_pf_fuse_append_dev.  Three launches, every argument constant between keyframes. */
+int e2e_frame_append_dev(float* map_points, float* map_normals, float* map_colors, float* map_ccounts, long long* map_count_dev,
+                         int64_t map_capacity, const float* depth, const float* rgb, const float* K, const float* pose, float alpha_den,
+                         void* workspace, int H, int W, void* stream) {
+    E2E_REQUIRE(map_capacity > 0 && H > 0 && W > 0 && (int64_t)H * W * 3 < (1ll << 31), E2E_ERR_ARG, "e2e_frame_append_dev: bad sizes");
+    E2E_REQUIRE(map_points && map_normals && map_colors && map_ccounts && map_count_dev && depth && rgb && K && pose && workspace,
+                E2E_ERR_ARG, "e2e_frame_append_dev: null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    const PfWs w = pf_ws(workspace, map_capacity, H, W);
+    const int64_t N = (int64_t)H * W;
+    const int nb = (int)((N + CP_BLOCK - 1) / CP_BLOCK);
+    hipLaunchKernelGGL(k_fa_count, dim3(nb), dim3(PF_T), 0, st, depth, N, w.counts);
+    hipLaunchKernelGGL(k_fa_append, dim3(nb), dim3(PF_T), 0, st, depth, rgb, K, pose, alpha_den, (const unsigned int*)w.counts, map_points,
+                       map_normals, map_colors, map_ccounts, (const long long*)map_count_dev, map_capacity, H, W);
+    hipLaunchKernelGGL(k_fa_commit, dim3(1), dim3(PF_T), 0, st, (const unsigned int*)w.counts, nb, map_count_dev, (long long)map_capacity);
+    E2E_LAUNCH_CHECK("e2e_frame_append_dev");
     return E2E_OK;
 }
 

@@ -76,6 +76,7 @@ SIGNATURES = {
     "e2e_pf_fuse_append": [c_fp, c_fp, c_fp, c_fp, c_i64, c_i64, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_fp, c_fp],
     "e2e_pf_associate_dev": [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_f32, c_f32, c_fp, c_i64, c_int, c_int, c_fp],
     "e2e_pf_fuse_append_dev": [c_fp, c_fp, c_fp, c_fp, c_fp, c_i64, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_fp],
+    "e2e_frame_append_dev": [c_fp, c_fp, c_fp, c_fp, c_fp, c_i64, c_fp, c_fp, c_fp, c_fp, c_f32, c_fp, c_int, c_int, c_fp],
     "e2e_knn1_index_capacity_bytes": [c_i64, c_i64],
     "e2e_knn1_index_build_dev": [c_fp, c_fp, c_i64, c_i64, c_fp, c_fp],
     "e2e_knn1_index_query_dev": [c_fp, c_i64, c_i64, c_i64, c_fp, c_fp, c_fp, c_fp],

@@ -28,6 +28,7 @@ class FusionMap:
         self._knn = None
         self._knn_dirty = True
         self._frame = None                                  # preallocated frame maps of the resident step
+        self._alpha_den = None
         # thresholds: python doubles rounded to fp32 at the call, like a tensor-vs-float comparison in torch
         self.dist_th = float(dist_th)
         self.dot_th = math.cos(float(angle_th) * math.pi / 180.0)
@@ -146,6 +147,23 @@ class FusionMap:
         L.call("e2e_pf_fuse_append_dev", L.ptr(self.points), L.ptr(self.normals), L.ptr(self.colors), L.ptr(self.ccounts), L.ptr(self.count),
                self.cap, L.ptr(depth), L.ptr(m["Vg"]), L.ptr(m["ng"]), L.ptr(rgb), L.ptr(m["alpha"]), L.ptr(self.ws), self.H, self.W, st)
         self._M = None                                      # the device knows; the host asks when it needs to
+        self._assoc_M = None
+        self._knn_dirty = True
+
+    def append_resident(self, rgb, depth, K, pose):
+        """The aggregation map step (gradslam ICPSLAM._map = update_map_aggregate; MODEL.slam: ICPSLAM) in the form of step_resident:
+        every pixel with depth != 0 is appended in row-major order, nothing is associated or fused.  One fused kernel computes the rows
+        from depth / K / pose (e2e_frame_append_dev): no frame maps, no host read, no allocation, constant launch arguments.  The rows
+        are bit-identical to step_resident's on a map where nothing matches."""
+        if self._alpha_den is None:
+            from .ops import fusion_alpha_den
+            self._alpha_den = float(fusion_alpha_den(self.sigma))
+        for n, t in (("rgb", rgb), ("depth", depth), ("K", K), ("pose", pose)):
+            if not L.dev(t, n).is_contiguous():
+                raise ValueError(f"append_resident: {n} must be contiguous")
+        L.call("e2e_frame_append_dev", L.ptr(self.points), L.ptr(self.normals), L.ptr(self.colors), L.ptr(self.ccounts), L.ptr(self.count),
+               self.cap, L.ptr(depth), L.ptr(rgb), L.ptr(K), L.ptr(pose), self._alpha_den, L.ptr(self.ws), self.H, self.W, L.stream())
+        self._M = None
         self._assoc_M = None
         self._knn_dirty = True
 

@@ -280,43 +280,49 @@ class RefineStepPlan:
         self._run("fwd", self._forward)
         return self.depth
 
-    def update_map(self, fmap, first, prefetch=False):
+    def update_map(self, fmap, first, prefetch=False, aggregate=False):
         """The keyframe's PointFusion map step(s) (online_adaption.py:347-363 with the ground-truth poses) and the rebuild of the
         nearest-neighbour index over the grown map, from RESIDENT buffers -- the stashed frames and poses of the pair (stash_map_inputs),
         the median-scaled depths of the last forward (predict_depths), the intrinsics -- so that every launch argument is constant and the
         ~25 launches replay as one captured graph (issued eagerly they left the GPU idle ~8 us per launch: the host cannot run ahead of a
         replaying graph).  first: the map is empty, the previous keyframe's frame is fused before the new one's.
-        prefetch: the NEXT pair is already loaded (its source frame = this pair's target): forward its target frame concurrently."""
+        prefetch: the NEXT pair is already loaded (its source frame = this pair's target): forward its target frame concurrently.
+        aggregate: the frame step is ICPSLAM's (MODEL.slam: ICPSLAM; FusionMap.append_resident: every valid pixel appended, no fusion)."""
+        frame_step = fmap.append_resident if aggregate else fmap.step_resident
+
         def fn():
             if prefetch:
                 self._prefetch_fork()
             if first:
-                fmap.step_resident(self.map_rgb[0], self.depth[0, 0], self.K[0], self.map_pose_src[0])
-            fmap.step_resident(self.map_rgb[1], self.depth[1, 0], self.K[0], self.map_pose_tgt[0])
+                frame_step(self.map_rgb[0], self.depth[0, 0], self.K[0], self.map_pose_src[0])
+            frame_step(self.map_rgb[1], self.depth[1, 0], self.K[0], self.map_pose_tgt[0])
             fmap.knn_index(self.N)                                  # rebuilt in place from the device-resident point count
             if prefetch:
                 self._prefetch_join()
-        self._run(("map", bool(first), id(fmap), bool(prefetch)), fn)
+        self._run(("map", bool(first), id(fmap), bool(aggregate), bool(prefetch)), fn)
         fmap.mark_updated_on_device(index_current=True)
 
-    def update_map_odom(self, fmap, first, odometry, prefetch=False):
+    def update_map_odom(self, fmap, first, odometry, prefetch=False, aggregate=False):
         """update_map with the reference's default map step (configs/config.yaml:30 odom: gradicp; online_adaption.py:362 passes
         prev_frame): the new keyframe's pose comes from frame-to-model odometry against the map, started at the previous keyframe's
         pose, and the frame is fused with the ESTIMATED pose.  odometry: e2ehip.icp.ResidentOdometry over `fmap` -- source / target
         selection, index build and its numiters iterations incl. the 6x6 solves are launches over resident buffers, so the whole
         map step (odometry, fusion, rebuild of the nearest-neighbour index) replays as ONE captured graph.  The estimate is left in
-        odometry.pose (device)."""
+        odometry.pose (device).  aggregate: as update_map -- ICPSLAM shares the localisation (frame-to-model against the active map
+        points) and appends the frame with the estimated pose."""
+        frame_step = fmap.append_resident if aggregate else fmap.step_resident
+
         def fn():
             if prefetch:
                 self._prefetch_fork()
             if first:
-                fmap.step_resident(self.map_rgb[0], self.depth[0, 0], self.K[0], self.map_pose_src[0])
+                frame_step(self.map_rgb[0], self.depth[0, 0], self.K[0], self.map_pose_src[0])
             pose = odometry.run(self.depth[1, 0], self.K[0], self.map_pose_src[0])
-            fmap.step_resident(self.map_rgb[1], self.depth[1, 0], self.K[0], pose)
+            frame_step(self.map_rgb[1], self.depth[1, 0], self.K[0], pose)
             fmap.knn_index(self.N)
             if prefetch:
                 self._prefetch_join()
-        self._run(("map_odom", bool(first), id(fmap), id(odometry), bool(prefetch)), fn)
+        self._run(("map_odom", bool(first), id(fmap), id(odometry), bool(aggregate), bool(prefetch)), fn)
         fmap.mark_updated_on_device(index_current=True)
 
     def close(self):

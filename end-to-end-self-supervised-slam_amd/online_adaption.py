@@ -1,5 +1,5 @@
 """MI355X counterpart of the reference's final system, online_adaption.py: online depth refinement on keyframe
-pairs + PointFusion mapping, same class / method names and the same order of operations, but launched the
+pairs + PointFusion or ICPSLAM mapping (MODEL.slam), same class / method names and the same order of operations, but launched the
 MI355X way:
 
   * the keyframe pair goes through the depth network as ONE batch of two (BN is in eval mode);
@@ -13,7 +13,8 @@ MI355X way:
     (e2ehip.stepplan / e2ehip.netplan): no autograd graph, no allocator traffic, no host synchronisation in a step;
     `refinement_autograd` keeps the torch.autograd form of the same step (same kernels) for the off-by-default loss
     terms and as the cross-check of the plan;
-  * the global map is a resident e2ehip.FusionMap updated in place.
+  * the global map is a resident e2ehip.FusionMap updated in place (PointFusion: associate + fuse + append; ICPSLAM: one fused
+    append of every valid pixel).
 
 reference: online_adaption.py:39-57 (SLAM.__init__), :98-155 (model_init), :175-205, :207-257 (main),
 :259-327 (refinement), :329-366 (create_refined_pointcloud), :369-645 (losses).
@@ -110,8 +111,11 @@ class SLAM:
     def model_init(self):
         a = self.args
         self.models = {}
-        if a.MODEL.slam != "PointFusion":
-            raise NotImplementedError("MODEL.slam: only PointFusion is on the online-adaption path")
+        # the reference's two map steps (online_adaption.py:110-124): PointFusion associates and fuses, ICPSLAM appends every valid pixel
+        # (gradslam update_map_aggregate); both localise frame-to-model against the active map points
+        if a.MODEL.slam not in ("PointFusion", "ICPSLAM"):
+            raise ValueError("MODEL.slam must be PointFusion or ICPSLAM")
+        self.aggregate = a.MODEL.slam == "ICPSLAM"
         if a.MODEL.odom not in ("gt", "icp", "gradicp"):
             raise ValueError("MODEL.odom must be gt, icp or gradicp")
         self.estimated_poses = []          # (frame index, estimated pose, ground-truth pose) when odometry runs
@@ -126,6 +130,8 @@ class SLAM:
         self.train_params = list(self.models["depth"].parameters())
         self.optimizer = define_optim(a, self.train_params)
         self.schedular = define_schedular(a, self.optimizer)
+        # a pass fuses at most sequence_length frames (the first keyframe brings its source frame along) and a frame adds at most H*W rows
+        # -- exactly H*W under ICPSLAM, which appends every valid pixel -- so the default holds any pass by construction
         cap = int(getattr(a.MODEL, "map_capacity", 0)) or (self.sequence_length + 1) * self.H * self.W
         self.map = FusionMap(cap, self.H, self.W, self.device, a.MODEL.dist_th, a.MODEL.angle_th, a.MODEL.sigma)
         reg = a.LOSS.depth_regularizer_type if a.LOSS.depth_regularizer else None
@@ -339,13 +345,13 @@ class SLAM:
             #  back, as round 3 found for backward-weight next to backward-data; the sequential single-frame forward stays the default)
             prefetch = self.prefetch_forward and self.reuse_forward and next_pair[0] == cur
         if a.MODEL.odom == "gt":
-            sp.update_map(self.map, self.first_iter, prefetch=prefetch)
+            sp.update_map(self.map, self.first_iter, prefetch=prefetch, aggregate=self.aggregate)
         else:
             # MODEL.odom icp / gradicp (the reference's default, configs/config.yaml:30): frame-to-model odometry from the previous keyframe's
             # pose inside the same captured map step (e2ehip.icp.ResidentOdometry: no host round trip per iteration); the map is fused with
             # the ESTIMATED pose and the pose itself, which the reference drops (online_adaption.py:362-363), is kept for the trajectory error
             odo = self._odometry()
-            sp.update_map_odom(self.map, self.first_iter, odo, prefetch=prefetch)
+            sp.update_map_odom(self.map, self.first_iter, odo, prefetch=prefetch, aggregate=self.aggregate)
             self.estimated_poses.append((odo.pose.clone(), self.poses[0, cur]))
         # slots of the plan's batch that hold a complete forward pass made with the current weights: (frame in slot 0, frame in slot 1)
         self._forward_holds = (cur, next_pair[1]) if prefetch else (None, cur)
@@ -496,16 +502,18 @@ class SLAM:
 
     @torch.no_grad()
     def _update_map(self, rgb_prev, rgb_cur, depth, pose_prev, pose_cur):
-        """PointFusion map step(s) with the refined, median-scaled depths (2,1,H,W) of the pair (online_adaption.py:347-363)."""
+        """Map step(s) of MODEL.slam with the refined, median-scaled depths (2,1,H,W) of the pair (online_adaption.py:347-363)."""
         K = self.intrinsics[0, 0]
         if self.args.MODEL.odom == "gt":
             # resident form: map size, association tables and the appended rows never leave the device (no host read per keyframe)
+            frame_step = self.map.append_resident if self.aggregate else self.map.step_resident
             if self.first_iter:
-                self.map.step_resident(rgb_prev, depth[0, 0], K, pose_prev)
-            self.map.step_resident(rgb_cur, depth[1, 0], K, pose_cur)
+                frame_step(rgb_prev, depth[0, 0], K, pose_prev)
+            frame_step(rgb_cur, depth[1, 0], K, pose_cur)
             return self.map
+        frame_step = self.map.append_resident if self.aggregate else self.map.step
         if self.first_iter:
-            self.map.step(rgb_prev, depth[0, 0], K, pose_prev)
+            frame_step(rgb_prev, depth[0, 0], K, pose_prev)
         live_pose = pose_cur
         if self.args.MODEL.odom != "gt":
             # the reference passes prev_frame here (online_adaption.py:362-363): frame-to-model odometry from the
@@ -514,7 +522,7 @@ class SLAM:
             from e2ehip import icp
             live_pose, _ = icp.frame_to_model(self.map, depth[1, 0], K, pose_prev, numiters=self.args.MODEL.numiters, mode=self.args.MODEL.odom)
             self.estimated_poses.append((live_pose, pose_cur))
-        self.map.step(rgb_cur, depth[1, 0], K, live_pose)
+        frame_step(rgb_cur, depth[1, 0], K, live_pose.contiguous())
         return self.map
 
     def absolute_trajectory_error(self):

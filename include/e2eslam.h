@@ -303,6 +303,20 @@ int e2e_pf_fuse_append_dev(float* map_points, float* map_normals, float* map_col
                            long long* map_count_dev, int64_t map_capacity, const float* depth, const float* Vg,
                            const float* Ng, const float* rgb, const float* alpha, void* workspace, int H, int W,
                            void* stream);
+/* Aggregation map step (MODEL.slam: ICPSLAM, online_adaption.py:110-124; gradslam ICPSLAM._map = update_map_aggregate, SURVEY.md
+ * Appendix A) on the same resident map: every pixel of the live frame with depth != 0 becomes one row {global vertex, global normal,
+ * colour, alpha} at map_count_dev[0], in row-major pixel order -- no association, no fusion.  depth (H,W), rgb (H,W,3), K / pose (4,4)
+ * device fp32; alpha_den as for e2e_vertex_normal_maps.  Vertex, forward-difference normal and alpha are computed inside the kernel
+ * that writes the rows (no per-pixel intermediate in memory), with the expressions of e2e_vertex_normal_maps: the rows are
+ * bit-identical to e2e_vertex_normal_maps + e2e_pf_fuse_append_dev on a map where nothing matches.  Commit as
+ * e2e_pf_fuse_append_dev: [0] = min(needed, map_capacity), [1] = needed, [2] = needed when it exceeded map_capacity; nothing is
+ * written at or beyond map_capacity.  Three launches, all arguments constant between keyframes (capturable).
+ * Size range: meant for camera frames.  Each of the ceil(H*W / 1024) workgroups sums the counts of the workgroups before it
+ * (that is what keeps it at three launches with no workgroup waiting on another): H*W / 1024 squared / 2 four-byte reads out of L2 in
+ * total -- 45 000 at 480x640, 8 M at 4096x4096; quadratic beyond that, where a scan launch between count and append would be due. */
+int e2e_frame_append_dev(float* map_points, float* map_normals, float* map_colors, float* map_ccounts,
+                         long long* map_count_dev, int64_t map_capacity, const float* depth, const float* rgb,
+                         const float* K, const float* pose, float alpha_den, void* workspace, int H, int W, void* stream);
 
 /* ------------------------------------------------------------------------------------------ */
 /* chamferdist.knn_points, K = 1, D = 3 (loss/losses.py:3,57)                                   */
