@@ -388,7 +388,9 @@ int e2e_knn1_index_query_dev_image_warm(const float* p1, int64_t n1, int row_len
 /* torch.median over all elements (online_adaption.py:295,343): the LOWER median (rank (n-1)/2) by
  * radix select; *value_out (device).  workspace: e2e_median_workspace_bytes() bytes; afterwards it
  * also holds the smallest index whose value equals the median and the number of elements that hold it (used by
- * the scale chain's autograd). */
+ * the scale chain's autograd).  Values are ordered by their bit patterns: -0.0 sorts below +0.0, and a NaN is not propagated -- one
+ * with the sign bit clear sorts above +inf, one with it set below -inf, so the result is NaN only when the rank falls among them
+ * (torch.median returns NaN as soon as one is present; depths and disparities hold none). */
 int64_t e2e_median_workspace_bytes(void);
 int e2e_median_lower(const float* x, int64_t n, float* value_out, void* workspace, void* stream);
 
@@ -443,15 +445,16 @@ int e2e_adam_step(float* params, const float* grads, float* exp_avg, float* exp_
                   float lr, float beta1, float beta2, float eps, int step, void* stream);
 /* The data-parallel form (one sequence per GPU): `grad_sums` is the flat bucket after ONE all-reduce(SUM)
  * over the ranks, `participants` (device scalar, all-reduced as the bucket's extra tail element) the number of ranks that
- * took a refinement step; the update uses grad_sums / max(participants, 1).  participants == 1: identical to
- * e2e_adam_step. */
+ * took a refinement step; the update uses grad_sums / max(participants, 1), so every value <= 1 (0 included) leaves the
+ * gradient as it is.  participants == 1: identical to e2e_adam_step, bit for bit. */
 int e2e_adam_step_mean(float* params, const float* grad_sums, const float* participants, float* exp_avg,
                        float* exp_avg_sq, int64_t n, float lr, float beta1, float beta2, float eps,
                        int step, void* stream);
 /* The hipGraph-safe form: the step count lives on the device.  schedule (device, 8-byte aligned) holds for t = 1..len the
  * pair { lr / (1 - beta1^t), sqrt(1 - beta2^t) } exactly as the host computes it for e2e_adam_step (doubles rounded to
- * fp32); the launch uses entry step_counter[0] (1-based, clamped to len) and a second one-thread kernel advances the
- * counter, so a captured step replays through the bias corrections.  participants may be NULL (= 1). */
+ * fp32); the launch uses entry step_counter[0] (1-based, clamped to [1, len]: a counter of 0 or less reads the first row, one
+ * past len the last) and a second one-thread kernel advances the counter by exactly 1 whatever its value, so a captured step
+ * replays through the bias corrections.  participants may be NULL (= 1).  Equal inputs give e2e_adam_step's bits. */
 int e2e_adam_step_resident(float* params, const float* grad_sums, const float* participants, float* exp_avg,
                            float* exp_avg_sq, int64_t n, float beta1, float beta2, float eps,
                            const float* schedule, int schedule_len, int* step_counter, void* stream);
@@ -749,7 +752,8 @@ int e2e_masked_l1_lossgrad(const float* prediction, const float* sparse_gt, cons
                            void* stream);
 
 /* train_depth.py:657-661: mean over (b,y,x) of min over the C stacked error maps (B,C,H,W); the
- * gradient goes to the first minimal channel. */
+ * gradient goes to the first minimal channel.  A NaN wins the minimum like in torch.min (the first NaN channel takes the
+ * gradient, the loss is NaN). */
 int e2e_min_reprojection_lossgrad(const float* errors, int B, int C, int H, int W, float* loss_out,
                                   float* g_errors, float* workspace, void* stream);
 
@@ -767,12 +771,16 @@ int e2e_mean_normalize(const float* d, const float* g, int B, int H, int W, floa
 /* mean of values[i] over the elements whose gate[i] != 0, and weight x its gradient: the 3-D point loss
  * (online_adaption.py:638-645; loss/losses.py:57-63 `torch.mean(dists)`) over the valid-depth pixels without the
  * reference's boolean indexing (dynamic shape + host sync): gate = the depth map.  out3 = {mean, count, weight / count};
- * g_values (may be NULL) = weight * [gate != 0] / count.  workspace: e2e_aux_workspace_floats() floats. */
+ * g_values (may be NULL) = weight * [gate != 0] / count.  Every gate that compares unequal to zero selects -- negative, tiny and
+ * subnormal ones too; +0.0 and -0.0 do not.  An empty selection gives {NaN, 0, 0} and an all-zero gradient.
+ * workspace: e2e_aux_workspace_floats() floats. */
 int e2e_masked_mean_lossgrad(const float* values, const float* gate, int64_t n, float weight, float* out3,
                              float* g_values, float* workspace, void* stream);
 
 /* train_depth.py:224-237 process_disparity: disp_pair (2,1,H,W) = net(img), net(flip(img)) ->
- * out (1,1,H,W); bwd: g_out (H,W) -> g_disp_pair (2,1,H,W). */
+ * out (1,1,H,W); bwd: g_out (H,W) -> g_disp_pair (2,1,H,W).  With left = disp_pair[0], right = flip_w(disp_pair[1]),
+ * middle = (left + right) / 2 and the ROW mask l(y) = 1 - clip(20 (y / (H - 1) - 0.05), 0, 1) (y / (H - 1) = 0 for H = 1; the
+ * reference's meshgrid varies along rows, so its flipped mask r equals l):  out = l left + l right + (1 - 2 l) middle. */
 int e2e_disp_blend_fwd(const float* disp_pair, int H, int W, float* out, void* stream);
 int e2e_disp_blend_bwd(const float* g_out, int H, int W, float* g_disp_pair, void* stream);
 

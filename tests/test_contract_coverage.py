@@ -1,0 +1,25 @@
+"""Host-only: every entry point that include/e2eslam.h declares and csrc/depth_ops.hip, aux_losses.hip or nn_misc.hip implements is
+called by one of the two contract modules (tests/test_gpu_depth_aux_contracts.py, tests/test_gpu_nn_misc_contracts.py)."""
+import os
+import re
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "end-to-end-self-supervised-slam_amd", "csrc")
+
+
+def _read(*parts):
+    with open(os.path.join(*parts)) as f:
+        return f.read()
+
+
+def test_every_entry_point_of_the_three_files_has_a_contract_case():
+    declared = set(re.findall(r"^(?:int|int64_t|long long)\s+(e2e_\w+)\s*\(", _read(ROOT, "include", "e2eslam.h"), re.M))
+    implemented = set()
+    for name in ("depth_ops.hip", "aux_losses.hip", "nn_misc.hip"):
+        implemented |= set(re.findall(r"^(?:int|int64_t|long long)\s+(e2e_\w+)\s*\(", _read(CSRC, name), re.M))
+    names = declared & implemented
+    assert len(names) >= 37, sorted(names)                                # 15 + 11 + 11 at the time of writing: the greps still find them
+    assert implemented <= declared, sorted(implemented - declared)
+    tests = _read(ROOT, "tests", "test_gpu_depth_aux_contracts.py") + _read(ROOT, "tests", "test_gpu_nn_misc_contracts.py")
+    called = set(re.findall(r"[\"'.](e2e_\w+)[\"'(]", tests))
+    assert not names - called, f"no contract case calls {sorted(names - called)}"

@@ -57,6 +57,10 @@ def test_mean_diff_vs_golden(golden, kind):
     out.backward()
     if kind == "l2":
         torch.testing.assert_close(d1.grad.cpu(), g["greg_l2"], rtol=1e-5, atol=1e-9)
+    else:
+        # the golden file holds no greg_l1: d/d(d1) mean |d0 - d1| = -sign(d0 - d1) / n (one rounding, of 1 / n)
+        ref = -torch.sign(g["d0"].double() - g["d1"].double()) / g["d0"].numel()
+        torch.testing.assert_close(d1.grad.cpu().double(), ref, rtol=2.0 ** -23, atol=0)
     with pytest.raises(ValueError):
         ops.mean_diff(g["d0"].to(DEV), d1, "huber")
 
