@@ -100,7 +100,7 @@ class ResidentOdometry:
     """PointFusion._localize for the driver's resident map WITHOUT a host round trip: source / target selection, the nearest-neighbour
     index over the targets and the `numiters` Gauss-Newton (icp) or Levenberg-Marquardt (gradicp) iterations are a fixed sequence of
     launches over buffers allocated once -- sizes that depend on the map (live points, active points, targets) are device data -- so a
-    keyframe's odometry can sit inside the captured map-update graph (RefineStepPlan.update_map_odom).  Same arithmetic as
+    keyframe's odometry can sit inside the captured map-update graph (RefineStepPlan.update_map(odometry=...)).  Same arithmetic as
     frame_to_model / point_to_plane_icp above (which remain for ad-hoc clouds and as the cross-check) with the 6x6 solve, the se(3)
     exponential and the damping update in the e2e_icp_update kernel instead of numpy.
 

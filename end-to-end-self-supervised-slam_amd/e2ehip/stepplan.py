@@ -81,9 +81,6 @@ class RefineStepPlan:
         self.map_rgb = torch.empty(2, H, W, 3, **f)
         self.map_pose_src, self.map_pose_tgt = (torch.eye(4, **f).reshape(1, 4, 4).clone() for _ in range(2))
         self._pstream = None
-        # tests: device int32 indices (into the stacked (2,1,H,W) predictions) of the elements the CPU evaluation's torch.median holds
-        # as the median -- the ratio's gradient then lands on exactly those (e2e_depth_scale_bwd_at) instead of on this evaluation's own
-        self.median_elements_override = None
         self.net.refresh_layouts()
 
     # ---- per keyframe -----------------------------------------------------------------------------------------------------
@@ -128,10 +125,8 @@ class RefineStepPlan:
 
     # ---- the pieces -------------------------------------------------------------------------------------------------------
     def _forward(self):
-        st = L.stream()
-        disp = self.net.forward()
-        L.call("e2e_depth_scale_fwd", L.ptr(disp), L.ptr(self.median_gt), L.ptr(self.delta), L.ptr(self.depth), L.ptr(self.md), L.ptr(self.ratio),
-               L.ptr(self.ws_scale), disp.numel(), st)
+        self.net.forward()
+        self._scale_only()
 
     def stash_map_inputs(self):
         """Private copies of the loaded pair's frames and poses for the map step that follows (three device-to-device copies)."""
@@ -140,8 +135,9 @@ class RefineStepPlan:
         self.map_pose_tgt.copy_(self.pose_tgt)
 
     def _scale_only(self):
-        """First 'forward' of a keyframe whose two frames already went through the network with the current weights (the source frame in
-        the previous keyframe's map-update forward, the target frame next to that keyframe's map step: update_map(prefetch=True))."""
+        """1/disp of the pair in the network's output buffer, its median, the median-scaled depths: the tail of every forward, and the
+        whole first 'forward' of a keyframe whose two frames already went through the network with the current weights (the source frame
+        in the previous keyframe's map-update forward, the target frame next to that keyframe's map step: update_map(prefetch=True))."""
         disp = self.net.disp.t.view(2, 1, self.H, self.W)
         L.call("e2e_depth_scale_fwd", L.ptr(disp), L.ptr(self.median_gt), L.ptr(self.delta), L.ptr(self.depth), L.ptr(self.md), L.ptr(self.ratio),
                L.ptr(self.ws_scale), disp.numel(), L.stream())
@@ -166,12 +162,9 @@ class RefineStepPlan:
         (predict_depths, online_adaption.py:329-345) ran this very frame through these very weights -- no optimiser step lies between it and
         the first forward of the next keyframe (:281) -- so its activations are moved from batch slot 1 to slot 0 and only the new
         target frame goes through the network (1/8 of all forward work of a keyframe; the reference computes both frames again)."""
-        st = L.stream()
         self.net.move_slot(1, 0)
         self.net.forward_one(1)
-        disp = self.net.disp.t.view(2, 1, self.H, self.W)
-        L.call("e2e_depth_scale_fwd", L.ptr(disp), L.ptr(self.median_gt), L.ptr(self.delta), L.ptr(self.depth), L.ptr(self.md), L.ptr(self.ratio),
-               L.ptr(self.ws_scale), disp.numel(), st)
+        self._scale_only()
 
     def _loss3d(self, index, warm=False):
         """online_adaption.py:457-471 + :638-645: the target frame's cloud in world coordinates (its pose), transformed AGAIN by T
@@ -197,9 +190,7 @@ class RefineStepPlan:
         self.loss.step()                                            # losses -> self.loss.loss[0..1]; d/d depth -> self.g_depth
         if use_3d:                                                  # g_depth_tgt += d(w_3d * l3)/d depth_tgt
             L.call("e2e_conv2d_act_bwd_acc", L.ptr(self.g3), L.ptr(self.g3), None, L.ptr(self.g_depth[1:2]), self.N, 1, 0, 1, st)
-        ov = self.median_elements_override
-        L.call("e2e_depth_scale_bwd_at", L.ptr(self.g_depth), L.ptr(self.delta), L.ptr(self.median_gt), L.ptr(self.md), L.ptr(ov),
-               0 if ov is None else int(ov.numel()), L.ptr(self.net.disp.g), L.ptr(self.ws_scale), self.g_depth.numel(), st)
+        self._median_chain_backward(st)
         if self.flagged:
             # the smoothness term is a function of the source frame's DISPARITY (online_adaption.py:600-610), not of a depth: its
             # gradient joins d loss / d disp[0] after the median chain wrote that buffer, before the network's backward reads it
@@ -211,6 +202,15 @@ class RefineStepPlan:
         self.net.backward()
         if with_adam:
             self._adam()
+
+    def _median_chain_backward(self, st):
+        """d loss / d depth -> d loss / d disp through the scaling: the ratio's gradient is shared among the elements equal to the median."""
+        L.call("e2e_depth_scale_bwd", L.ptr(self.g_depth), L.ptr(self.delta), L.ptr(self.median_gt), L.ptr(self.md), L.ptr(self.net.disp.g),
+               L.ptr(self.ws_scale), self.g_depth.numel(), st)
+
+    def _backward_key(self, use_3d, ikey):
+        """Key of the captured single-GPU backward graph: everything that changes its launches or their arguments."""
+        return ("bwd", use_3d, True, ikey)
 
     def _adam(self):
         self.opt.step()
@@ -245,8 +245,7 @@ class RefineStepPlan:
             # (SLAM.compute_flagged_losses; online_adaption.py:498) and copied into the resident plane the captured launch reads
             self.loss.noise.copy_(torch.randn(self.loss.noise.shape, device=self.dev) * 0.00001)
         if not edist.data_parallel():
-            okey = None if self.median_elements_override is None else (self.median_elements_override.data_ptr(), self.median_elements_override.numel())
-            self._run(("bwd", use_3d, True, ikey, okey), lambda: self._backward(use_3d, True, index=cap_idx, warm=warm))
+            self._run(self._backward_key(use_3d, ikey), lambda: self._backward(use_3d, True, index=cap_idx, warm=warm))
         else:
             # data-parallel: the exchange of the bucket's tail (head, decoder, layer4: 80 % of the bytes, complete after the first
             # part of the backward pass) travels while the early layers' backward computes; then the remaining 20 %, then Adam
@@ -280,14 +279,19 @@ class RefineStepPlan:
         self._run("fwd", self._forward)
         return self.depth
 
-    def update_map(self, fmap, first, prefetch=False, aggregate=False):
-        """The keyframe's PointFusion map step(s) (online_adaption.py:347-363 with the ground-truth poses) and the rebuild of the
-        nearest-neighbour index over the grown map, from RESIDENT buffers -- the stashed frames and poses of the pair (stash_map_inputs),
-        the median-scaled depths of the last forward (predict_depths), the intrinsics -- so that every launch argument is constant and the
-        ~25 launches replay as one captured graph (issued eagerly they left the GPU idle ~8 us per launch: the host cannot run ahead of a
-        replaying graph).  first: the map is empty, the previous keyframe's frame is fused before the new one's.
+    def update_map(self, fmap, first, prefetch=False, aggregate=False, odometry=None):
+        """The keyframe's PointFusion map step(s) (online_adaption.py:347-363) and the rebuild of the nearest-neighbour index over the
+        grown map, from RESIDENT buffers -- the stashed frames and poses of the pair (stash_map_inputs), the median-scaled depths of the
+        last forward (predict_depths), the intrinsics -- so that every launch argument is constant and the ~25 launches replay as one
+        captured graph (issued eagerly they left the GPU idle ~8 us per launch: the host cannot run ahead of a replaying graph).
+        first: the map is empty, the previous keyframe's frame is fused before the new one's.
         prefetch: the NEXT pair is already loaded (its source frame = this pair's target): forward its target frame concurrently.
-        aggregate: the frame step is ICPSLAM's (MODEL.slam: ICPSLAM; FusionMap.append_resident: every valid pixel appended, no fusion)."""
+        aggregate: the frame step is ICPSLAM's (MODEL.slam: ICPSLAM; FusionMap.append_resident: every valid pixel appended, no fusion).
+        odometry: None fuses the new keyframe with its ground-truth pose.  An e2ehip.icp.ResidentOdometry over `fmap` is the reference's
+        default map step (configs/config.yaml:30 odom: gradicp; online_adaption.py:362 passes prev_frame): the pose comes from
+        frame-to-model odometry against the map, started at the previous keyframe's pose -- source / target selection, index build and
+        its numiters iterations incl. the 6x6 solves are launches over resident buffers, part of the same graph -- and the frame is fused
+        with the ESTIMATE, which is left in odometry.pose (device).  ICPSLAM shares the localisation (against the active map points)."""
         frame_step = fmap.append_resident if aggregate else fmap.step_resident
 
         def fn():
@@ -295,34 +299,13 @@ class RefineStepPlan:
                 self._prefetch_fork()
             if first:
                 frame_step(self.map_rgb[0], self.depth[0, 0], self.K[0], self.map_pose_src[0])
-            frame_step(self.map_rgb[1], self.depth[1, 0], self.K[0], self.map_pose_tgt[0])
+            pose = self.map_pose_tgt[0] if odometry is None else odometry.run(self.depth[1, 0], self.K[0], self.map_pose_src[0])
+            frame_step(self.map_rgb[1], self.depth[1, 0], self.K[0], pose)
             fmap.knn_index(self.N)                                  # rebuilt in place from the device-resident point count
             if prefetch:
                 self._prefetch_join()
-        self._run(("map", bool(first), id(fmap), bool(aggregate), bool(prefetch)), fn)
-        fmap.mark_updated_on_device(index_current=True)
-
-    def update_map_odom(self, fmap, first, odometry, prefetch=False, aggregate=False):
-        """update_map with the reference's default map step (configs/config.yaml:30 odom: gradicp; online_adaption.py:362 passes
-        prev_frame): the new keyframe's pose comes from frame-to-model odometry against the map, started at the previous keyframe's
-        pose, and the frame is fused with the ESTIMATED pose.  odometry: e2ehip.icp.ResidentOdometry over `fmap` -- source / target
-        selection, index build and its numiters iterations incl. the 6x6 solves are launches over resident buffers, so the whole
-        map step (odometry, fusion, rebuild of the nearest-neighbour index) replays as ONE captured graph.  The estimate is left in
-        odometry.pose (device).  aggregate: as update_map -- ICPSLAM shares the localisation (frame-to-model against the active map
-        points) and appends the frame with the estimated pose."""
-        frame_step = fmap.append_resident if aggregate else fmap.step_resident
-
-        def fn():
-            if prefetch:
-                self._prefetch_fork()
-            if first:
-                frame_step(self.map_rgb[0], self.depth[0, 0], self.K[0], self.map_pose_src[0])
-            pose = odometry.run(self.depth[1, 0], self.K[0], self.map_pose_src[0])
-            frame_step(self.map_rgb[1], self.depth[1, 0], self.K[0], pose)
-            fmap.knn_index(self.N)
-            if prefetch:
-                self._prefetch_join()
-        self._run(("map_odom", bool(first), id(fmap), id(odometry), bool(aggregate), bool(prefetch)), fn)
+        key = ("map", bool(first), id(fmap)) if odometry is None else ("map_odom", bool(first), id(fmap), id(odometry))
+        self._run(key + (bool(aggregate), bool(prefetch)), fn)
         fmap.mark_updated_on_device(index_current=True)
 
     def close(self):

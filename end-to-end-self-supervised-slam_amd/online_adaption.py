@@ -47,6 +47,8 @@ from utils.yaml_configs import load_yaml  # noqa: E402
 
 
 class SLAM:
+    step_plan_class = RefineStepPlan            # the launch plan a run builds (_step_plan)
+
     def __init__(self, arguments, sequence=None, state_dict=None):
         """arguments: the reference's config tree (configs/config.yaml).  sequence: optional pre-loaded
         (colors 0-1 (1,L,H,W,3), depths (1,L,H,W,1), intrinsics (1,1,4,4), poses (1,L,4,4)); default: synthetic."""
@@ -78,11 +80,6 @@ class SLAM:
         # LOSS.geometric / smoothness / auto_masking / min_reprojection on the launch plan (e2e_warp_photo_terms_lossgrad +
         # e2e_smoothness_norm_lossgrad inside the captured step) instead of refinement_autograd.  E2E_PLAN_LOSS_TERMS=1: on; default off
         self.plan_loss_terms = os.environ.get("E2E_PLAN_LOSS_TERMS", "0") == "1"
-        # test hooks (the median ELEMENT of the predictions is where two correct fp32 evaluations of this loop can part: among 614 400
-        # depths the median's neighbours lie ~1e-6 away; tests name one run's elements to the other and compare everything else):
-        # median_elements[k]: device int32 indices for refinement step k of this object; median_elements_log: filled when it is a list
-        self.median_elements = None
-        self.median_elements_log = None
         self._preloaded = None             # keyframe pair whose inputs already sit in the plan's buffers (refinement(next_pair=...))
 
     # ------------------------------------------------------------------------------------------------
@@ -265,10 +262,10 @@ class SLAM:
                 terms["w_geometric"] = a.LOSS.geometric_weight
             if "smoothness" in terms:
                 terms["w_smoothness"] = a.LOSS.smoothness_weight
-            self.step_plan = RefineStepPlan(self.models["depth"], self.optimizer, self.H, self.W, self.device, a.MODEL.padding_mode,
-                                            a.LOSS.photometric_mask, a.LOSS.depth_regularizer_type if use_reg else None,
-                                            a.LOSS.depth_regularizer_weight if use_reg else 0.0, a.LOSS.three3d_loss_weight, self.map.sigma,
-                                            overlap=self.overlap_wgrad, use_graphs=self.use_graphs, **terms)
+            self.step_plan = self.step_plan_class(self.models["depth"], self.optimizer, self.H, self.W, self.device, a.MODEL.padding_mode,
+                                                 a.LOSS.photometric_mask, a.LOSS.depth_regularizer_type if use_reg else None,
+                                                 a.LOSS.depth_regularizer_weight if use_reg else 0.0, a.LOSS.three3d_loss_weight, self.map.sigma,
+                                                 overlap=self.overlap_wgrad, use_graphs=self.use_graphs, **terms)
             self._inv_K = torch.pinverse(self.intrinsics[0, 0])
             self._poses_h = self.poses.detach().cpu()
             # (prev, cur) -> relative transform pinv(P_prev) P_cur (training_utils.py:191-216) on the device: the whole keyframe schedule
@@ -294,6 +291,17 @@ class SLAM:
         sp.set_pair(self.colors[0, prev], self.colors[0, cur], self.gt_depths[0, prev], self.gt_depths[0, cur], self.intrinsics[0, 0], T, self.poses[0, cur],
                     inv_K=self._inv_K, pose_src=self.poses[0, prev])
 
+    # ---- seams for subclasses: the product's bodies do nothing ------------------------------------------------------------
+    def _before_plan_step(self, sp):
+        """Called with the step plan before every sp.step(...) of refinement()."""
+
+    def _after_plan_step(self, sp):
+        """Called with the step plan after every sp.step(...) of refinement(), before refinement_steps_done counts it."""
+
+    def _scale_gradient_elements(self):
+        """Third argument of ops.depth_from_disp_median_scaled in refinement_autograd (None: the operator's own choice)."""
+        return None
+
     def refinement(self, prev, cur, max_steps=None, next_pair=None):
         """One keyframe: `OPTIMIZATION.refinement_steps` optimisation steps on the pair (prev, cur), then the map update
         (online_adaption.py:259-327).  max_steps (bench.py) truncates the optimisation loop to time an exact step count.
@@ -312,11 +320,9 @@ class SLAM:
         nsteps = a.OPTIMIZATION.refinement_steps if max_steps is None else min(int(max_steps), a.OPTIMIZATION.refinement_steps)
         for refine_step in range(nsteps):
             held = self._forward_holds if (refine_step == 0 and self.reuse_forward and self._forward_holds is not None) else (None, None)
-            if self.median_elements is not None:
-                sp.median_elements_override = self.median_elements[self.refinement_steps_done]
+            self._before_plan_step(sp)
             sp.step(refine_step == 0, index, source_forward_is_current=held == (None, prev), both_forwards_are_current=held == (prev, cur))
-            if self.median_elements_log is not None:
-                self.median_elements_log.append((sp.delta.reshape(-1) == sp.md).nonzero().reshape(-1).to(torch.int32))
+            self._after_plan_step(sp)
             self._forward_holds = None              # Adam stepped
             self.refinement_steps_done += 1
             if a.DEBUG.print_metrics:
@@ -344,14 +350,12 @@ class SLAM:
             #  201.1 steps/s -- the forward's GEMMs and the map step's memory-bound kernels take more from each other than the overlap gives
             #  back, as round 3 found for backward-weight next to backward-data; the sequential single-frame forward stays the default)
             prefetch = self.prefetch_forward and self.reuse_forward and next_pair[0] == cur
-        if a.MODEL.odom == "gt":
-            sp.update_map(self.map, self.first_iter, prefetch=prefetch, aggregate=self.aggregate)
-        else:
-            # MODEL.odom icp / gradicp (the reference's default, configs/config.yaml:30): frame-to-model odometry from the previous keyframe's
-            # pose inside the same captured map step (e2ehip.icp.ResidentOdometry: no host round trip per iteration); the map is fused with
-            # the ESTIMATED pose and the pose itself, which the reference drops (online_adaption.py:362-363), is kept for the trajectory error
-            odo = self._odometry()
-            sp.update_map_odom(self.map, self.first_iter, odo, prefetch=prefetch, aggregate=self.aggregate)
+        # MODEL.odom icp / gradicp (the reference's default, configs/config.yaml:30): frame-to-model odometry from the previous keyframe's
+        # pose inside the same captured map step (e2ehip.icp.ResidentOdometry: no host round trip per iteration); the map is fused with
+        # the ESTIMATED pose and the pose itself, which the reference drops (online_adaption.py:362-363), is kept for the trajectory error
+        odo = None if a.MODEL.odom == "gt" else self._odometry()
+        sp.update_map(self.map, self.first_iter, prefetch=prefetch, aggregate=self.aggregate, odometry=odo)
+        if odo is not None:
             self.estimated_poses.append((odo.pose.clone(), self.poses[0, cur]))
         # slots of the plan's batch that hold a complete forward pass made with the current weights: (frame in slot 0, frame in slot 1)
         self._forward_holds = (cur, next_pair[1]) if prefetch else (None, cur)
@@ -390,8 +394,7 @@ class SLAM:
         for refine_step in range(nsteps):
             self.optimizer.zero_grad()
             disp = self.models["depth"](colors[0], 0)[("disp", 0, 0)]                     # (2,1,H,W): pair as one batch
-            depth, delta, ratio = ops.depth_from_disp_median_scaled(
-                disp, median_gt, None if self.median_elements is None else self.median_elements[self.refinement_steps_done])
+            depth, delta, ratio = ops.depth_from_disp_median_scaled(disp, median_gt, self._scale_gradient_elements())
             if refine_step == 0 and use_reg:
                 initial = delta.clone()                                                  # 1/disp BEFORE scaling (:284-285)
             d_src, d_tgt = depth[0:1], depth[1:2]

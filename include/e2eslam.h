@@ -409,11 +409,12 @@ int e2e_depth_scale_fwd(const float* disp, const float* median_gt, float* delta,
 int e2e_depth_scale_bwd(const float* g_depth, const float* delta, const float* median_gt,
                         const float* median_delta, float* g_disp, void* workspace, int64_t n,
                         void* stream);
-/* The same chain with the elements that receive the median's gradient NAMED by the caller (device int32 indices into the
- * n stacked predictions, 1..64 of them, sharing the gradient equally; n_elements == 0: e2e_depth_scale_bwd).  For callers
- * that hold torch.median's own choice: among 614 400 fp32 depths the neighbours of the median lie ~1e-6 apart, closer than two
- * correct evaluations of the network agree, so WHICH element it is belongs to the evaluation, not to the algorithm --
- * the parity tests name the CPU evaluation's elements here and compare everything else (online_adaption.py:295-298). */
+/* TEST INSTRUMENTATION, no counterpart in the reference; the refinement step itself calls e2e_depth_scale_bwd.  The same chain
+ * with the elements that receive the median's gradient NAMED by the caller (device int32 indices into the n stacked
+ * predictions, 1..64 of them, sharing the gradient equally; n_elements == 0: e2e_depth_scale_bwd).  Among 614 400 fp32 depths
+ * the neighbours of the median lie ~1e-6 apart, closer than two correct evaluations of the network agree, so WHICH element
+ * it is belongs to the evaluation, not to the algorithm -- the parity tests name the CPU evaluation's elements here and
+ * compare everything else (online_adaption.py:295-298). */
 int e2e_depth_scale_bwd_at(const float* g_depth, const float* delta, const float* median_gt,
                            const float* median_delta, const int* elements, int n_elements,
                            float* g_disp, void* workspace, int64_t n, void* stream);

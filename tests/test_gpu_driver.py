@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 import torch
 
+from median_pin import PinnedSLAM, pin
 from oracle import depthnet, refine
 
 pytestmark = pytest.mark.gpu
@@ -66,7 +67,6 @@ def test_every_step_of_two_keyframes_vs_oracle_teacher_forced(H, W):
     decomposition the bench uses, the 307 200-query KNN against the fused map (oracle: C brute force), the full-size PointFusion step."""
     from e2ehip import ops
     from e2ehip.synthetic import make_sequence
-    from online_adaption import SLAM
     from utils.training_utils import torch_poses_to_transforms
     L = 3
     seq = make_sequence(L, H, W, seed=7)
@@ -121,7 +121,7 @@ def test_every_step_of_two_keyframes_vs_oracle_teacher_forced(H, W):
     # ---- GPU, one step at a time from the oracle's state ----------------------------------------------------------------------------
     cfg = _cfg(H, W, L)
     cfg.DEBUG.print_metrics = False
-    slam = SLAM(cfg, sequence=seq, state_dict=sd)
+    slam = PinnedSLAM(cfg, sequence=seq, state_dict=sd)
     slam.set_refinement_mode()
     sp = slam._step_plan()
     params = dict(slam.models["depth"].named_parameters())
@@ -151,7 +151,7 @@ def test_every_step_of_two_keyframes_vs_oracle_teacher_forced(H, W):
         for k in range(3):
             load(snaps[step])
             r = recs[step]
-            sp.median_elements_override = torch.tensor(r["median_indices"], dtype=torch.int32, device="cuda")
+            sp.median_elements_override = pin(r["median_indices"], "cuda")
             sp.step(k == 0, index)
             lp, lr, l3 = (float(v) for v in sp.losses())
             np.testing.assert_allclose(lp, r["photometric"], rtol=1e-4)
@@ -184,7 +184,7 @@ def test_every_step_of_two_keyframes_vs_oracle_teacher_forced(H, W):
             # all pixels on the ONE element torch.median names, and that element carries most of the parameter gradient.  Among 614 400
             # values the neighbours of the median are ~1e-6 apart, closer than two fp32 evaluations of a depth agree, so WHICH element
             # it is differs between two correct evaluations (round 3 compared gradients only where it happened to agree: 1 step of 6).
-            # The choice is taken out of the comparison instead: the plan's median_elements_override names the oracle's elements (every
+            # The choice is taken out of the comparison instead: PinnedStepPlan.median_elements_override names the oracle's elements (every
             # element equal to its median value: torch.median(x) shares the gradient among them, evenly_distribute_backward) as the
             # ones the gradient lands on (e2e_depth_scale_bwd_at), after checking that on the GPU too their values are the median to
             # within fp32 rounding of a depth; the median VALUE, the ratio and every loss term stay the GPU's own.
@@ -247,7 +247,6 @@ def test_default_head_first_step_vs_oracle(H, W):
     to be held to the better reference (tests/test_oracle_conditioning.py).  One-element tensors get that measured
     conditioning as their bound (1e-2: relative error of a single cancelling sum); every other tensor the usual 1e-4 / 1e-3 of its maximum."""
     from e2ehip.synthetic import make_sequence
-    from online_adaption import SLAM
     seq = make_sequence(2, H, W, seed=9)
     sd = depthnet.random_state_dict(0)
     colors, gt, K, poses = (t.double() for t in seq)
@@ -264,12 +263,11 @@ def test_default_head_first_step_vs_oracle(H, W):
     r = ora.refine_pair(colors, gt, poses, K, update_map=False)[0]
     cfg = _cfg(H, W, 2)
     cfg.DEBUG.print_metrics = False
-    slam = SLAM(cfg, sequence=seq, state_dict=sd)
+    slam = PinnedSLAM(cfg, sequence=seq, state_dict=sd)
     slam.set_refinement_mode()
     sp = slam._step_plan()
     slam._load_pair(sp, 0, 1)
-    assert len(r["median_indices"]) <= 64, len(r["median_indices"])
-    sp.median_elements_override = torch.tensor(r["median_indices"], dtype=torch.int32, device="cuda")
+    sp.median_elements_override = pin(r["median_indices"], "cuda")
     sp.step(True, None)
     lp, lr, _ = (float(v) for v in sp.losses())
     np.testing.assert_allclose(lp, r["photometric"], rtol=1e-4)
@@ -301,11 +299,10 @@ def test_default_head_first_step_vs_oracle(H, W):
 
 def _run_two_keyframes(mode, median_elements=None):
     from e2ehip.synthetic import make_sequence
-    from online_adaption import SLAM
     H, W, L = 64, 96, 3
     sd = depthnet.random_state_dict(0)
     sd["decoder.decoder.10.conv.weight"] = sd["decoder.decoder.10.conv.weight"] * 40.0
-    slam = SLAM(_cfg(H, W, L), sequence=make_sequence(L, H, W, seed=11), state_dict=sd)
+    slam = PinnedSLAM(_cfg(H, W, L), sequence=make_sequence(L, H, W, seed=11), state_dict=sd)
     slam.use_graphs = mode == "graphs"
     slam.median_elements = median_elements
     slam.median_elements_log = [] if median_elements is None else None
@@ -323,7 +320,7 @@ def test_launch_plan_equals_autograd_path_and_graph_replay_is_exact():
     """The static launch plan (e2ehip.stepplan) against torch.autograd over the per-layer Functions (same kernels), and its
     eager form against the captured-hipGraph form: the second and third step of every keyframe are graph replays."""
     # the graphs run names, step by step, WHICH element of its predictions was the median; the other two runs put the ratio's gradient on
-    # the same elements (SLAM.median_elements).  For the eager run that changes nothing (it is the same arithmetic, checked bit for bit);
+    # the same elements (PinnedSLAM.median_elements).  For the eager run that changes nothing (it is the same arithmetic, checked bit for bit);
     # the autograd run differs from the plan in rounding -- enough, now and then, to make a neighbour 1e-7 away the median, after which
     # the two trajectories are different (equally valid) experiments and the comparison below would measure that, not the kernels
     log_g, map_g, sd_g, elems = _run_two_keyframes("graphs")
@@ -353,7 +350,6 @@ def test_tum_shaped_sequence_vs_oracle_first_keyframe(H, W):
     DATA.name TUM (the holes are masked in depth_metrics only, losses.py:167-169; the median of the ground truth includes them,
     online_adaption.py:295), keyframe threshold 0.12: 3 refinement steps of the first keyframe against the oracle, then the map."""
     from e2ehip.synthetic import make_sequence, tum_intrinsics
-    from online_adaption import SLAM
     L = 3
     seq = make_sequence(L, H, W, seed=13, step=0.13, K=tum_intrinsics(H, W), holes=0.1)
     assert float((seq[1] == 0).float().mean()) > 0.05
@@ -366,12 +362,12 @@ def test_tum_shaped_sequence_vs_oracle_first_keyframe(H, W):
     ocfg.dataset = "TUM"
     ora = refine.Refiner(sd, ocfg)
     recs = ora.refine_pair(colors[:, [0, 1]], gt[:, [0, 1]], poses[:, [0, 1]], K)
-    slam = SLAM(cfg, sequence=seq, state_dict=sd)
+    slam = PinnedSLAM(cfg, sequence=seq, state_dict=sd)
     assert len(slam.keyframe_schedule()) == L - 1                    # 0.13 m steps: every frame is a keyframe at threshold 0.12
     slam.set_refinement_mode()
     slam.first_iter = True
     # the one discrete choice of a step -- which near-tied prediction is the median element -- is the oracle's (see the teacher-forced test)
-    slam.median_elements = [torch.tensor(r["median_indices"][:64], dtype=torch.int32, device="cuda") for r in recs]
+    slam.median_elements = [pin(r["median_indices"], "cuda") for r in recs]
     slam.refinement(0, 1)
     log = torch.stack(slam.log)
     np.testing.assert_allclose(log[:, 1].numpy(), [r["photometric"] for r in recs], rtol=1e-4)
@@ -542,15 +538,14 @@ def test_two_keyframes_free_running_vs_oracle(head_scale, dtype, tol):
     oracle does)."""
     from test_oracle_conditioning import run_two_keyframes
     from e2ehip.synthetic import make_sequence
-    from online_adaption import SLAM
     H, W, L = 64, 96, 3
     recs = run_two_keyframes(dtype, head_scale)
     sd = depthnet.random_state_dict(0)
     sd["decoder.decoder.10.conv.weight"] = sd["decoder.decoder.10.conv.weight"] * head_scale
-    slam = SLAM(_cfg(H, W, L), sequence=make_sequence(L, H, W, seed=7), state_dict=sd)
+    slam = PinnedSLAM(_cfg(H, W, L), sequence=make_sequence(L, H, W, seed=7), state_dict=sd)
     # free-running in everything but ONE discrete choice: which of the (near-)tied predictions is the median element, i.e. where the
     # ratio's gradient lands, is the oracle's at every step (its own trajectory's torch.median; see the teacher-forced test)
-    slam.median_elements = [torch.tensor(r["median_indices"][:64], dtype=torch.int32, device="cuda") for r in recs]
+    slam.median_elements = [pin(r["median_indices"], "cuda") for r in recs]
     slam.main()
     log = torch.stack(slam.log).double().numpy()
     assert log.shape[0] == 6

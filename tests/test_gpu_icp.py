@@ -70,7 +70,7 @@ def test_resident_odometry_equals_host_loop_and_oracle(mode):
 
 def test_driver_gradicp_runs_resident_and_reports_ate():
     """configs/config.yaml:30 (odom: gradicp) through the driver's launch plan: the map step with odometry is one captured graph
-    (RefineStepPlan.update_map_odom); the estimated poses stay on the device until the trajectory error is asked for."""
+    (RefineStepPlan.update_map(odometry=...)); the estimated poses stay on the device until the trajectory error is asked for."""
     from e2ehip.synthetic import make_sequence
     from online_adaption import SLAM, default_config
     from oracle import depthnet

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+from median_pin import PinnedSLAM, pin
 from oracle import depthnet, refine, warp_loss
 from oracle import icp as oicp
 from test_gpu_frame_append import aggregate_rows
@@ -55,7 +56,6 @@ def test_icpslam_two_keyframes_free_running_vs_aggregating_oracle():
     relative -- the project's bound for these quantities (metrics: rtol 1e-4 with the atol 1e-6 of the teacher-forced test) -- and the
     map size exactly: predicted depths are never zero, so every fused frame adds H * W rows."""
     from e2ehip.synthetic import make_sequence
-    from online_adaption import SLAM
     H, W, L = 64, 96, 3
     seq = make_sequence(L, H, W, seed=7)
     colors, gt, K, poses = seq
@@ -65,8 +65,8 @@ def test_icpslam_two_keyframes_free_running_vs_aggregating_oracle():
     for a, b in ((0, 1), (1, 2)):
         recs += ora.refine_pair(colors[:, [a, b]], gt[:, [a, b]], poses[:, [a, b]], K)
     assert ora.map["points"].shape[0] == 3 * H * W and "knn" in recs[3]
-    slam = SLAM(_cfg(H, W, L), sequence=seq, state_dict=sd)
-    slam.median_elements = [torch.tensor(r["median_indices"][:64], dtype=torch.int32, device="cuda") for r in recs]
+    slam = PinnedSLAM(_cfg(H, W, L), sequence=seq, state_dict=sd)
+    slam.median_elements = [pin(r["median_indices"], "cuda") for r in recs]
     slam.main()
     log = torch.stack(slam.log).double().numpy()
     assert log.shape[0] == 6
@@ -90,9 +90,8 @@ def test_icpslam_two_keyframes_free_running_vs_aggregating_oracle():
 
 def _run_two_keyframes(mode, median_elements=None):
     from e2ehip.synthetic import make_sequence
-    from online_adaption import SLAM
     H, W, L = 64, 96, 3
-    slam = SLAM(_cfg(H, W, L), sequence=make_sequence(L, H, W, seed=11), state_dict=_head40())
+    slam = PinnedSLAM(_cfg(H, W, L), sequence=make_sequence(L, H, W, seed=11), state_dict=_head40())
     slam.use_graphs = mode == "graphs"
     slam.median_elements = median_elements
     slam.median_elements_log = [] if median_elements is None else None

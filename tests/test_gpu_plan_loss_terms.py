@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+from median_pin import PinnedSLAM, pin
 from oracle import depthnet, refine, warp_loss
 
 pytestmark = pytest.mark.gpu
@@ -246,9 +247,8 @@ def test_plan_loss_flags_vs_oracle_two_keyframes(H, W, flags):
     """test_off_by_default_loss_flags_vs_oracle's comparison through the launch plan: 3 refinement steps over the first keyframe and 3
     over a second one (3-D loss active), loss / photometric / regulariser at 2e-4, ratio at 1e-4 (that test's bounds), tie-break noise
     zero on both sides.  The one discrete choice of a step -- which near-tied prediction is the median element -- is the oracle's
-    (SLAM.median_elements, as in test_tum_shaped_sequence_vs_oracle_first_keyframe).  128x160 rather than 120x160: the launch plan
+    (PinnedSLAM.median_elements, as in test_tum_shaped_sequence_vs_oracle_first_keyframe).  128x160 rather than 120x160: the launch plan
     needs height and width to be multiples of 32 (e2ehip.netplan); 20480 pixels keep the geometric term live (> 10000 valid)."""
-    import online_adaption as oa
     from e2ehip.synthetic import make_sequence
     L = 3
     seq = make_sequence(L, H, W, seed=21)
@@ -265,9 +265,9 @@ def test_plan_loss_flags_vs_oracle_two_keyframes(H, W, flags):
         recs += ora.refine_pair(colors[:, [a, b]], gt[:, [a, b]], poses[:, [a, b]], K)
     assert len(recs) == 6 and "knn" in recs[3]
     with _zero_randn():
-        slam = oa.SLAM(cfg, sequence=seq, state_dict=sd)
+        slam = PinnedSLAM(cfg, sequence=seq, state_dict=sd)
         slam.plan_loss_terms = True
-        slam.median_elements = [torch.tensor(r["median_indices"][:64], dtype=torch.int32, device="cuda") for r in recs]
+        slam.median_elements = [pin(r["median_indices"], "cuda") for r in recs]
         slam.main()
     assert slam.step_plan is not None and any(isinstance(k, tuple) and k[0] == "bwd" for k in slam.step_plan._graphs)
     log = torch.stack(slam.log)
@@ -302,7 +302,6 @@ def test_plan_form_equals_autograd_form_and_replay_equals_eager():
     with _zero_randn():
         plan = oa.SLAM(_cfg(H, W, L, flags), sequence=seq, state_dict=sd)
         plan.plan_loss_terms = True
-        plan.median_elements_log = []
         plan.set_refinement_mode()
         plan.first_iter = True
         sp = plan._step_plan()
@@ -325,7 +324,7 @@ def test_plan_form_equals_autograd_form_and_replay_equals_eager():
         assert any(isinstance(k, tuple) and k[0] == "bwd" for k in sp._graphs)
         sp.step(True, None)
         g_replay = first_moments(plan)
-        auto = oa.SLAM(_cfg(H, W, L, flags), sequence=seq, state_dict=sd)
+        auto = PinnedSLAM(_cfg(H, W, L, flags), sequence=seq, state_dict=sd)
         assert not auto.plan_loss_terms and not auto._plan_eligible()
         auto.median_elements = elems
         auto.set_refinement_mode()

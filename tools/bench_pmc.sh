@@ -10,9 +10,10 @@ cd $GRAFT_REPO_ROOT
 STEPS=9; WARM=3
 ARGS="--no-cpu-baseline --no-roofline --steps $STEPS --warmup $WARM"
 STAMP=$(python3 bench.py --print-stamp)
-rocprofv3 --pmc FETCH_SIZE --output-format csv -d /tmp/bp_f_$TAG -o pmc -- python3 bench.py $ARGS > $OUT/fetch.log 2>&1
+# each pass under its own time limit; a pass that fails or runs out of time ends the script (nothing more is started on that GPU)
+timeout -k 10 420 rocprofv3 --pmc FETCH_SIZE --output-format csv -d /tmp/bp_f_$TAG -o pmc -- python3 bench.py $ARGS > $OUT/fetch.log 2>&1 || exit 1
 echo "fetch pass done" > $OUT/progress.txt
-rocprofv3 --pmc WRITE_SIZE --output-format csv -d /tmp/bp_w_$TAG -o pmc -- python3 bench.py $ARGS > $OUT/write.log 2>&1
+timeout -k 10 420 rocprofv3 --pmc WRITE_SIZE --output-format csv -d /tmp/bp_w_$TAG -o pmc -- python3 bench.py $ARGS > $OUT/write.log 2>&1 || exit 1
 echo "write pass done" >> $OUT/progress.txt
 python3 - /tmp/bp_f_$TAG /tmp/bp_w_$TAG $((STEPS + WARM)) $STAMP > $OUT/traffic.txt <<'PY'
 import csv, glob, sys, collections, json
