@@ -18,6 +18,7 @@
 // global loads of the next chunk are issued before the current chunk's MFMAs.  Operands are gathered through buffer
 // resources with 32-bit offsets: padding, stride holes and tile tails are out-of-range offsets that the hardware
 // answers with zeros, so the K loop has no branches and no 64-bit address arithmetic.
+#include <cassert>
 #include <type_traits>
 
 #include "e2e_common.h"
@@ -297,7 +298,7 @@ __device__ __forceinline__ unsigned xcd_contiguous(unsigned id, unsigned n) {
 // Static wave priority by launch order.  The workgroups that share a CU run the same program and, with the matrix pipe arbitrated fairly
 // between them, fall into LOCKSTEP: all of them multiply at the same time (n x 1024 cycles per chunk, interleaved) and then all of them
 // stage / synchronise / read LDS at the same time with the pipe idle (~1570 cycles) -- measured per chunk: 0.66 us + 0.43 us x n
-// (scratch/conv_stamps.py).  Workgroups id, id + 256, id + 512 ... are the ones that end up on one CU (256 CUs, round-robin dispatch):
+// (profiles/r03_conv_phase_stamps.txt).  Workgroups id, id + 256, id + 512 ... are the ones that end up on one CU (256 CUs, round-robin dispatch):
 // giving them DIFFERENT priorities lets the highest one run its MFMA chain unimpeded while the others fill its staging phase, and the
 // phases stay interleaved.  Speed only.
 __device__ __forceinline__ void set_wave_priority(unsigned linear_block_id) {
@@ -310,7 +311,7 @@ __device__ __forceinline__ void set_wave_priority(unsigned linear_block_id) {
 // The workgroup a GEMM body works on, passed in explicitly: the hardware's own ids for a standalone launch (HwIds: read where they are
 // used, as the kernels did before they had bodies -- the standalone kernels compile to the same code), a VIRTUAL id inside a grid that
 // carries two tile sets (PartIds, k_conv_bwd_pair).  Everything that depends on launch order -- the XCD-contiguous remap, the static wave
-// priority, the parity-class decode, the diagnostic stamps -- reads these, never blockIdx / gridDim.
+// priority, the parity-class decode -- reads these, never blockIdx / gridDim.
 struct HwIds {
     __device__ __forceinline__ unsigned x() const { return blockIdx.x; }
     __device__ __forceinline__ unsigned y() const { return blockIdx.y; }
@@ -332,25 +333,6 @@ struct PartIds {
     __device__ __forceinline__ unsigned lin() const { return l; }
 };
 
-#ifdef E2E_CONV_STAMPS          // diagnostic build only (scratch/conv_stamps.py): s_memtime / s_memrealtime stamps of every workgroup's phases
-__device__ unsigned long long g_stamps[8192 * 8];
-#define STAMP(i) do { if (threadIdx.x == 0 && wg.y() == 0 && wg.z() == 0 && wg.x() < 8192) g_stamps[wg.x() * 8 + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-__device__ unsigned long long g_stamps2[8192 * 4];      // finer stamps inside the prologue of k_conv_gemm
-#define STAMP2(i) do { if (threadIdx.x == 0 && wg.y() == 0 && wg.z() == 0 && wg.x() < 8192) g_stamps2[wg.x() * 4 + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-// shader-clock time spent in the phases of the K loop (wave 0 of every workgroup, summed over its chunks).  The scheduling barriers pin
-// the phases, so this build runs a slightly different (more serial) schedule than the product: it locates the stalls, it is not the product's timing
-__device__ unsigned long long g_phases[8192 * 8];
-#define PHASE_DECL unsigned long long ph_last = __builtin_amdgcn_s_memtime(), ph_acc[6] = {0, 0, 0, 0, 0, 0}
-#define PHASE(i) do { __builtin_amdgcn_sched_barrier(0); const unsigned long long t_ = __builtin_amdgcn_s_memtime(); ph_acc[i] += t_ - ph_last; ph_last = t_; __builtin_amdgcn_sched_barrier(0); } while (0)
-#define PHASE_WRITE do { if (threadIdx.x == 0 && wg.y() == 0 && wg.z() == 0 && wg.x() < 8192) for (int i_ = 0; i_ < 6; ++i_) g_phases[wg.x() * 8 + i_] = ph_acc[i_]; } while (0)
-#else
-#define STAMP(i) do { } while (0)
-#define STAMP2(i) do { } while (0)
-#define PHASE_DECL do { } while (0)
-#define PHASE(i) do { } while (0)
-#define PHASE_WRITE do { } while (0)
-#endif
-
 // LDS tiles of k_conv_gemm: double-buffered A (k-major, row stride padded for the VEC == 4 loader's transposing stores) and B
 template <int WM, int WN, int TM, int TN, int VEC, int CB>
 struct ConvGemmLds {
@@ -371,7 +353,6 @@ __device__ __forceinline__ void conv_gemm_body(const ConvArgs& a, const Ids& wg,
     constexpr int B_CNT = CB * (BN / 4);                   // float4 loads of the B tile
     constexpr int B_PER = (B_CNT + NT - 1) / NT;
     static_assert(NT % KQ == 0 && NT % BM == 0, "tile / thread-count mismatch");
-    STAMP(0);
     set_wave_priority(wg.lin());
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave % WM, wn = wave / WM;
@@ -382,7 +363,6 @@ __device__ __forceinline__ void conv_gemm_body(const ConvArgs& a, const Ids& wg,
     const int kh0 = CLS ? ((py + a.off) & 1) : 0, kw0 = CLS ? ((px + a.off) & 1) : 0, kstep = CLS ? 2 : 1;
     const int nkh = CLS ? (a.KH - kh0 + 1) / 2 : a.KH, nkw = CLS ? (a.KW - kw0 + 1) / 2 : a.KW;
     const int64_t Ntot = (int64_t)a.B * Hc * Wc;
-    if (Ntot > 0) STAMP2(0);                                 // (diagnostic) the kernel arguments have arrived
     // non-class form: the launch's linear id -> XCD-contiguous order, decoded with the column tile fastest, then the row tile, the K slice
     // slowest: an XCD's contiguous range then covers one or two K slices, i.e. that part of the WEIGHT matrix only -- with the row tile
     // slowest (the first form) every XCD's L2 fetched the whole matrix, eight times per launch in total (the bulk of FETCH_SIZE on the
@@ -455,11 +435,10 @@ __device__ __forceinline__ void conv_gemm_body(const ConvArgs& a, const Ids& wg,
     }
     const int sh = a.up >> 1;                                // up is 1 or 2: source coordinate = full-res coordinate >> sh
     const int Hl = a.Hs >> sh, Wl = a.Ws >> sh, C2 = a.Cin - a.C1;
-    if (ab[0] >= 0) STAMP2(1);                               // (diagnostic) rows decoded
 
     // staging registers: TWO sets -- the global loads of chunk c + 2 are issued while chunk c is multiplied and chunk c + 1 waits in the
     // other set for its turn to be written to LDS.  (One set = loads one chunk ahead left every workgroup waiting ~1.5 us per chunk for
-    // fabric-served loads against 0.43 us of MFMA work: round-3 phase stamps, scratch/conv_stamps.py.)
+    // fabric-served loads against 0.43 us of MFMA work: round-3 phase stamps, profiles/r03_conv_phase_stamps.txt.)
     f4v areg[2][A_PER];
     float areg1[2][A_PER];
     f4v breg[2][B_PER];
@@ -519,7 +498,6 @@ __device__ __forceinline__ void conv_gemm_body(const ConvArgs& a, const Ids& wg,
         ld_cc = cbeg - t0 * cpt;
         set_tap();
     }
-    if (off0[0] != 1u) STAMP2(2);                            // (diagnostic) tap tables built, first tap selected
 
     auto load_chunk = [&](int chunk, int set) {
         const int kbase = chunk * CB;
@@ -589,14 +567,11 @@ __device__ __forceinline__ void conv_gemm_body(const ConvArgs& a, const Ids& wg,
 
     if (cbeg < cend) {
         load_chunk(cbeg, 0);
-        STAMP(1);
         if (VEC == 4 || cbeg + 1 < cend) load_chunk(cbeg + 1, 1);
         store_chunk(0, 0);
     }
     __syncthreads();
-    STAMP(2);
     const int arow_l = wm * TM * 32 + (lane & 31), khalf = lane >> 5;
-    PHASE_DECL;
     // one K chunk: chunk c (in LDS buffer `BUF`) is multiplied while the loads of chunk c + 2 go to register set BUF (free: its chunk c
     // is in LDS) and chunk c + 1 -- loaded one iteration earlier into set BUF ^ 1 -- is written to the other LDS buffer afterwards
     auto chunk_step = [&](int c, auto buf_c) {
@@ -604,9 +579,7 @@ __device__ __forceinline__ void conv_gemm_body(const ConvArgs& a, const Ids& wg,
         // VEC == 4: loads and stores are UNCONDITIONAL (chunks past the end of the slice are fetched -- out-of-range offsets return zeros --
         // and written to the LDS buffer nobody reads any more): the chunk is one basic block and the scheduler may place the staging
         // instructions between the MFMAs
-        PHASE(5);                                            // (diagnostic) loop control between two chunks
         if (VEC == 4 || c + 2 < cend) load_chunk(c + 2, buf);
-        PHASE(0);                                            // (diagnostic) loads of chunk c + 2 issued, next tap selected
         // operand fragments of the WHOLE chunk are read into registers first, the MFMAs follow with counted LDS waits: hipcc's own
         // schedule of the fused loop was read -> s_waitcnt lgkmcnt(0) -> 2 MFMAs per k-pair on ONE register set, i.e. every pair of MFMAs
         // waited for a fresh LDS round trip (~190 cycles per 128 cycles of matrix work: the kernels ran at half the MFMA rate with
@@ -631,22 +604,18 @@ __device__ __forceinline__ void conv_gemm_body(const ConvArgs& a, const Ids& wg,
             __builtin_amdgcn_sched_group_barrier(0x100, KH2 * (TM + TN) / 2, 0);     // all LDS reads of the batch (ds_read2: two values each) ...
             __builtin_amdgcn_sched_group_barrier(0x008, KH2 * TM * TN, 0);           // ... ahead of its MFMAs
         }
-        PHASE(1);                                            // (diagnostic) fragments read, all MFMAs of the chunk ISSUED
         // nothing moves across this point: left to itself hipcc hoists the LDS stores of chunk c + 1 (and with them the s_waitcnt vmcnt
         // for its global loads, issued ONE step earlier) to the top of the step, ahead of 14 of the 16 MFMAs -- every step then waited
         // for memory with the matrix pipe idle (round-3 disassembly: 1.14 us per chunk for a workgroup alone on its SIMDs, 0.43 us of
         // it MFMA work).  Here the wait comes after the MFMAs have been issued: two steps after the loads.
         __builtin_amdgcn_sched_barrier(0);
         if (VEC == 4 || c + 1 < cend) store_chunk(buf ^ 1, buf ^ 1);
-        PHASE(2);                                            // (diagnostic) chunk c + 1 has arrived from memory and is on its way to LDS
         __syncthreads();
-        PHASE(3);                                            // (diagnostic) barrier passed
-        if (c == cbeg) STAMP(4);
     };
     // ---- software-pipelined form (every VEC == 4 single-accumulator instantiation, i.e. every product launch) ----------------------
     // Step c of the form above is: read chunk c's fragments -> 16 dependent MFMAs -> store chunk c + 1 -> barrier; the matrix pipe idles
     // from the last MFMA of a step until the first fragments of the next chunk have come back from LDS (store, barrier, LDS round trip:
-    // 330 - 500 of ~1500 cycles per step, round-3 phase clocks in scratch/conv_stamps.py).  Here the barrier sits in the MIDDLE of the step
+    // 330 - 500 of ~1500 cycles per step, round-3 phase clocks, profiles/r03_conv_phase_clocks_plain_loop.txt).  Here the barrier sits in the MIDDLE of the step
     // and the fragments of chunk c + 1 are read under the second half of chunk c's MFMAs into a second fragment register set:
     //   store chunk c + 1 (loaded one step ago) | MFMAs 0-7 of chunk c | barrier | read fragments of chunk c + 1 | MFMAs 8-15 of chunk c
     // so the first MFMA of step c + 1 finds its operands in registers.  LDS stays double-buffered: buffer (c + 1) & 1 held chunk c - 1,
@@ -693,7 +662,6 @@ __device__ __forceinline__ void conv_gemm_body(const ConvArgs& a, const Ids& wg,
             __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
         }
         __builtin_amdgcn_sched_barrier(0);
-        if (c == cbeg) STAMP(4);
     };
     if (PIPE) {
         if (cbeg < cend) {
@@ -718,8 +686,6 @@ __device__ __forceinline__ void conv_gemm_body(const ConvArgs& a, const Ids& wg,
         }
         if (c < cend) chunk_step(c, std::integral_constant<int, 0>{});
     }
-    PHASE_WRITE;
-    STAMP(3);
 
     // ---- epilogue (epilogue_block above; split-K slices store raw partial sums instead) --------------------------------------
     if (a.ksplit > 1) {                                      // raw partial sums; the scale / shift / activation run after the reduction
@@ -755,18 +721,6 @@ __device__ __forceinline__ void conv_gemm_body(const ConvArgs& a, const Ids& wg,
 #pragma unroll
             for (int t = 0; t < TN; ++t)
                 epilogue_block<TRANSPOSED>(a, er, acc[u][t], c0 + (wn * TN + t) * 32 + (lane & 31), n0 + (wm * TM + u) * 32 + 4 * khalf, Ntot);
-#ifdef E2E_CONV_STAMPS
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        STAMP(5);
-        if (threadIdx.x == 0 && wg.y() == 0 && wg.z() == 0 && wg.x() < 8192) {
-            unsigned hw;
-            asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-            unsigned xcc;
-            asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-            g_stamps[wg.x() * 8 + 6] = hw;
-            g_stamps[wg.x() * 8 + 7] = xcc;
-        }
-#endif
         return;
     }
     // class form (3 small layers): GEMM row n = (b, yc, xc) of the class lattice -> output pixel (b, 2 yc + py, 2 xc + px), decoded like
@@ -845,13 +799,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_gemm_sk(ConvArgs a, SkArgs s) {
     __shared__ float As[2][CB][BM + 1];
     __shared__ float Bs[2][CB][BN];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave & 1, wn = wave >> 1;
-#ifdef E2E_CONV_STAMPS
-    const HwIds wg{};
-#endif
     set_wave_priority(blockIdx.x);
-    STAMP(0);
-    int stamp_piece = 0;
-    (void)stamp_piece;
     const int g = (int)xcd_contiguous(blockIdx.x, gridDim.x);          // consecutive iteration ranges (neighbouring tiles) share an XCD's L2
     const int64_t Ntot = (int64_t)a.B * a.Hd * a.Wd;
     constexpr unsigned OOB = 0x80000000u;
@@ -965,7 +913,6 @@ __global__ __launch_bounds__(256, 2) void k_conv_gemm_sk(ConvArgs a, SkArgs s) {
             store_chunk(buf ^ 1, buf ^ 1);
             __syncthreads();
         };
-        if (stamp_piece == 0) STAMP(1);
         {                                                       // (pairs + an odd tail outside the loop: see k_conv_gemm)
             int c = cb;
             for (; c + 1 < ce; c += 2) {
@@ -974,7 +921,6 @@ __global__ __launch_bounds__(256, 2) void k_conv_gemm_sk(ConvArgs a, SkArgs s) {
             }
             if (c < ce) chunk_step(c, std::integral_constant<int, 0>{});
         }
-        if (stamp_piece == 0) STAMP(2);
         // ---- what to do with the accumulator ------------------------------------------------------------------------------------
         const unsigned sl_off = (unsigned)((wave * 4 * 64 + lane) * 16);         // this lane's first 16-byte quad inside a slab
         if (cb != 0) {
@@ -997,7 +943,6 @@ __global__ __launch_bounds__(256, 2) void k_conv_gemm_sk(ConvArgs a, SkArgs s) {
         } else {
             if (ce != s.C) {
                 // the tile's head: this workgroup finishes the tile with the pieces of g + 1, g + 2, ... (increasing K)
-                STAMP(4);
                 const int64_t tile_end = (int64_t)(tile + 1) * s.C;
                 int h_last = g;
                 for (int h = g + 1; h < s.G && s.I * h / s.G < tile_end; ++h) h_last = h;
@@ -1013,7 +958,6 @@ __global__ __launch_bounds__(256, 2) void k_conv_gemm_sk(ConvArgs a, SkArgs s) {
                 }
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 __syncthreads();
-                STAMP(5);
                 for (int h = g + 1; h <= h_last; ++h) {
                     const __amdgpu_buffer_rsrc_t rsl = __builtin_amdgcn_make_buffer_rsrc((void*)(s.slabs + (int64_t)h * (BM * BN)), 0, BM * BN * 4, 0x00020000);
                     f4v t[4];
@@ -1030,15 +974,8 @@ __global__ __launch_bounds__(256, 2) void k_conv_gemm_sk(ConvArgs a, SkArgs s) {
             const EpiRsrc er = make_epi_rsrc<TRANSPOSED>(a);
             epilogue_block<TRANSPOSED>(a, er, acc, c0 + wn * 32 + (lane & 31), n0 + wm * 32 + 4 * khalf, Ntot);
         }
-        if (stamp_piece == 0) STAMP(3);
-        ++stamp_piece;
         it += ce - cb;
     }
-#ifdef E2E_CONV_STAMPS
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    STAMP(6);
-    if (threadIdx.x == 0) g_stamps[wg.x() * 8 + 7] = (unsigned long long)stamp_piece;
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -2637,26 +2574,26 @@ __global__ __launch_bounds__(256) void k_head_wreduce(const float* __restrict__ 
 // ---------------------------------------------------------------------------------------------------------------------
 static inline int egrid(int64_t n) { int64_t g = (n + 255) / 256; return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g)); }
 
-// K-chunk depth: 32 when the channel count allows (a chunk never straddles a tap; a row's chunk is one 128-byte line)
-#define GEMM_LAUNCH(WM, WN, TM, TN, GRID)                                                                                   \
-    do {                                                                                                                    \
-        if (cb == 32) hipLaunchKernelGGL((k_conv_gemm<WM, WN, TM, TN, 4, TR, 32>), GRID, dim3(64 * WM * WN), 0, st, a);     \
-        else hipLaunchKernelGGL((k_conv_gemm<WM, WN, TM, TN, 4, TR, 16>), GRID, dim3(64 * WM * WN), 0, st, a);              \
-    } while (0)
-
 // A GEMM decomposition: rows x columns of the workgroup tile and the number of K slices (split-K); S < 0: stream-K on -S persistent
 // workgroups (k_conv_gemm_sk, 64x64 tiles).  bm == 0: not forced.  Tuning choices travel PER CALL (the *_tuned entry points); the
 // library keeps no mutable state.
 struct GemmCfg { int bm, bn, S; };
 #define WGRAD_TARGET 1024                   // workgroups a backward-weight launch aims at by default
 
-// waves of a tile shape (one 32x32xTMxTN accumulator block per wave) -- 0: unsupported shape
-static int tile_waves(int bm, int bn) {
-    if ((bm == 64 && bn == 64) || (bm == 128 && bn == 64) || (bm == 128 && bn == 128) || (bm == 128 && bn == 32) || (bm == 32 && bn == 128)) return 4;
-    if ((bm == 32 && bn == 64) || (bm == 64 && bn == 32)) return 2;
-    if (bm == 32 && bn == 32) return 1;
+// The workgroup tile shapes k_conv_gemm is instantiated for, X(bm, bn, WM, WN, TM, TN, deepest K chunk): WM x WN waves, each with one
+// 32x32xTMxTN accumulator block.  K-chunk depth: 32 when the channel count allows (a chunk never straddles a tap; a row's chunk is one
+// 128-byte line) -- except for the shape with 2 x 2 blocks per wave, which exists at depth 16 only.
+#define CONV_TILE_SHAPES(X)                                                                                      \
+    X(64, 64, 2, 2, 1, 1, 32) X(128, 64, 2, 2, 2, 1, 32) X(128, 128, 2, 2, 2, 2, 16) X(128, 32, 4, 1, 1, 1, 32) \
+    X(32, 128, 1, 4, 1, 1, 32) X(32, 64, 1, 2, 1, 1, 32) X(64, 32, 2, 1, 1, 1, 32) X(32, 32, 1, 1, 1, 1, 32)
+static int tile_max_cb(int bm, int bn) {                   // 0: unsupported shape
+#define X(BM, BN, WM, WN, TM, TN, MAXCB) if (bm == BM && bn == BN) return MAXCB;
+    CONV_TILE_SHAPES(X)
+#undef X
     return 0;
 }
+// the depth-16-only shape gives way to 128 x 64: in choose_cfg where the call runs deeper chunks, in plan_gemm throughout the class form
+static void demote_cb16_only(GemmCfg& c) { if (tile_max_cb(c.bm, c.bn) == 16) c.bn = 64; }
 
 // The decomposition of a GEMM of rows x cols x K.  Calibrated on tools/gemm_tune.py (profiles/r02_gemm_tune*.txt: every tile
 // family x 1..16 K slices timed on every layer shape of the 480x640 network, forward and backward-data):
@@ -2668,7 +2605,7 @@ static int tile_waves(int bm, int bn) {
 //     do not pay: the kernels are not bound by tile quantisation but by the phases every wave of a launch goes through at
 //     the same time (operand set-up, epilogue), which more but smaller workgroups do not shorten.
 static GemmCfg choose_cfg(int64_t rows, int cols, int K, int cb, bool allow_split, GemmCfg force = GemmCfg{0, 0, 0}) {
-    if (force.bm) { GemmCfg f = force; if (!allow_split && f.S > 1) f.S = 1; if (f.bm == 128 && f.bn == 128 && cb != 16) f.bn = 64; return f; }
+    if (force.bm) { GemmCfg f = force; if (!allow_split && f.S > 1) f.S = 1; if (cb != 16) demote_cb16_only(f); return f; }
     GemmCfg c = {64, 64, 1};
     // round 3 (branch-free loaders, profiles/r03_gemm_tune_final.txt): with >= 128 columns the 32 x 128 tile (four waves side by side on ONE
     // 32-row A block) wins 5-10 % over 64 x 64 at the same slice count -- the gathered A operand is the expensive one to stage, and this
@@ -2720,14 +2657,16 @@ static GemmCfg choose_cfg(int64_t rows, int cols, int K, int cb, bool allow_spli
 
 template <bool TR>
 static void launch_tile(ConvArgs& a, int cb, GemmCfg c, dim3 g, hipStream_t st) {
-    if (c.bm == 64 && c.bn == 64) GEMM_LAUNCH(2, 2, 1, 1, g);
-    else if (c.bm == 128 && c.bn == 64) GEMM_LAUNCH(2, 2, 2, 1, g);
-    else if (c.bm == 128 && c.bn == 128) hipLaunchKernelGGL((k_conv_gemm<2, 2, 2, 2, 4, TR, 16>), g, dim3(256), 0, st, a);
-    else if (c.bm == 128 && c.bn == 32) GEMM_LAUNCH(4, 1, 1, 1, g);
-    else if (c.bm == 32 && c.bn == 128) GEMM_LAUNCH(1, 4, 1, 1, g);
-    else if (c.bm == 32 && c.bn == 64) GEMM_LAUNCH(1, 2, 1, 1, g);
-    else if (c.bm == 64 && c.bn == 32) GEMM_LAUNCH(2, 1, 1, 1, g);
-    else GEMM_LAUNCH(1, 1, 1, 1, g);
+#define X(BM, BN, WM, WN, TM, TN, MAXCB)                                                                                                 \
+    if (c.bm == BM && c.bn == BN) {                                                                                                      \
+        if constexpr (MAXCB == 32)                                                                                                       \
+            if (cb == 32) { hipLaunchKernelGGL((k_conv_gemm<WM, WN, TM, TN, 4, TR, 32>), g, dim3(64 * WM * WN), 0, st, a); return; }     \
+        hipLaunchKernelGGL((k_conv_gemm<WM, WN, TM, TN, 4, TR, 16>), g, dim3(64 * WM * WN), 0, st, a);                                   \
+        return;                                                                                                                          \
+    }
+    CONV_TILE_SHAPES(X)
+#undef X
+    assert(!"launch_tile: shape not in CONV_TILE_SHAPES");   // not reached: choose_cfg picks table shapes only, tuning_ok refuses any other forced shape
 }
 
 // stream-K launch: G persistent workgroups over tiles x chunks (see k_conv_gemm_sk).  workspace = [flags | slabs]
@@ -2754,6 +2693,12 @@ enum GemmKind { GK_SCALAR, GK_STREAMK, GK_TILE };
 enum GemmTail { GT_NONE, GT_SPLITK4, GT_SPLITK, GT_CLS };
 struct GemmLaunch { GemmKind kind; GemmTail tail; GemmCfg c; int cb; dim3 g; int G; };
 
+// The stride-2 class form of backward-data: 4 parity classes of up to ceil(Hd/2) x ceil(Wd/2) pixels per image.  Where plan_gemm slices
+// the classes by tap (GT_CLS), every (tap slice, class) pair owns a slab of cls_rows x cols partial sums.
+#define CLS_TAP_SLICES 4
+static int64_t cls_rows(int B, int Hd, int Wd) { return (int64_t)B * ((Hd + 1) / 2) * ((Wd + 1) / 2); }
+static int64_t cls_slab_floats(int B, int Hd, int Wd, int cols) { return CLS_TAP_SLICES * 4 * cls_rows(B, Hd, Wd) * cols; }
+
 template <bool TR>
 static GemmLaunch plan_gemm(ConvArgs& a, int vec, float* workspace_all, GemmCfg force) {
     GemmLaunch p{GK_TILE, GT_NONE, GemmCfg{0, 0, 0}, 16, dim3(1), 0};
@@ -2774,9 +2719,9 @@ static GemmLaunch plan_gemm(ConvArgs& a, int vec, float* workspace_all, GemmCfg 
     if (TR && a.cls) {
         // 4 parity classes x the tiles of the largest class (ceil(Hd/2) x ceil(Wd/2) pixels per image); blockIdx.x & 3 = class.
         // The classes carry 1, 2, 2 and 4 of the 9 taps: price the decomposition on the average (K * 9/16 of a class of Nc rows x 4)
-        const int64_t Nc = (int64_t)a.B * ((a.Hd + 1) / 2) * ((a.Wd + 1) / 2);
+        const int64_t Nc = cls_rows(a.B, a.Hd, a.Wd);
         GemmCfg c = choose_cfg(Nc * 4, a.Ncols, (K * 9 / 16 + cb - 1) / cb * cb, cb, false, force.S < 0 ? GemmCfg{0, 0, 0} : force);
-        if (c.bm == 128 && c.bn == 128) c.bn = 64;
+        demote_cb16_only(c);
         p.c = c;
         // The classes of a 3x3 kernel carry 4, 2, 2 and 1 taps: with so few workgroups the launch lasts as long as a 4-tap one
         // (l4.0.conv1: 57 us against 26 us for the forward).  Slice every class by TAP: equal work per workgroup, partial sums in
@@ -2785,8 +2730,8 @@ static GemmLaunch plan_gemm(ConvArgs& a, int vec, float* workspace_all, GemmCfg 
         const int64_t cls_wgs = 4 * ((Nc + c.bm - 1) / c.bm) * ((a.Ncols + c.bn - 1) / c.bn);     // measured: 304 workgroups 49.7 -> 38.6 us, 160: 57.6 -> 35.1, 600: 39 -> 40
         if (workspace && cls_wgs < 500 && a.KH == 3 && a.KW == 3 && a.Cin % cb == 0 && a.Ncols % 4 == 0 && total < (1ll << 31) && !a.scale && !a.shift &&
             a.act == ACT_NONE) {
-            a.ksplit = 4; a.cps = a.Cin / cb; a.cls_rows = Nc;
-            p.g = dim3((unsigned)(4 * ((Nc + c.bm - 1) / c.bm)), (unsigned)((a.Ncols + c.bn - 1) / c.bn), 4u);
+            a.ksplit = CLS_TAP_SLICES; a.cps = a.Cin / cb; a.cls_rows = Nc;
+            p.g = dim3((unsigned)(4 * ((Nc + c.bm - 1) / c.bm)), (unsigned)((a.Ncols + c.bn - 1) / c.bn), (unsigned)CLS_TAP_SLICES);
             p.tail = GT_CLS;
             return p;
         }
@@ -2867,15 +2812,6 @@ int e2e_conv_weight_layouts_batched(const long long* desc, int nlayers, void* st
 
 /* floats of workspace a GEMM of `rows` x `cols` with reduction length K may use: the stream-K flag region (SK_FLAG_FLOATS, which the
  * owner zeroes ONCE after allocating) followed by split-K slabs or stream-K slabs, whichever is larger (0: the layer takes neither) */
-int64_t e2e_conv2d_splitk_workspace_floats(int64_t rows, int cols, int K);
-/* workspace of a backward-data call: the split-K slabs of the stride-1 form, or the (tap, class) slabs of the stride-2 class form */
-int64_t e2e_conv2d_bwd_data_workspace_floats(int B, int Hd, int Wd, int cols, int K, int stride) {
-    const int64_t plain = e2e_conv2d_splitk_workspace_floats((int64_t)B * Hd * Wd, cols, K);
-    if (stride != 2) return plain;
-    const int64_t cls = SK_FLAG_FLOATS + (int64_t)16 * B * ((Hd + 1) / 2) * ((Wd + 1) / 2) * cols;      // 4 tap slices x 4 classes x the largest class
-    return cls > plain ? cls : plain;
-}
-
 int64_t e2e_conv2d_splitk_workspace_floats(int64_t rows, int cols, int K) {
     if (K % 16 != 0) return 0;
     int smax = 1;                                            // the largest slice count any chunk depth would choose
@@ -2888,6 +2824,14 @@ int64_t e2e_conv2d_splitk_workspace_floats(int64_t rows, int cols, int K) {
     int64_t n = smax > 1 ? (int64_t)smax * rows * cols : 0;
     if (sk && n < (int64_t)SK_MAX_G * 64 * 64) n = (int64_t)SK_MAX_G * 64 * 64;
     return n ? n + SK_FLAG_FLOATS : 0;
+}
+
+/* workspace of a backward-data call: the split-K slabs of the stride-1 form, or the (tap, class) slabs of the stride-2 class form */
+int64_t e2e_conv2d_bwd_data_workspace_floats(int B, int Hd, int Wd, int cols, int K, int stride) {
+    const int64_t plain = e2e_conv2d_splitk_workspace_floats((int64_t)B * Hd * Wd, cols, K);
+    if (stride != 2) return plain;
+    const int64_t cls = SK_FLAG_FLOATS + cls_slab_floats(B, Hd, Wd, cols);
+    return cls > plain ? cls : plain;
 }
 
 /* workspace that covers ANY tile / split-K (<= 16 slices) / stream-K choice of a *_tuned call on a GEMM of rows x cols */
@@ -2907,12 +2851,27 @@ int e2e_conv_gemm_choice(int64_t rows, int cols, int K, int chunk_depth, int all
     return E2E_OK;
 }
 
-static int conv_fwd_impl(const float* src0, const float* src1, int C1, int up, const float* w_fwd, int ld_fwd, const float* scale,
-                         const float* shift, const float* residual, float* out, int B, int Hs, int Ws, int Cin, int Cout, int KH,
-                         int KW, int stride, int pad, int pad_mode, int act, float in_sub, float in_mul, float* workspace, GemmCfg force, void* stream) {
-    E2E_REQUIRE(src0 && w_fwd && out && B > 0 && Hs > 0 && Ws > 0 && Cin > 0 && Cout > 0, E2E_ERR_ARG, "e2e_conv2d_fwd: bad argument");
+// The geometry of one convolution call: batch, the full-resolution source grid Hs x Ws (the first C1 of the Cin channels upsampled by `up`), output
+// channels and grid, kernel, stride, padding (pad_mode 1: reflection), input normalisation.  Forward calls leave Ho / Wo to the implementation.
+struct ConvGeom { int B, Hs, Ws, Cin, Cout, Ho, Wo, KH, KW, stride, pad, pad_mode, C1, up; float in_sub, in_mul; };
+// Every entry point names these arguments alike; the macros bind them BY NAME, once (a positional list lets Hs and Ho swap unnoticed).
+#define GEOM_LAYER(g) ConvGeom g{}; g.B = B; g.Hs = Hs; g.Ws = Ws; g.Cin = Cin; g.Cout = Cout; g.KH = KH; g.KW = KW; g.stride = stride; g.pad = pad; g.pad_mode = pad_mode
+#define GEOM_SOURCES(g) g.C1 = C1; g.up = up; g.in_sub = in_sub; g.in_mul = in_mul
+#define GEOM_OUTPUT(g) g.Ho = Ho; g.Wo = Wo
+#define GEOM_BWD_DATA(g) GEOM_LAYER(g); GEOM_OUTPUT(g)
+#define GEOM_BWD_WEIGHT(g) GEOM_LAYER(g); GEOM_OUTPUT(g); GEOM_SOURCES(g)
+#define GEOM_WGRAD_QUERY(g) ConvGeom g{}; g.B = B; g.Ho = Ho; g.Wo = Wo; g.Cin = Cin; g.Cout = Cout; g.KH = KH; g.KW = KW
+// the operands of a forward, a backward-data and a backward-weight call
+struct FwdOps { const float *src0, *src1, *w_fwd; int ld_fwd; const float *scale, *shift, *residual; float* out; int act; };
+struct BwdDataOps { const float* dz; const float* w_bwd; int ld_bwd; float* dxp; int accumulate; const float* x_in; int in_act; const float* pre_add; };
+struct WgradIn { const float *dz, *src0, *src1; float* workspace; };
+
+static int conv_fwd_impl(const FwdOps& f, const ConvGeom& g, float* workspace, GemmCfg force, void* stream) {
+    const int B = g.B, Hs = g.Hs, Ws = g.Ws, Cin = g.Cin, Cout = g.Cout, KH = g.KH, KW = g.KW, stride = g.stride, pad = g.pad, pad_mode = g.pad_mode;
+    const int C1 = g.C1, up = g.up, ld_fwd = f.ld_fwd;
+    E2E_REQUIRE(f.src0 && f.w_fwd && f.out && B > 0 && Hs > 0 && Ws > 0 && Cin > 0 && Cout > 0, E2E_ERR_ARG, "e2e_conv2d_fwd: bad argument");
     E2E_REQUIRE(up == 1 || up == 2, E2E_ERR_ARG, "e2e_conv2d_fwd: upsample factor must be 1 or 2");
-    E2E_REQUIRE(C1 > 0 && C1 <= Cin && (C1 == Cin || src1), E2E_ERR_ARG, "e2e_conv2d_fwd: bad channel split");
+    E2E_REQUIRE(C1 > 0 && C1 <= Cin && (C1 == Cin || f.src1), E2E_ERR_ARG, "e2e_conv2d_fwd: bad channel split");
     E2E_REQUIRE(pad_mode == 0 || (pad_mode == 1 && pad == 1 && Hs >= 2 && Ws >= 2), E2E_ERR_ARG, "e2e_conv2d_fwd: reflection padding needs pad == 1");
     E2E_REQUIRE(stride == 1 || stride == 2, E2E_ERR_ARG, "e2e_conv2d_fwd: stride must be 1 or 2");
     E2E_REQUIRE(Hs % up == 0 && Ws % up == 0 && ld_fwd % 4 == 0 && ld_fwd >= Cout, E2E_ERR_ARG, "e2e_conv2d_fwd: bad sizes");
@@ -2922,28 +2881,24 @@ static int conv_fwd_impl(const float* src0, const float* src1, int C1, int up, c
                 "e2e_conv2d_fwd: activations must stay below 1 GB, weights below 2 GB (32-bit buffer offsets with out-of-range markers)");
     E2E_REQUIRE(vec != 4 || (KH <= 3 && KW <= 3), E2E_ERR_ARG, "e2e_conv2d_fwd: the channel-quad loader takes kernels up to 3 x 3");
     ConvArgs a{};
-    a.src0 = src0; a.src1 = src1; a.w = w_fwd; a.scale = scale; a.shift = shift; a.res = residual; a.out = out;
+    a.src0 = f.src0; a.src1 = f.src1; a.w = f.w_fwd; a.scale = f.scale; a.shift = f.shift; a.res = f.residual; a.out = f.out;
     a.B = B; a.Hs = Hs; a.Ws = Ws; a.Cin = Cin; a.C1 = C1; a.up = up;
     a.Hd = (Hs + 2 * pad - KH) / stride + 1; a.Wd = (Ws + 2 * pad - KW) / stride + 1;
-    a.Ncols = Cout; a.ldw = ld_fwd; a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad; a.pad_mode = pad_mode; a.off = 0; a.act = act;
-    a.in_sub = in_sub; a.in_mul = in_mul;
+    a.Ncols = Cout; a.ldw = ld_fwd; a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad; a.pad_mode = pad_mode; a.off = 0; a.act = f.act;
+    a.in_sub = g.in_sub; a.in_mul = g.in_mul;
     // the RGB stem: patch kernel
-    if (!force.bm && KH == 7 && KW == 7 && stride == 2 && pad == 3 && pad_mode == 0 && Cin == 3 && Cout == 64 && C1 == Cin && up == 1 && !residual && ld_fwd >= 64) {
-        StemArgs t{src0, w_fwd, scale, shift, out, B, Hs, Ws, a.Hd, a.Wd, ld_fwd, act, in_sub, in_mul};
+    if (!force.bm && KH == 7 && KW == 7 && stride == 2 && pad == 3 && pad_mode == 0 && Cin == 3 && Cout == 64 && C1 == Cin && up == 1 && !f.residual && ld_fwd >= 64) {
+        StemArgs t{f.src0, f.w_fwd, f.scale, f.shift, f.out, B, Hs, Ws, a.Hd, a.Wd, ld_fwd, f.act, g.in_sub, g.in_mul};
         hipLaunchKernelGGL(k_conv7x7_stem, dim3((a.Wd + 31) / 32, (a.Hd + 3) / 4, B), dim3(256), 0, (hipStream_t)stream, t);
-        E2E_LAUNCH_CHECK("e2e_conv2d_fwd");
-        return E2E_OK;
     }
     // the two 16-output-channel layers at the decoder's last level: patch-in-LDS kernel (k_conv3x3_thin)
-    if (!force.bm && KH == 3 && KW == 3 && stride == 1 && pad == 1 && pad_mode == 1 && Cout == 16 && C1 == Cin && !scale && !residual && ld_fwd >= 16 &&
+    else if (!force.bm && KH == 3 && KW == 3 && stride == 1 && pad == 1 && pad_mode == 1 && Cout == 16 && C1 == Cin && !f.scale && !f.residual && ld_fwd >= 16 &&
         ((Cin == 16 && up == 2) || (Cin == 32 && up == 1))) {
-        ThinArgs t{src0, w_fwd, shift, out, B, Hs / up, Ws / up, Hs, Ws, ld_fwd, act, 1, 0};
+        ThinArgs t{f.src0, f.w_fwd, f.shift, f.out, B, Hs / up, Ws / up, Hs, Ws, ld_fwd, f.act, 1, 0};
         if (Cin == 16) hipLaunchKernelGGL((k_conv3x3_thin<16, 2, true, 8>), dim3((Ws + 63) / 64, (Hs + 7) / 8, B), dim3(256), 0, (hipStream_t)stream, t);
         else hipLaunchKernelGGL((k_conv3x3_thin<32, 1, true, 4>), dim3((Ws + 63) / 64, (Hs + 3) / 4, B), dim3(256), 0, (hipStream_t)stream, t);
-        E2E_LAUNCH_CHECK("e2e_conv2d_fwd");
-        return E2E_OK;
-    }
-    launch_gemm<false>(a, vec, workspace, force, (hipStream_t)stream);
+    } else
+        launch_gemm<false>(a, vec, workspace, force, (hipStream_t)stream);
     E2E_LAUNCH_CHECK("e2e_conv2d_fwd");
     return E2E_OK;
 }
@@ -2951,8 +2906,8 @@ static int conv_fwd_impl(const float* src0, const float* src1, int C1, int up, c
 int e2e_conv2d_fwd(const float* src0, const float* src1, int C1, int up, const float* w_fwd, int ld_fwd, const float* scale,
                    const float* shift, const float* residual, float* out, int B, int Hs, int Ws, int Cin, int Cout, int KH,
                    int KW, int stride, int pad, int pad_mode, int act, float in_sub, float in_mul, float* workspace, void* stream) {
-    return conv_fwd_impl(src0, src1, C1, up, w_fwd, ld_fwd, scale, shift, residual, out, B, Hs, Ws, Cin, Cout, KH, KW, stride, pad, pad_mode, act, in_sub, in_mul,
-                         workspace, GemmCfg{0, 0, 0}, stream);
+    GEOM_LAYER(g); GEOM_SOURCES(g);
+    return conv_fwd_impl(FwdOps{src0, src1, w_fwd, ld_fwd, scale, shift, residual, out, act}, g, workspace, GemmCfg{0, 0, 0}, stream);
 }
 
 // a tuned call's decomposition: tile_m x tile_n workgroup tiles; ksplit >= 1: that many K slices, ksplit < 0: stream-K on -ksplit
@@ -2960,7 +2915,7 @@ int e2e_conv2d_fwd(const float* src0, const float* src1, int C1, int up, const f
 static bool tuning_ok(int tile_m, int tile_n, int ksplit) {
     if (tile_m == 0) return true;
     if (ksplit < 0) return tile_m == 64 && tile_n == 64 && -ksplit <= SK_MAX_G;
-    return tile_waves(tile_m, tile_n) != 0 && ksplit >= 1 && ksplit <= 16;
+    return tile_max_cb(tile_m, tile_n) != 0 && ksplit >= 1 && ksplit <= 16;
 }
 
 int e2e_conv2d_fwd_tuned(const float* src0, const float* src1, int C1, int up, const float* w_fwd, int ld_fwd, const float* scale,
@@ -2968,32 +2923,32 @@ int e2e_conv2d_fwd_tuned(const float* src0, const float* src1, int C1, int up, c
                          int KW, int stride, int pad, int pad_mode, int act, float in_sub, float in_mul, float* workspace, int tile_m, int tile_n,
                          int ksplit, void* stream) {
     E2E_REQUIRE(tuning_ok(tile_m, tile_n, ksplit), E2E_ERR_ARG, "e2e_conv2d_fwd_tuned: unsupported decomposition %d x %d / %d", tile_m, tile_n, ksplit);
-    return conv_fwd_impl(src0, src1, C1, up, w_fwd, ld_fwd, scale, shift, residual, out, B, Hs, Ws, Cin, Cout, KH, KW, stride, pad, pad_mode, act, in_sub, in_mul,
-                         workspace, GemmCfg{tile_m, tile_n, ksplit}, stream);
+    GEOM_LAYER(g); GEOM_SOURCES(g);
+    return conv_fwd_impl(FwdOps{src0, src1, w_fwd, ld_fwd, scale, shift, residual, out, act}, g, workspace, GemmCfg{tile_m, tile_n, ksplit}, stream);
 }
 
 // backward-data up to its GEMM: checks the arguments, serves the 16 -> 16 reflection-padded layer with its patch kernel (*done = true), or
 // fills the GEMM's ConvArgs (and zeroes the classes a 1x1 stride-2 kernel does not reach).  Shared by bwd_data_impl and the paired backward.
-static int bwd_data_setup(const float* dz, const float* w_bwd, int ld_bwd, float* dxp, int B, int Hs, int Ws, int Cin, int Cout, int Ho, int Wo,
-                          int KH, int KW, int stride, int pad, int pad_mode, int accumulate, const float* x_in, int in_act, const float* pre_add,
-                          GemmCfg force, hipStream_t stream, ConvArgs& a, bool& done) {
+static int bwd_data_setup(const BwdDataOps& d, const ConvGeom& g, GemmCfg force, hipStream_t stream, ConvArgs& a, bool& done) {
+    const int B = g.B, Hs = g.Hs, Ws = g.Ws, Cin = g.Cin, Cout = g.Cout, Ho = g.Ho, Wo = g.Wo, KH = g.KH, KW = g.KW, stride = g.stride, pad = g.pad;
+    const int pad_mode = g.pad_mode, ld_bwd = d.ld_bwd;
     done = false;
-    E2E_REQUIRE(pre_add == nullptr || pad_mode == 0, E2E_ERR_ARG, "e2e_conv2d_bwd_data: the pre-activation addend takes a zero-padded layer");
-    E2E_REQUIRE(in_act == 0 || (x_in && (in_act == ACT_RELU || in_act == ACT_ELU) && pad_mode == 0), E2E_ERR_ARG,
+    E2E_REQUIRE(d.pre_add == nullptr || pad_mode == 0, E2E_ERR_ARG, "e2e_conv2d_bwd_data: the pre-activation addend takes a zero-padded layer");
+    E2E_REQUIRE(d.in_act == 0 || (d.x_in && (d.in_act == ACT_RELU || d.in_act == ACT_ELU) && pad_mode == 0), E2E_ERR_ARG,
                 "e2e_conv2d_bwd_data: the fused input-activation derivative takes ReLU / ELU, the activation's output and a zero-padded layer");
-    E2E_REQUIRE(dz && w_bwd && dxp && B > 0 && Cin > 0 && Cout > 0 && Cout % 16 == 0, E2E_ERR_ARG, "e2e_conv2d_bwd_data: bad argument (Cout %% 16 == 0)");
+    E2E_REQUIRE(d.dz && d.w_bwd && d.dxp && B > 0 && Cin > 0 && Cout > 0 && Cout % 16 == 0, E2E_ERR_ARG, "e2e_conv2d_bwd_data: bad argument (Cout %% 16 == 0)");
     E2E_REQUIRE(ld_bwd % 4 == 0 && ld_bwd >= Cin && (stride == 1 || stride == 2), E2E_ERR_ARG, "e2e_conv2d_bwd_data: bad sizes");
     E2E_REQUIRE((int64_t)B * Ho * Wo * Cout * 4 < (1ll << 30) && (int64_t)KH * KW * Cout * ld_bwd * 4 < (1ll << 31) && KH <= 3 && KW <= 3, E2E_ERR_ARG,
                 "e2e_conv2d_bwd_data: gradients must stay below 1 GB, weights below 2 GB (32-bit buffer offsets), kernels up to 3 x 3");
     // 16 -> 16 channels on the padded grid of a reflection-padded layer (upconv(0,1)): dXp[q] = sum_t dZ[q - t] Wb[t], patch kernel
-    if (!force.bm && KH == 3 && KW == 3 && stride == 1 && pad == 1 && pad_mode == 1 && Cin == 16 && Cout == 16 && !accumulate && !in_act && !pre_add && ld_bwd >= 16) {
-        ThinArgs t{dz, w_bwd, nullptr, dxp, B, Ho, Wo, Hs + 2, Ws + 2, ld_bwd, ACT_NONE, 2, 1};
+    if (!force.bm && KH == 3 && KW == 3 && stride == 1 && pad == 1 && pad_mode == 1 && Cin == 16 && Cout == 16 && !d.accumulate && !d.in_act && !d.pre_add && ld_bwd >= 16) {
+        ThinArgs t{d.dz, d.w_bwd, nullptr, d.dxp, B, Ho, Wo, Hs + 2, Ws + 2, ld_bwd, ACT_NONE, 2, 1};
         hipLaunchKernelGGL((k_conv3x3_thin<16, 1, false, 8>), dim3((Ws + 2 + 63) / 64, (Hs + 2 + 7) / 8, B), dim3(256), 0, stream, t);
         done = true;
         return E2E_OK;
     }
     a = ConvArgs{};
-    a.src0 = dz; a.src1 = nullptr; a.w = w_bwd; a.out = dxp;
+    a.src0 = d.dz; a.src1 = nullptr; a.w = d.w_bwd; a.out = d.dxp;
     a.B = B; a.Hs = Ho; a.Ws = Wo; a.Cin = Cout; a.C1 = Cout; a.up = 1;
     const int pp = pad_mode == 1 ? pad : 0;                // reflect: produce the whole padded domain, folded afterwards
     a.Hd = Hs + 2 * pp; a.Wd = Ws + 2 * pp; a.off = pad_mode == 1 ? 0 : pad;
@@ -3001,22 +2956,19 @@ static int bwd_data_setup(const float* dz, const float* w_bwd, int ld_bwd, float
     // stride 2: parity classes (each input-gradient pixel only visits the taps that reach it).  A 1x1 kernel reaches one class
     // only -- the other three quarters of dxp are zeros, written by a memset node on the same stream.
     // (class lattices of 2^24 rows or more take the plain transposed form: the class epilogue decodes its rows in fp32)
-    a.cls = (stride == 2 && (int64_t)B * ((a.Hd + 1) / 2) * ((a.Wd + 1) / 2) < (1 << 24)) ? 1 : 0;
-    if (a.cls && (KH < 2 || KW < 2) && !accumulate)
-        (void)hipMemsetAsync(dxp, 0, (size_t)B * a.Hd * a.Wd * Cin * sizeof(float), stream);
+    a.cls = (stride == 2 && cls_rows(B, a.Hd, a.Wd) < (1 << 24)) ? 1 : 0;
+    if (a.cls && (KH < 2 || KW < 2) && !d.accumulate)
+        (void)hipMemsetAsync(d.dxp, 0, (size_t)B * a.Hd * a.Wd * Cin * sizeof(float), stream);
     // accumulate: dxp += result -- the epilogue's residual input reads the element it is about to overwrite (same thread)
-    if (accumulate) a.res = dxp;
-    a.xin = in_act ? x_in : nullptr; a.dact = in_act; a.pre = pre_add;
+    if (d.accumulate) a.res = d.dxp;
+    a.xin = d.in_act ? d.x_in : nullptr; a.dact = d.in_act; a.pre = d.pre_add;
     return E2E_OK;
 }
 
-static int bwd_data_impl(const float* dz, const float* w_bwd, int ld_bwd, float* dxp, int B, int Hs, int Ws, int Cin, int Cout, int Ho, int Wo,
-                         int KH, int KW, int stride, int pad, int pad_mode, int accumulate, const float* x_in, int in_act, const float* pre_add,
-                         float* workspace, void* stream, GemmCfg force = GemmCfg{0, 0, 0}) {
+static int bwd_data_impl(const BwdDataOps& d, const ConvGeom& g, float* workspace, void* stream, GemmCfg force = GemmCfg{0, 0, 0}) {
     ConvArgs a;
     bool done;
-    const int rc = bwd_data_setup(dz, w_bwd, ld_bwd, dxp, B, Hs, Ws, Cin, Cout, Ho, Wo, KH, KW, stride, pad, pad_mode, accumulate, x_in, in_act, pre_add,
-                                  force, (hipStream_t)stream, a, done);
+    const int rc = bwd_data_setup(d, g, force, (hipStream_t)stream, a, done);
     if (rc != E2E_OK) return rc;
     if (!done) launch_gemm<true>(a, 4, workspace, force, (hipStream_t)stream);
     E2E_LAUNCH_CHECK("e2e_conv2d_bwd_data");
@@ -3025,45 +2977,49 @@ static int bwd_data_impl(const float* dz, const float* w_bwd, int ld_bwd, float*
 
 int e2e_conv2d_bwd_data(const float* dz, const float* w_bwd, int ld_bwd, float* dxp, int B, int Hs, int Ws, int Cin, int Cout,
                         int Ho, int Wo, int KH, int KW, int stride, int pad, int pad_mode, float* workspace, void* stream) {
-    return bwd_data_impl(dz, w_bwd, ld_bwd, dxp, B, Hs, Ws, Cin, Cout, Ho, Wo, KH, KW, stride, pad, pad_mode, 0, nullptr, 0, nullptr, workspace, stream);
+    GEOM_BWD_DATA(g);
+    return bwd_data_impl(BwdDataOps{dz, w_bwd, ld_bwd, dxp, 0, nullptr, 0, nullptr}, g, workspace, stream);
 }
 
 int e2e_conv2d_bwd_data_acc(const float* dz, const float* w_bwd, int ld_bwd, float* dxp, int B, int Hs, int Ws, int Cin, int Cout,
                             int Ho, int Wo, int KH, int KW, int stride, int pad, int pad_mode, int accumulate, float* workspace,
                             void* stream) {
-    return bwd_data_impl(dz, w_bwd, ld_bwd, dxp, B, Hs, Ws, Cin, Cout, Ho, Wo, KH, KW, stride, pad, pad_mode, accumulate, nullptr, 0, nullptr, workspace, stream);
+    GEOM_BWD_DATA(g);
+    return bwd_data_impl(BwdDataOps{dz, w_bwd, ld_bwd, dxp, accumulate, nullptr, 0, nullptr}, g, workspace, stream);
 }
 
 int e2e_conv2d_bwd_data_fused(const float* da, const float* w_bwd, int ld_bwd, float* dxp, int B, int Hs, int Ws, int Cin, int Cout,
                               int Ho, int Wo, int KH, int KW, int stride, int pad, int pad_mode, int accumulate, const float* x_in,
                               int in_act, const float* pre_add, float* workspace, void* stream) {
-    return bwd_data_impl(da, w_bwd, ld_bwd, dxp, B, Hs, Ws, Cin, Cout, Ho, Wo, KH, KW, stride, pad, pad_mode, accumulate, x_in, in_act, pre_add, workspace,
-                         stream);
+    GEOM_BWD_DATA(g);
+    return bwd_data_impl(BwdDataOps{da, w_bwd, ld_bwd, dxp, accumulate, x_in, in_act, pre_add}, g, workspace, stream);
 }
 
 int e2e_conv2d_bwd_data_fused_tuned(const float* da, const float* w_bwd, int ld_bwd, float* dxp, int B, int Hs, int Ws, int Cin, int Cout,
                                     int Ho, int Wo, int KH, int KW, int stride, int pad, int pad_mode, int accumulate, const float* x_in,
                                     int in_act, const float* pre_add, float* workspace, int tile_m, int tile_n, int ksplit, void* stream) {
     E2E_REQUIRE(tuning_ok(tile_m, tile_n, ksplit), E2E_ERR_ARG, "e2e_conv2d_bwd_data_fused_tuned: unsupported decomposition %d x %d / %d", tile_m, tile_n, ksplit);
-    return bwd_data_impl(da, w_bwd, ld_bwd, dxp, B, Hs, Ws, Cin, Cout, Ho, Wo, KH, KW, stride, pad, pad_mode, accumulate, x_in, in_act, pre_add, workspace,
-                         stream, GemmCfg{tile_m, tile_n, ksplit});
+    GEOM_BWD_DATA(g);
+    return bwd_data_impl(BwdDataOps{da, w_bwd, ld_bwd, dxp, accumulate, x_in, in_act, pre_add}, g, workspace, stream, GemmCfg{tile_m, tile_n, ksplit});
 }
 
 // launch the adjoint of pad + upsample + concat: 16-byte channel quads when the channel split allows, 32-bit indices
-static void launch_gather_adjoint(const float* dxp, int B, int Hs, int Ws, int Cin, int C1, int up, int padded, float* d0, float* d1, int acc0, int acc1,
-                                  const float* x0, int act0, const float* x1, int act1, hipStream_t st) {
-    const int64_t n = (int64_t)B * (Hs / up) * (Ws / up) * C1 + (int64_t)B * Hs * Ws * (Cin - C1);
-    if (Cin % 4 == 0 && C1 % 4 == 0 && n < (1ll << 31))
-        hipLaunchKernelGGL(k_gather_adjoint4, dim3(egrid(n / 4)), dim3(256), 0, st, dxp, B, Hs, Ws, Cin, C1, up, padded ? 1 : 0, d0, d1, acc0, acc1, x0, act0, x1, act1);
+struct GatherAdjoint { const float* dxp; int B, Hs, Ws, Cin, C1, up, padded; float *d0, *d1; int acc0, acc1; const float* x0; int act0; const float* x1; int act1; };
+static void launch_gather_adjoint(const GatherAdjoint& q, hipStream_t st) {
+    const int64_t n = (int64_t)q.B * (q.Hs / q.up) * (q.Ws / q.up) * q.C1 + (int64_t)q.B * q.Hs * q.Ws * (q.Cin - q.C1);
+    if (q.Cin % 4 == 0 && q.C1 % 4 == 0 && n < (1ll << 31))
+        hipLaunchKernelGGL(k_gather_adjoint4, dim3(egrid(n / 4)), dim3(256), 0, st, q.dxp, q.B, q.Hs, q.Ws, q.Cin, q.C1, q.up, q.padded ? 1 : 0, q.d0, q.d1, q.acc0, q.acc1,
+                           q.x0, q.act0, q.x1, q.act1);
     else
-        hipLaunchKernelGGL(k_gather_adjoint, dim3(egrid(n)), dim3(256), 0, st, dxp, B, Hs, Ws, Cin, C1, up, padded ? 1 : 0, d0, d1, acc0, acc1, x0, act0, x1, act1);
+        hipLaunchKernelGGL(k_gather_adjoint, dim3(egrid(n)), dim3(256), 0, st, q.dxp, q.B, q.Hs, q.Ws, q.Cin, q.C1, q.up, q.padded ? 1 : 0, q.d0, q.d1, q.acc0, q.acc1,
+                           q.x0, q.act0, q.x1, q.act1);
 }
 
 int e2e_conv2d_gather_adjoint(const float* dxp, int B, int Hs, int Ws, int Cin, int C1, int up, int padded, float* d_src0,
                               float* d_src1, int accumulate0, int accumulate1, void* stream) {
     E2E_REQUIRE(dxp && d_src0 && B > 0 && Cin > 0 && C1 > 0 && C1 <= Cin && (C1 == Cin || d_src1) && (up == 1 || up == 2), E2E_ERR_ARG,
                 "e2e_conv2d_gather_adjoint: bad argument");
-    launch_gather_adjoint(dxp, B, Hs, Ws, Cin, C1, up, padded, d_src0, d_src1, accumulate0, accumulate1, nullptr, 0, nullptr, 0, (hipStream_t)stream);
+    launch_gather_adjoint(GatherAdjoint{dxp, B, Hs, Ws, Cin, C1, up, padded, d_src0, d_src1, accumulate0, accumulate1, nullptr, 0, nullptr, 0}, (hipStream_t)stream);
     E2E_LAUNCH_CHECK("e2e_conv2d_gather_adjoint");
     return E2E_OK;
 }
@@ -3074,7 +3030,7 @@ int e2e_conv2d_gather_adjoint_act(const float* dxp, int B, int Hs, int Ws, int C
                 "e2e_conv2d_gather_adjoint_act: bad argument");
     E2E_REQUIRE((act0 == 0 || src0) && (act1 == 0 || src1) && act0 >= 0 && act0 <= 2 && act1 >= 0 && act1 <= 2, E2E_ERR_ARG,
                 "e2e_conv2d_gather_adjoint_act: an activation derivative needs the activation's output");
-    launch_gather_adjoint(dxp, B, Hs, Ws, Cin, C1, up, padded, d_src0, d_src1, accumulate0, accumulate1, src0, act0, src1, act1, (hipStream_t)stream);
+    launch_gather_adjoint(GatherAdjoint{dxp, B, Hs, Ws, Cin, C1, up, padded, d_src0, d_src1, accumulate0, accumulate1, src0, act0, src1, act1}, (hipStream_t)stream);
     E2E_LAUNCH_CHECK("e2e_conv2d_gather_adjoint_act");
     return E2E_OK;
 }
@@ -3102,8 +3058,8 @@ int e2e_head_fwd(const float* x, const float* w, const float* bias, float* y, in
     return E2E_OK;
 }
 int64_t e2e_head_workspace_floats(void) { return (int64_t)HEAD_PARTS * (9 * HC + 1); }
-static int head_bwd_impl(const float* dz, const float* x, const float* w, float* dx, float* dw, float* dbias, float* workspace, int B, int H,
-                         int W, int Cin, int in_act, void* stream) {
+int e2e_head_bwd_act(const float* dz, const float* x, const float* w, float* dx, float* dw, float* dbias, float* workspace, int B, int H,
+                     int W, int Cin, int in_act, void* stream) {
     E2E_REQUIRE(dz && x && w && workspace && B > 0 && H >= 2 && W >= 2 && Cin == HC && in_act >= 0 && in_act <= 2, E2E_ERR_ARG, "e2e_head_bwd: bad argument");
     E2E_REQUIRE((int64_t)B * H * W * HC < (1ll << 31), E2E_ERR_ARG, "e2e_head_bwd: activation too large for 32-bit element offsets");
     hipStream_t st = (hipStream_t)stream;
@@ -3118,92 +3074,104 @@ static int head_bwd_impl(const float* dz, const float* x, const float* w, float*
 
 int e2e_head_bwd(const float* dz, const float* x, const float* w, float* dx, float* dw, float* dbias, float* workspace, int B, int H,
                  int W, int Cin, void* stream) {
-    return head_bwd_impl(dz, x, w, dx, dw, dbias, workspace, B, H, W, Cin, 0, stream);
+    return e2e_head_bwd_act(dz, x, w, dx, dw, dbias, workspace, B, H, W, Cin, 0, stream);
 }
 
-int e2e_head_bwd_act(const float* dz, const float* x, const float* w, float* dx, float* dw, float* dbias, float* workspace, int B, int H,
-                     int W, int Cin, int in_act, void* stream) {
-    return head_bwd_impl(dz, x, w, dx, dw, dbias, workspace, B, H, W, Cin, in_act, stream);
-}
-
-// backward-weight decomposition shared by the workspace query and the launch: tile shape, padded GEMM size, pixel slices
-struct WgradPlan { int tm, tn, Mpad, Npad; int64_t S; };
-static WgradPlan wgrad_plan(int B, int Ho, int Wo, int Cin, int Cout, int KH, int KW, int has_bias, bool use16, int wg_target = WGRAD_TARGET) {
-    WgradPlan p;
-    const int Ng = KH * KW * Cin + (has_bias ? 1 : 0);
-    p.tm = Cout <= 32 ? 32 : 64; p.tn = Cout <= 32 ? 128 : 64;        // 32x128 tiles for the thin layers
-    if (use16) { p.tm = 16; p.tn = 160; }                              // k_wgrad_gemm16 (16x16x4 MFMA tiles)
-    p.Mpad = (Cout + p.tm - 1) / p.tm * p.tm; p.Npad = (Ng + p.tn - 1) / p.tn * p.tn;
-    const int64_t P = (int64_t)B * Ho * Wo;
-    const int64_t tiles = (int64_t)(p.Mpad / p.tm) * (p.Npad / p.tn);
-    const int target = use16 ? wg_target * 3 / 4 : wg_target;     // measured: 768 slices suit the 16-channel kernel (94 vs 110 us)
-    int64_t S = (target + tiles - 1) / tiles;                // pixel slices: ~target workgroups in total
-    const int64_t maxS = (P + 255) / 256;                   // at least 256 pixels per slice
-    if (S > maxS) S = maxS;
-    if (S < 1) S = 1;
-    p.S = S;
-    return p;
-}
-
-// decomposition of k_wgrad3x3_thin: workgroups of `tiles_x` consecutive 4 x 64 tiles, ~1200 of them; one slab per workgroup position
-struct ThinWgradPlan { int tiles_x, nxg, ny, npad; int64_t S; };
-// measured against the implicit-GEMM kernels (tools/gemm_tune.py wgrad): upconv(0,1) 16 -> 16: 94 -> 66 us, upconv(0,0) 32 -> 16: 55 -> 45 us,
-// upconv(1,1) 96 -> 32: 174 -> 142 us; upconv(1,0) 64 -> 32 is faster as a GEMM (39 vs 46 us) and stays there
-static bool thin_wgrad_ok(int Cin, int Cout, int KH, int KW) {
-    return KH == 3 && KW == 3 && ((Cout == 16 && (Cin == 16 || Cin == 32)) || (Cout == 32 && Cin == 96));
-}
-static ThinWgradPlan thin_wgrad_plan(int B, int Ho, int Wo, int Cin, int has_bias) {
-    ThinWgradPlan p;
-    const int txt = (Wo + 63) / 64;
-    p.ny = (Ho + 3) / 4;
-    const int64_t total = (int64_t)B * p.ny * txt * (Cin / 16);
-    p.tiles_x = 1;
-    while (total / p.tiles_x > 1400 && p.tiles_x < txt) ++p.tiles_x;
-    p.nxg = (txt + p.tiles_x - 1) / p.tiles_x;
-    p.S = (int64_t)B * p.ny * p.nxg;
-    p.npad = (9 * Cin + (has_bias ? 1 : 0) + 3) / 4 * 4;
-    return p;
-}
-
-// decomposition of k_wgrad3x3_taps: (Cin / 32) x (Cout / 32) tiles x S pixel slices of whole 8 x 8 patches, ~TAP_TARGET workgroups of 3 waves
+// Backward-weight.  Every path ends in partial-sum slabs [S][Mpad][Npad] in the caller's workspace and the common slab reduction.
+// wgrad_plan is the ONLY place a path's decomposition and slab size are worked out: the launch (wgrad_choose, wgrad_setup) and the workspace
+// queries both call it.  It reads B, Ho, Wo, Cin, Cout, KH and KW of the geometry and nothing else -- all a query is given -- and answers
+// open == false where these channels and this kernel size never take the path: a query sizes for the open paths, a call takes one of them.
+enum WgradPath { WP_STEM, WP_THIN, WP_TAPS, WP_GEMM16, WP_GEMM_LEAN, WP_GEMM, WP_COUNT };
+// tm, tn: tile shape (implicit GEMM); nxg, ny, tiles_x: workgroup grid, tiles per workgroup (stem, thin); ptx .. cps: 8 x 8 patches, patches per slice (taps)
+struct WgradPlan { WgradPath path; bool open; int64_t S; int Mpad, Npad, tm, tn, nxg, ny, tiles_x, ptx, pty, nchunks, cps; };
 #define TAP_TARGET 640
-struct TapWgradPlan { int ptx, pty, nchunks, cps, S, Npad; };
-static bool tap_wgrad_shape_ok(int Cin, int Cout, int KH, int KW) { return KH == 3 && KW == 3 && Cin % 32 == 0 && Cout % 32 == 0; }
-static TapWgradPlan tap_wgrad_plan(int B, int H, int W, int Cin, int Cout, int has_bias) {
-    TapWgradPlan p;
-    p.ptx = (W + 7) / 8; p.pty = (H + 7) / 8;
-    p.nchunks = B * p.ptx * p.pty;
-    const int tiles = (Cin / 32) * (Cout / 32);
-    static const int target = getenv("E2E_TAP_TARGET") ? atoi(getenv("E2E_TAP_TARGET")) : TAP_TARGET;      // (diagnostic sweep; read once)
-    int S = (target + tiles - 1) / tiles;
-    if (S > p.nchunks) S = p.nchunks;
-    if (S < 1) S = 1;
-    p.cps = (p.nchunks + S - 1) / S;
-    p.S = (p.nchunks + p.cps - 1) / p.cps;
-    p.Npad = (9 * Cin + (has_bias ? 1 : 0) + 3) / 4 * 4;
+static WgradPlan wgrad_plan(WgradPath path, const ConvGeom& g, int has_bias, bool tuned, int wg_target) {
+    const int B = g.B, Ho = g.Ho, Wo = g.Wo, Cin = g.Cin, Cout = g.Cout, KH = g.KH, KW = g.KW;
+    WgradPlan p{path};
+    // (the patch kernels serve untuned calls only: a tuned call runs the implicit GEMM, and its workspace query does not cover their slabs)
+    if (path == WP_STEM) {                                   // k_wgrad7x7_stem: one slab [64][148] per pair of 4 x 32 tiles
+        if (tuned || !(KH == 7 && KW == 7 && Cin == 3 && Cout == 64)) return p;
+        p.nxg = ((Wo + 31) / 32 + 1) / 2; p.ny = (Ho + 3) / 4;
+        p.S = (int64_t)B * p.ny * p.nxg; p.Mpad = 64; p.Npad = 148;
+    } else if (path == WP_THIN) {    // k_wgrad3x3_thin: workgroups of `tiles_x` consecutive 4 x 64 tiles, ~1200 of them; one slab per workgroup position
+        // measured against the implicit-GEMM kernels (tools/gemm_tune.py wgrad): upconv(0,1) 16 -> 16: 94 -> 66 us, upconv(0,0) 32 -> 16: 55 -> 45 us,
+        // upconv(1,1) 96 -> 32: 174 -> 142 us; upconv(1,0) 64 -> 32 is faster as a GEMM (39 vs 46 us) and stays there
+        if (tuned || !(KH == 3 && KW == 3 && ((Cout == 16 && (Cin == 16 || Cin == 32)) || (Cout == 32 && Cin == 96)))) return p;
+        const int txt = (Wo + 63) / 64;
+        p.ny = (Ho + 3) / 4;
+        const int64_t total = (int64_t)B * p.ny * txt * (Cin / 16);
+        p.tiles_x = 1;
+        while (total / p.tiles_x > 1400 && p.tiles_x < txt) ++p.tiles_x;
+        p.nxg = (txt + p.tiles_x - 1) / p.tiles_x;
+        p.S = (int64_t)B * p.ny * p.nxg; p.Mpad = Cout; p.Npad = (9 * Cin + (has_bias ? 1 : 0) + 3) / 4 * 4;
+    } else if (path == WP_TAPS) {    // k_wgrad3x3_taps: (Cin / 32) x (Cout / 32) tiles x S pixel slices of whole 8 x 8 patches, ~TAP_TARGET workgroups of 3 waves
+        if (tuned || !(KH == 3 && KW == 3 && Cin % 32 == 0 && Cout % 32 == 0)) return p;
+        p.ptx = (Wo + 7) / 8; p.pty = (Ho + 7) / 8;
+        p.nchunks = B * p.ptx * p.pty;
+        const int tiles = (Cin / 32) * (Cout / 32);
+        int S = (TAP_TARGET + tiles - 1) / tiles;
+        if (S > p.nchunks) S = p.nchunks;
+        if (S < 1) S = 1;
+        p.cps = (p.nchunks + S - 1) / S;
+        p.S = (p.nchunks + p.cps - 1) / p.cps; p.Mpad = Cout; p.Npad = (9 * Cin + (has_bias ? 1 : 0) + 3) / 4 * 4;
+    } else {                                                 // the implicit-GEMM kernels: tile shape, padded GEMM size, pixel slices
+        const bool use16 = path == WP_GEMM16;                // k_wgrad_gemm16 (16x16x4 MFMA tiles); a call takes it if it can take the lean loader
+        if (use16 && Cout != 16) return p;
+        const int Ng = KH * KW * Cin + (has_bias ? 1 : 0);
+        p.tm = Cout <= 32 ? 32 : 64; p.tn = Cout <= 32 ? 128 : 64;    // 32x128 tiles for the thin layers
+        if (use16) { p.tm = 16; p.tn = 160; }
+        p.Mpad = (Cout + p.tm - 1) / p.tm * p.tm; p.Npad = (Ng + p.tn - 1) / p.tn * p.tn;
+        const int64_t P = (int64_t)B * Ho * Wo;
+        const int64_t tiles = (int64_t)(p.Mpad / p.tm) * (p.Npad / p.tn);
+        const int target = use16 ? wg_target * 3 / 4 : wg_target;     // measured: 768 slices suit the 16-channel kernel (94 vs 110 us)
+        int64_t S = (target + tiles - 1) / tiles;            // pixel slices: ~target workgroups in total
+        const int64_t maxS = (P + 255) / 256;                // at least 256 pixels per slice
+        if (S > maxS) S = maxS;
+        if (S < 1) S = 1;
+        p.S = S;
+    }
+    p.open = true;
     return p;
+}
+
+// the largest slab set among the open paths
+static int64_t wgrad_workspace_floats(const ConvGeom& g, int has_bias, bool tuned, int wg_target) {
+    int64_t n = 0;
+    for (int i = 0; i < WP_COUNT; ++i) {
+        const WgradPlan p = wgrad_plan((WgradPath)i, g, has_bias, tuned, wg_target);
+        if (p.open && p.S * p.Mpad * p.Npad > n) n = p.S * p.Mpad * p.Npad;
+    }
+    return n;
+}
+
+// the path a backward-weight call takes, planned: the first open path whose other conditions the call meets (has_src1: a second source is given)
+static WgradPlan wgrad_choose(const ConvGeom& g, int has_bias, bool has_src1, bool tuned, int wg_target) {
+    const int Hs = g.Hs, Ws = g.Ws, Cin = g.Cin, Cout = g.Cout, Ho = g.Ho, Wo = g.Wo, stride = g.stride, pad = g.pad, pad_mode = g.pad_mode, C1 = g.C1, up = g.up;
+    const int vec = (Cin % 4 == 0 && C1 % 4 == 0) ? 4 : 1;
+    const int64_t P = (int64_t)g.B * Ho * Wo;
+    auto plan = [&](WgradPath w) { return wgrad_plan(w, g, has_bias, tuned, wg_target); };
+    // lean VEC-4 kernel: 32 pixels per chunk; needs Cout % 4 == 0, 32-bit offsets and image rows of at least 8 pixels
+    const bool lean = vec == 4 && Cout % 4 == 0 && Wo >= 8 && (int64_t)g.B * Hs * Ws * Cin * 4 < (1ll << 31) && P * Cout * 4 < (1ll << 31) && P < (1ll << 24);
+    WgradPlan p{WP_GEMM};
+    if (stride == 2 && pad == 3 && pad_mode == 0 && C1 == Cin && up == 1 && !has_bias && Ho == (Hs + 6 - 7) / 2 + 1 && Wo == (Ws + 6 - 7) / 2 + 1 &&
+        (p = plan(WP_STEM)).open)                            // the RGB stem
+        return p;
+    if (lean && stride == 1 && pad == 1 && pad_mode == 1 && C1 % 16 == 0 && Ho == Hs && Wo == Ws && (C1 == Cin || has_src1) && Hs % up == 0 && Ws % up == 0 &&
+        (p = plan(WP_THIN)).open)                            // the thin 3x3 layers of the decoder's last two levels (reflection pad, 16 / 32 output channels)
+        return p;
+    // the 32-channel-tile 3x3 layers (encoder stages, decoder upconv(k, 0) and the concat layers whose two sources are multiples of 32 wide):
+    // tap-reuse patch kernel.  OPT-IN (E2E_WGRAD_TAPS=1, read per call): measured at parity with or behind the implicit-GEMM
+    // kernels on every layer (profiles/r04_wgrad_taps.txt: 52.7 vs 48.4 us on layer1 at its best decomposition) -- it is kept, tested, as
+    // the record of that experiment and as a starting point, not as the product's path
+    if (vec == 4 && stride == 1 && pad == 1 && Ho == Hs && Wo == Ws && (up == 1 || up == 2) && Hs % up == 0 && Ws % up == 0 && (C1 == Cin || (has_src1 && C1 % 32 == 0)) &&
+        getenv("E2E_WGRAD_TAPS") != nullptr && getenv("E2E_WGRAD_TAPS")[0] == '1' && (p = plan(WP_TAPS)).open)
+        return p;
+    return lean && (p = plan(WP_GEMM16)).open ? p : plan(lean ? WP_GEMM_LEAN : WP_GEMM);
 }
 
 int64_t e2e_conv2d_wgrad_workspace_floats(int B, int Ho, int Wo, int Cin, int Cout, int KH, int KW, int has_bias) {
-    const WgradPlan p = wgrad_plan(B, Ho, Wo, Cin, Cout, KH, KW, has_bias, false);
-    int64_t n = p.S * (int64_t)p.Mpad * p.Npad;
-    if (tap_wgrad_shape_ok(Cin, Cout, KH, KW)) {
-        const TapWgradPlan t = tap_wgrad_plan(B, Ho, Wo, Cin, Cout, has_bias);
-        if ((int64_t)t.S * Cout * t.Npad > n) n = (int64_t)t.S * Cout * t.Npad;
-    }
-    if (Cout == 16) {                                                  // the 16-channel kernel is chosen at launch (it needs the lean loader)
-        const WgradPlan q = wgrad_plan(B, Ho, Wo, Cin, Cout, KH, KW, has_bias, true);
-        if (q.S * (int64_t)q.Mpad * q.Npad > n) n = q.S * (int64_t)q.Mpad * q.Npad;
-    }
-    if (thin_wgrad_ok(Cin, Cout, KH, KW)) {
-        const ThinWgradPlan t = thin_wgrad_plan(B, Ho, Wo, Cin, has_bias);
-        if (t.S * Cout * t.npad > n) n = t.S * Cout * t.npad;
-    }
-    if (KH == 7 && KW == 7 && Cin == 3 && Cout == 64) {                 // k_wgrad7x7_stem: one slab [64][148] per pair of 4 x 32 tiles
-        const int64_t S = (int64_t)B * ((Ho + 3) / 4) * (((Wo + 31) / 32 + 1) / 2);
-        if (S * 64 * 148 > n) n = S * 64 * 148;
-    }
-    return n;
+    GEOM_WGRAD_QUERY(g);
+    return wgrad_workspace_floats(g, has_bias, false, WGRAD_TARGET);
 }
 
 // where a backward-weight call's result goes: the slab reduction that ends every path is launched, or -- defer -- described for
@@ -3229,101 +3197,72 @@ enum WgradKernel { WK_DONE, WK_GEMM16, WK_GEMM4_32, WK_GEMM4_64, WK_GEMM_32, WK_
 struct WgradLaunch { WgradKernel k; dim3 g; int Sz; };
 
 // backward-weight up to its GEMM: checks the arguments, serves the stem / thin / tap layers with their patch kernels and reductions
-// (L.k = WK_DONE), or fills the GEMM's WgradArgs and decomposition.  Shared by bwd_weight_impl and the paired backward.
-static int wgrad_setup(const float* dz, const float* src0, const float* src1, int C1, int up, float* workspace, int B, int Hs, int Ws, int Cin,
-                       int Cout, int Ho, int Wo, int KH, int KW, int stride, int pad, int pad_mode, float in_sub, float in_mul, int wg_target,
-                       const WgradOut& o, hipStream_t st, WgradArgs& a, WgradLaunch& L) {
+// (L.k = WK_DONE), or fills the GEMM's WgradArgs and decomposition (wg_target == 0: an untuned call).  Shared by bwd_weight_impl and the paired backward.
+static int wgrad_setup(const WgradIn& in, const ConvGeom& g, int wg_target, const WgradOut& o, hipStream_t st, WgradArgs& a, WgradLaunch& L) {
+    const int B = g.B, Cin = g.Cin, Cout = g.Cout, Ho = g.Ho, Wo = g.Wo;
     const bool tuned = wg_target != 0;
     if (!tuned) wg_target = WGRAD_TARGET;
     L = WgradLaunch{WK_DONE, dim3(1), 0};
-    E2E_REQUIRE(dz && src0 && o.dw && workspace && B > 0 && Cin > 0 && Cout > 0, E2E_ERR_ARG, "e2e_conv2d_bwd_weight: bad argument");
-    const int vec = (Cin % 4 == 0 && C1 % 4 == 0) ? 4 : 1;
-    E2E_REQUIRE(vec == 4 || (C1 == Cin && up == 1 && pad_mode == 0), E2E_ERR_ARG, "e2e_conv2d_bwd_weight: scalar path takes one full-resolution zero-padded source");
+    E2E_REQUIRE(in.dz && in.src0 && o.dw && in.workspace && B > 0 && Cin > 0 && Cout > 0, E2E_ERR_ARG, "e2e_conv2d_bwd_weight: bad argument");
+    const int vec = (Cin % 4 == 0 && g.C1 % 4 == 0) ? 4 : 1;
+    E2E_REQUIRE(vec == 4 || (g.C1 == Cin && g.up == 1 && g.pad_mode == 0), E2E_ERR_ARG, "e2e_conv2d_bwd_weight: scalar path takes one full-resolution zero-padded source");
     a = WgradArgs{};
-    a.dz = dz; a.src0 = src0; a.src1 = src1; a.slabs = workspace;
-    a.B = B; a.Hs = Hs; a.Ws = Ws; a.Cin = Cin; a.C1 = C1; a.up = up; a.Ho = Ho; a.Wo = Wo; a.Cout = Cout;
-    a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad; a.pad_mode = pad_mode; a.has_bias = o.dbias ? 1 : 0;
-    a.Ngemm = KH * KW * Cin + a.has_bias;
-    const int64_t P = (int64_t)B * Ho * Wo;
-    // lean VEC-4 kernel: 32 pixels per chunk; needs Cout % 4 == 0, 32-bit offsets and image rows of at least 8 pixels
-    const bool lean = vec == 4 && Cout % 4 == 0 && Wo >= 8 && (int64_t)B * Hs * Ws * Cin * 4 < (1ll << 31) && P * Cout * 4 < (1ll << 31) && P < (1ll << 24);
-    // the RGB stem: patch kernel + the common slab reduction (untuned calls only: a tuned call runs the implicit GEMM, and its workspace query
-    // does not cover the stem's slabs)
-    if (!tuned && KH == 7 && KW == 7 && stride == 2 && pad == 3 && pad_mode == 0 && Cin == 3 && Cout == 64 && C1 == Cin && up == 1 && !o.dbias &&
-        Ho == (Hs + 6 - 7) / 2 + 1 && Wo == (Ws + 6 - 7) / 2 + 1) {
-        const int nxg = ((Wo + 31) / 32 + 1) / 2, ny = (Ho + 3) / 4;
-        StemWgradArgs ta{dz, src0, workspace, B, Hs, Ws, Ho, Wo, 2, nxg, in_sub, in_mul};
-        hipLaunchKernelGGL(k_wgrad7x7_stem, dim3(nxg, ny, B), dim3(256), 0, st, ta);
-        wgrad_reduce(a, o, B * ny * nxg, 64, 148, 8, st);
-        return E2E_OK;
-    }
-    // the thin 3x3 layers of the decoder's last two levels (reflection pad, 16 / 32 output channels): patch kernel + the common slab reduction
-    if (!tuned && lean && thin_wgrad_ok(Cin, Cout, KH, KW) && stride == 1 && pad == 1 && pad_mode == 1 && C1 % 16 == 0 && Ho == Hs && Wo == Ws &&
-        (C1 == Cin || src1) && Hs % up == 0 && Ws % up == 0) {
-        const ThinWgradPlan t = thin_wgrad_plan(B, Ho, Wo, Cin, a.has_bias);
-        ThinWgradArgs ta{dz, src0, src1, workspace, B, Ho, Wo, Cin, C1, up, t.npad, a.has_bias, t.tiles_x, t.nxg};
-        const dim3 tg((unsigned)t.nxg, (unsigned)t.ny, (unsigned)(B * (Cin / 16)));
+    a.dz = in.dz; a.src0 = in.src0; a.src1 = in.src1; a.slabs = in.workspace;
+    a.B = B; a.Hs = g.Hs; a.Ws = g.Ws; a.Cin = Cin; a.C1 = g.C1; a.up = g.up; a.Ho = Ho; a.Wo = Wo; a.Cout = Cout;
+    a.KH = g.KH; a.KW = g.KW; a.stride = g.stride; a.pad = g.pad; a.pad_mode = g.pad_mode; a.has_bias = o.dbias ? 1 : 0;
+    a.Ngemm = g.KH * g.KW * Cin + a.has_bias;
+    const WgradPlan p = wgrad_choose(g, a.has_bias, in.src1 != nullptr, tuned, wg_target);
+    const int S = (int)p.S;
+    if (p.path == WP_STEM) {                                 // the patch kernels: kernel + the common slab reduction
+        StemWgradArgs ta{in.dz, in.src0, in.workspace, B, g.Hs, g.Ws, Ho, Wo, 2, p.nxg, g.in_sub, g.in_mul};
+        hipLaunchKernelGGL(k_wgrad7x7_stem, dim3(p.nxg, p.ny, B), dim3(256), 0, st, ta);
+    } else if (p.path == WP_THIN) {
+        ThinWgradArgs ta{in.dz, in.src0, in.src1, in.workspace, B, Ho, Wo, Cin, g.C1, g.up, p.Npad, a.has_bias, p.tiles_x, p.nxg};
+        const dim3 tg((unsigned)p.nxg, (unsigned)p.ny, (unsigned)(B * (Cin / 16)));
         if (Cout == 32) hipLaunchKernelGGL((k_wgrad3x3_thin<2>), tg, dim3(256), 0, st, ta);
         else hipLaunchKernelGGL((k_wgrad3x3_thin<1>), tg, dim3(256), 0, st, ta);
-        wgrad_reduce(a, o, (int)t.S, Cout, t.npad, 8, st);
-        return E2E_OK;
-    }
-    // the 32-channel-tile 3x3 layers (encoder stages, decoder upconv(k, 0) and the concat layers whose two sources are multiples of 32 wide):
-    // tap-reuse patch kernel + the common slab reduction.  OPT-IN (E2E_WGRAD_TAPS=1): measured at parity with or behind the implicit-GEMM
-    // kernels on every layer (profiles/r04_wgrad_taps.txt: 52.7 vs 48.4 us on layer1 at its best decomposition) -- it is kept, tested, as
-    // the record of that experiment and as a starting point, not as the product's path
-    if (!tuned && vec == 4 && tap_wgrad_shape_ok(Cin, Cout, KH, KW) && stride == 1 && pad == 1 && Ho == Hs && Wo == Ws && (up == 1 || up == 2) &&
-        Hs % up == 0 && Ws % up == 0 && (C1 == Cin || (src1 && C1 % 32 == 0)) && getenv("E2E_WGRAD_TAPS") != nullptr && getenv("E2E_WGRAD_TAPS")[0] == '1') {
-        const TapWgradPlan t = tap_wgrad_plan(B, Ho, Wo, Cin, Cout, a.has_bias);
-        TapWgradArgs ta{dz, src0, src1, workspace, B, Ho, Wo, Cin, C1, up, Cout, pad_mode == 1 ? 1 : 0, a.has_bias, Cout, t.Npad, t.ptx, t.pty, t.nchunks, t.cps};
-        const dim3 tg((unsigned)(Cin / 32), (unsigned)(Cout / 32), (unsigned)t.S);
+    } else if (p.path == WP_TAPS) {
+        TapWgradArgs ta{in.dz, in.src0, in.src1, in.workspace, B, Ho, Wo, Cin, g.C1, g.up, Cout, g.pad_mode == 1 ? 1 : 0, a.has_bias,
+                        p.Mpad, p.Npad, p.ptx, p.pty, p.nchunks, p.cps};
+        const dim3 tg((unsigned)(Cin / 32), (unsigned)(Cout / 32), (unsigned)S);
         if (a.has_bias) hipLaunchKernelGGL(k_wgrad3x3_taps<true>, tg, dim3(TAP_NT), 0, st, ta);
         else hipLaunchKernelGGL(k_wgrad3x3_taps<false>, tg, dim3(TAP_NT), 0, st, ta);
-        wgrad_reduce(a, o, t.S, Cout, t.Npad, t.S >= 8 ? 8 : 2, st);
+    }
+    if (p.path == WP_STEM || p.path == WP_THIN || p.path == WP_TAPS) {
+        wgrad_reduce(a, o, S, p.Mpad, p.Npad, (p.path == WP_TAPS && S < 8) ? 2 : 8, st);
         return E2E_OK;
     }
-    const bool use16 = lean && Cout == 16;
-    const WgradPlan wp = wgrad_plan(B, Ho, Wo, Cin, Cout, KH, KW, a.has_bias, use16, wg_target);
-    const int tm = wp.tm, tn = wp.tn;
-    a.Mpad = wp.Mpad; a.Npad = wp.Npad;
-    a.in_sub = in_sub; a.in_mul = in_mul; a.vec = vec;
-    const int64_t S = wp.S;
+    const bool use16 = p.path == WP_GEMM16, lean = p.path != WP_GEMM;
+    a.Mpad = p.Mpad; a.Npad = p.Npad;
+    a.in_sub = g.in_sub; a.in_mul = g.in_mul; a.vec = vec;
+    const int64_t P = (int64_t)B * Ho * Wo;
     const int cbp = lean ? 32 : CBK;
-    a.pix_per_slice = ((P + S - 1) / S + cbp - 1) / cbp * cbp;
+    a.pix_per_slice = ((P + p.S - 1) / p.S + cbp - 1) / cbp * cbp;
     L.Sz = (int)((P + a.pix_per_slice - 1) / a.pix_per_slice);
-    L.g = dim3((unsigned)(a.Npad / tn), (unsigned)(a.Mpad / tm), (unsigned)L.Sz);
-    L.k = use16 ? WK_GEMM16 : lean ? (tm == 32 ? WK_GEMM4_32 : WK_GEMM4_64) : (tm == 32 ? WK_GEMM_32 : WK_GEMM_64);
+    L.g = dim3((unsigned)(a.Npad / p.tn), (unsigned)(a.Mpad / p.tm), (unsigned)L.Sz);
+    L.k = use16 ? WK_GEMM16 : lean ? (p.tm == 32 ? WK_GEMM4_32 : WK_GEMM4_64) : (p.tm == 32 ? WK_GEMM_32 : WK_GEMM_64);
     return E2E_OK;
 }
 
 static void wgrad_launch_gemm(const WgradArgs& a, const WgradLaunch& L, hipStream_t st) {
     const dim3 g = L.g;
     const bool two = a.src1 != nullptr;
-    if (L.k == WK_GEMM16) {
-        hipLaunchKernelGGL((k_wgrad_gemm16<10, 32>), g, dim3(256), 0, st, a);
-    } else if (L.k == WK_GEMM4_32) {
-        if (two) hipLaunchKernelGGL((k_wgrad_gemm4<1, 4, 32, true>), g, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((k_wgrad_gemm4<1, 4, 32, false>), g, dim3(256), 0, st, a);
-    } else if (L.k == WK_GEMM4_64) {
-        if (two) hipLaunchKernelGGL((k_wgrad_gemm4<2, 2, 32, true>), g, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((k_wgrad_gemm4<2, 2, 32, false>), g, dim3(256), 0, st, a);
-    } else if (L.k == WK_GEMM_32) {
-        if (a.vec == 4) hipLaunchKernelGGL((k_wgrad_gemm<1, 4, 4>), g, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((k_wgrad_gemm<1, 4, 1>), g, dim3(256), 0, st, a);
-    } else if (L.k == WK_GEMM_64) {
-        if (a.vec == 4) hipLaunchKernelGGL((k_wgrad_gemm<2, 2, 4>), g, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((k_wgrad_gemm<2, 2, 1>), g, dim3(256), 0, st, a);
-    }
+    if (L.k == WK_GEMM16) hipLaunchKernelGGL((k_wgrad_gemm16<10, 32>), g, dim3(256), 0, st, a);
+    else if (L.k == WK_GEMM4_32 && two) hipLaunchKernelGGL((k_wgrad_gemm4<1, 4, 32, true>), g, dim3(256), 0, st, a);
+    else if (L.k == WK_GEMM4_32) hipLaunchKernelGGL((k_wgrad_gemm4<1, 4, 32, false>), g, dim3(256), 0, st, a);
+    else if (L.k == WK_GEMM4_64 && two) hipLaunchKernelGGL((k_wgrad_gemm4<2, 2, 32, true>), g, dim3(256), 0, st, a);
+    else if (L.k == WK_GEMM4_64) hipLaunchKernelGGL((k_wgrad_gemm4<2, 2, 32, false>), g, dim3(256), 0, st, a);
+    else if (L.k == WK_GEMM_32 && a.vec == 4) hipLaunchKernelGGL((k_wgrad_gemm<1, 4, 4>), g, dim3(256), 0, st, a);
+    else if (L.k == WK_GEMM_32) hipLaunchKernelGGL((k_wgrad_gemm<1, 4, 1>), g, dim3(256), 0, st, a);
+    else if (L.k == WK_GEMM_64 && a.vec == 4) hipLaunchKernelGGL((k_wgrad_gemm<2, 2, 4>), g, dim3(256), 0, st, a);
+    else if (L.k == WK_GEMM_64) hipLaunchKernelGGL((k_wgrad_gemm<2, 2, 1>), g, dim3(256), 0, st, a);
 }
 
-static int bwd_weight_impl(const float* dz, const float* src0, const float* src1, int C1, int up, float* dw, float* dbias, float* workspace, int B,
-                           int Hs, int Ws, int Cin, int Cout, int Ho, int Wo, int KH, int KW, int stride, int pad, int pad_mode, int accumulate,
-                           float in_sub, float in_mul, const float* out_scale, void* stream, int wg_target = 0, e2e_wgrad_reduce_desc* defer = nullptr) {
+static int bwd_weight_impl(const WgradIn& in, const ConvGeom& g, const WgradOut& o, void* stream, int wg_target = 0) {
     const hipStream_t st = (hipStream_t)stream;
-    const WgradOut o{dw, dbias, out_scale, accumulate, defer};
     WgradArgs a;
     WgradLaunch L;
-    const int rc = wgrad_setup(dz, src0, src1, C1, up, workspace, B, Hs, Ws, Cin, Cout, Ho, Wo, KH, KW, stride, pad, pad_mode, in_sub, in_mul, wg_target, o, st, a, L);
+    const int rc = wgrad_setup(in, g, wg_target, o, st, a, L);
     if (rc != E2E_OK) return rc;
     if (L.k != WK_DONE) {
         wgrad_launch_gemm(a, L, st);
@@ -3336,15 +3275,15 @@ static int bwd_weight_impl(const float* dz, const float* src0, const float* src1
 int e2e_conv2d_bwd_weight(const float* dz, const float* src0, const float* src1, int C1, int up, float* dw, float* dbias,
                           float* workspace, int B, int Hs, int Ws, int Cin, int Cout, int Ho, int Wo, int KH, int KW, int stride,
                           int pad, int pad_mode, int accumulate, float in_sub, float in_mul, void* stream) {
-    return bwd_weight_impl(dz, src0, src1, C1, up, dw, dbias, workspace, B, Hs, Ws, Cin, Cout, Ho, Wo, KH, KW, stride, pad, pad_mode, accumulate,
-                           in_sub, in_mul, nullptr, stream);
+    GEOM_BWD_WEIGHT(g);
+    return bwd_weight_impl(WgradIn{dz, src0, src1, workspace}, g, WgradOut{dw, dbias, nullptr, accumulate, nullptr}, stream);
 }
 
 int e2e_conv2d_bwd_weight_scaled(const float* da, const float* out_scale, const float* src0, const float* src1, int C1, int up, float* dw,
                                  float* dbias, float* workspace, int B, int Hs, int Ws, int Cin, int Cout, int Ho, int Wo, int KH, int KW,
                                  int stride, int pad, int pad_mode, int accumulate, float in_sub, float in_mul, void* stream) {
-    return bwd_weight_impl(da, src0, src1, C1, up, dw, dbias, workspace, B, Hs, Ws, Cin, Cout, Ho, Wo, KH, KW, stride, pad, pad_mode, accumulate,
-                           in_sub, in_mul, out_scale, stream);
+    GEOM_BWD_WEIGHT(g);
+    return bwd_weight_impl(WgradIn{da, src0, src1, workspace}, g, WgradOut{dw, dbias, out_scale, accumulate, nullptr}, stream);
 }
 
 /* e2e_conv2d_bwd_weight_scaled WITHOUT its final launch: the partial slabs stay in `workspace` (which must stay untouched until the reduction
@@ -3356,8 +3295,8 @@ int e2e_conv2d_bwd_weight_scaled_deferred(const float* da, const float* out_scal
                                           int stride, int pad, int pad_mode, int accumulate, float in_sub, float in_mul,
                                           e2e_wgrad_reduce_desc* desc_out, void* stream) {
     E2E_REQUIRE(desc_out, E2E_ERR_ARG, "e2e_conv2d_bwd_weight_scaled_deferred: desc_out is NULL");
-    return bwd_weight_impl(da, src0, src1, C1, up, dw, dbias, workspace, B, Hs, Ws, Cin, Cout, Ho, Wo, KH, KW, stride, pad, pad_mode, accumulate,
-                           in_sub, in_mul, out_scale, stream, 0, desc_out);
+    GEOM_BWD_WEIGHT(g);
+    return bwd_weight_impl(WgradIn{da, src0, src1, workspace}, g, WgradOut{dw, dbias, out_scale, accumulate, desc_out}, stream);
 }
 
 /* A layer's backward-data (e2e_conv2d_bwd_data_fused; accumulate = 0, x_in = pre_add = NULL, in_act = 0 is e2e_conv2d_bwd_data) and its
@@ -3374,13 +3313,13 @@ int e2e_conv2d_bwd_pair_deferred(const float* da, const float* w_bwd, int ld_bwd
     const hipStream_t st = (hipStream_t)stream;
     ConvArgs ad;
     bool data_done;
-    int rc = bwd_data_setup(da, w_bwd, ld_bwd, dxp, B, Hs, Ws, Cin, Cout, Ho, Wo, KH, KW, stride, pad, pad_mode, accumulate, x_in, in_act, pre_add,
-                            GemmCfg{0, 0, 0}, st, ad, data_done);
+    GEOM_BWD_WEIGHT(g);
+    int rc = bwd_data_setup(BwdDataOps{da, w_bwd, ld_bwd, dxp, accumulate, x_in, in_act, pre_add}, g, GemmCfg{0, 0, 0}, st, ad, data_done);
     if (rc != E2E_OK) return rc;
     const WgradOut o{dw, dbias, out_scale, accumulate_w, desc_out};
     WgradArgs aw;
     WgradLaunch lw;
-    rc = wgrad_setup(da, src0, src1, C1, up, workspace_w, B, Hs, Ws, Cin, Cout, Ho, Wo, KH, KW, stride, pad, pad_mode, in_sub, in_mul, 0, o, st, aw, lw);
+    rc = wgrad_setup(WgradIn{da, src0, src1, workspace_w}, g, 0, o, st, aw, lw);
     if (rc != E2E_OK) return rc;
     GemmLaunch pd{};
     if (!data_done) pd = plan_gemm<true>(ad, 4, workspace, GemmCfg{0, 0, 0});
@@ -3393,14 +3332,14 @@ int e2e_conv2d_bwd_pair_deferred(const float* da, const float* w_bwd, int ld_bwd
         const unsigned nd = pg.dgx * pg.dgy * pg.dgz, nw = pg.wgx * pg.wgy * pg.wgz;
         pg.wgrad_first = wgrad_first ? 1 : 0;
         pg.first = ((wgrad_first ? nw : nd) + 7u) / 8u * 8u;
-        const dim3 g(pg.first + (wgrad_first ? nd : nw));
+        const dim3 grid(pg.first + (wgrad_first ? nd : nw));
         const bool two = aw.src1 != nullptr;
         if (d14) {
-            if (two) hipLaunchKernelGGL((k_conv_bwd_pair<1, 4, true>), g, dim3(256), 0, st, ad, aw, pg);
-            else hipLaunchKernelGGL((k_conv_bwd_pair<1, 4, false>), g, dim3(256), 0, st, ad, aw, pg);
+            if (two) hipLaunchKernelGGL((k_conv_bwd_pair<1, 4, true>), grid, dim3(256), 0, st, ad, aw, pg);
+            else hipLaunchKernelGGL((k_conv_bwd_pair<1, 4, false>), grid, dim3(256), 0, st, ad, aw, pg);
         } else {
-            if (two) hipLaunchKernelGGL((k_conv_bwd_pair<2, 2, true>), g, dim3(256), 0, st, ad, aw, pg);
-            else hipLaunchKernelGGL((k_conv_bwd_pair<2, 2, false>), g, dim3(256), 0, st, ad, aw, pg);
+            if (two) hipLaunchKernelGGL((k_conv_bwd_pair<2, 2, true>), grid, dim3(256), 0, st, ad, aw, pg);
+            else hipLaunchKernelGGL((k_conv_bwd_pair<2, 2, false>), grid, dim3(256), 0, st, ad, aw, pg);
         }
     } else {
         if (!data_done) launch_gemm_main<true>(ad, pd, workspace, st);
@@ -3440,26 +3379,13 @@ int e2e_conv2d_bwd_weight_scaled_tuned(const float* da, const float* out_scale, 
                                        float* dbias, float* workspace, int B, int Hs, int Ws, int Cin, int Cout, int Ho, int Wo, int KH, int KW,
                                        int stride, int pad, int pad_mode, int accumulate, float in_sub, float in_mul, int target_workgroups, void* stream) {
     E2E_REQUIRE(target_workgroups >= 64 && target_workgroups <= 8192, E2E_ERR_ARG, "e2e_conv2d_bwd_weight_scaled_tuned: 64 .. 8192 workgroups");
-    return bwd_weight_impl(da, src0, src1, C1, up, dw, dbias, workspace, B, Hs, Ws, Cin, Cout, Ho, Wo, KH, KW, stride, pad, pad_mode, accumulate,
-                           in_sub, in_mul, out_scale, stream, target_workgroups);
+    GEOM_BWD_WEIGHT(g);
+    return bwd_weight_impl(WgradIn{da, src0, src1, workspace}, g, WgradOut{dw, dbias, out_scale, accumulate, nullptr}, stream, target_workgroups);
 }
 
 int64_t e2e_conv2d_wgrad_tuned_workspace_floats(int B, int Ho, int Wo, int Cin, int Cout, int KH, int KW, int has_bias, int target_workgroups) {
-    int64_t n = 0;
-    for (int u = 0; u < 2; ++u) {
-        if (u == 1 && Cout != 16) break;
-        const WgradPlan p = wgrad_plan(B, Ho, Wo, Cin, Cout, KH, KW, has_bias, u == 1, target_workgroups);
-        if (p.S * (int64_t)p.Mpad * p.Npad > n) n = p.S * (int64_t)p.Mpad * p.Npad;
-    }
-    return n;
+    GEOM_WGRAD_QUERY(g);
+    return wgrad_workspace_floats(g, has_bias, true, target_workgroups);
 }
-
-#ifdef E2E_CONV_STAMPS
-int e2e_debug_read_stamps(unsigned long long* host, int n) {
-    if (n < -(1 << 20)) return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_phases), (size_t)(-n - (1 << 20)) * 8);   // the K-loop phase clocks
-    if (n < 0) return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_stamps2), (size_t)(-n) * 8);      // n < 0: the prologue stamps
-    return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_stamps), (size_t)n * 8);
-}
-#endif
 
 }  // extern "C"

@@ -9,7 +9,6 @@
 #   pmc_traffic.{txt,json}      tools/bench_pmc.sh (FETCH_SIZE / WRITE_SIZE passes, stamped with the source hash)
 #   gemm_tune.txt               tools/gemm_tune.py both
 #   pass_profile.txt            tools/pass_profile.py: wall time per keyframe over a whole pass + the map-size dependent entry points
-#   conv_stamps.txt             scratch/conv_stamps.py on the -DE2E_CONV_STAMPS build (if scratch/_stamped/ holds one)
 #   pytest_gpu.log              python3 -m pytest tests -m gpu -q
 # usage: tools/evidence.sh <tag> [bench|suite]   -- two parts, each within one gpurun call (20 minutes): "bench" = PMC traffic, the bench lines and
 # the rocprofv3 kernel statistics; "suite" = GEMM table, pass profile, GPU test log.  Default: both.
@@ -62,7 +61,6 @@ PY
 echo "fills done" >> $OUT/progress.txt
 timeout -k 10 500 python3 tools/gemm_tune.py both > $OUT/gemm_tune.txt 2>&1; echo "tune $?" >> $OUT/progress.txt
 timeout -k 10 300 python3 tools/pass_profile.py > $OUT/pass_profile.txt 2> $OUT/pass_profile.err; echo "pass profile $?" >> $OUT/progress.txt
-if [ -f scratch/_stamped/libe2eslam_hip_stamped.so ]; then python3 scratch/conv_stamps.py 2>&1 | grep -v amdgpu.ids > $OUT/conv_stamps.txt; echo "stamps $?" >> $OUT/progress.txt; fi
 timeout -k 10 600 python3 -m pytest tests -m gpu -q --durations=5 > $OUT/pytest_gpu.log 2>&1; echo "pytest $?" >> $OUT/progress.txt
 fi
 cat $OUT/progress.txt; head -c 300 $OUT/bench_default.json; echo; head -c 300 $OUT/bench_fullpass.json; echo; head -c 300 $OUT/bench_gradicp.json
