@@ -2255,58 +2255,142 @@ __global__ __launch_bounds__(256) void k_weight_layouts(const float* __restrict_
     }
 }
 
-// all layers of a network in ONE launch (after an optimiser step every layout is stale): blockIdx.y = layer, descriptor
-// table of 10 int64 per layer on the device: {w, w_fwd, w_bwd, Cout, Cin, KH, KW, ld_fwd, ld_bwd, bwd_scale (float* or 0)}
-__global__ __launch_bounds__(256) void k_weight_layouts_batched(const long long* __restrict__ desc) {
-    const long long* d = desc + (int64_t)blockIdx.y * 10;
-    const float* __restrict__ w = (const float*)d[0];
-    float* __restrict__ wf = (float*)d[1];
-    float* __restrict__ wb = (float*)d[2];
-    const int Cout = (int)d[3], Cin = (int)d[4], KH = (int)d[5], KW = (int)d[6], ldf = (int)d[7], ldb = (int)d[8];
-    // optional per-output-channel factor folded into the BACKWARD layout only (a folded BatchNorm scale: dX = (dA * scale) W^T is
-    // computed as dA (scale W)^T, so the backward GEMM reads dA directly -- e2ehip.netplan)
-    const float* __restrict__ bsc = (const float*)d[9];
-    const int T = KH * KW;
-    constexpr int TMAX = 9, TS = 32;
-    __shared__ float tile[TMAX][TS + 1][TS + 1];           // tap stride 33 * 33 = 1 mod 32 banks: the staging store walks taps fastest (PMC: 54 % conflicts with [TS][TS + 1])
-    if (T > TMAX) {                                           // the 7x7 stem (Cin = 3): element-wise, it is tiny
-        const int64_t total = (int64_t)Cout * Cin * T;
-        for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-            const int tap = (int)(i % T);
-            const int64_t r = i / T;
-            const int ci = (int)(r % Cin), co = (int)(r / Cin);
-            const float v = w[i];
-            if (wf) wf[((int64_t)tap * Cin + ci) * ldf + co] = v;
-            if (wb) wb[((int64_t)tap * Cout + co) * ldb + ci] = bsc ? v * bsc[co] : v;
+// all layers of a network in ONE launch (after an optimiser step every layout is stale).  Descriptor table of 10 int64 per layer on
+// the device: {w, w_fwd, w_bwd, Cout, Cin, KH, KW, ld_fwd, ld_bwd, bwd_scale (float* or 0)}.  bwd_scale: optional per-output-channel
+// factor folded into the BACKWARD layout only (a folded BatchNorm scale: dX = (dA * scale) W^T is computed as dA (scale W)^T, so the
+// backward GEMM reads dA directly -- e2ehip.netplan).
+// The work is ONE flat list over (layer, cout tile, cin tile) -- every workgroup finds its tiles through a prefix over the layers'
+// tile counts that it builds in LDS -- so a 64 x 64 layer costs 4 workgroups and a 512 x 512 layer is spread over 256 of them.
+// A tile is 32 (cout) x 32 (cin) x T floats for T = 1 and T = 9 (compile-time: no division by a run-time T); any other filter (the
+// 7x7 stem, Cin = 3) is copied element by element in items of WL_ELEMS.
+constexpr int WL_TS = 32, WL_ELEMS = 1024, WL_MAXL = 256;
+
+// LDS tile [co][ci * T + tap], row stride R = 32 T + 1 floats = 1 mod 32 banks.  Bank arithmetic (32 lanes per LDS pass):
+//   staging: a lane holds the quad at floats 4x .. 4x + 3 of a row (16-byte global load) and stores its element (s + x / 8) % 4 in
+//     pass s: lanes 8j .. 8j + 7 hit banks 4 (x % 8) + (s + j) % 4 -- all 32 distinct;
+//   w_fwd read: lane = (cq = l % 8, ci = 4 g + l / 8) reads rows 4 cq + k at column ci T + tap: bank = 4 cq + T (l / 8) + const,
+//     T = 9 or 1 is odd, so T (l / 8) runs through the residues mod 4 -- all 32 distinct;
+//   w_bwd read: lane = (iq = l % 8, co = 4 g + l / 8) reads row co at column (4 iq + k) T + tap: bank = 4 T iq + l / 8 + const and
+//     4 T = 4 mod 32 -- all 32 distinct.
+template <int T>
+__device__ __forceinline__ void weight_layout_tile(const float* __restrict__ w, float* __restrict__ wf, float* __restrict__ wb, const float* __restrict__ bsc,
+                                                   int Cout, int Cin, int ldf, int ldb, int co0, int ci0, float* tile) {
+    constexpr int R = WL_TS * T + 1;
+    const int nci = min(WL_TS, Cin - ci0), nco = min(WL_TS, Cout - co0);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int row = nci * T;                                  // contiguous floats of one cout row inside the tile
+    if ((Cin & 3) == 0 && ((uintptr_t)w & 15) == 0) {        // every row of the tile starts on 16 bytes and is whole quads
+        const int rot = (lane >> 3) & 3;
+        for (int co_l = wave; co_l < nco; co_l += 4) {
+            const f4v* src = (const f4v*)(w + ((int64_t)(co0 + co_l) * Cin + ci0) * T);
+            float* dst = tile + co_l * R;
+            for (int x = lane; x < row / 4; x += 64) {
+                const f4v v = src[x];
+#pragma unroll
+                for (int s = 0; s < 4; ++s) {
+                    const int k = (s + rot) & 3;
+                    dst[4 * x + k] = k == 0 ? v[0] : k == 1 ? v[1] : k == 2 ? v[2] : v[3];
+                }
+            }
         }
-        return;
+    } else {
+        for (int co_l = wave; co_l < nco; co_l += 4) {
+            const float* src = w + ((int64_t)(co0 + co_l) * Cin + ci0) * T;
+            float* dst = tile + co_l * R;
+            for (int x = lane; x < row; x += 64) dst[x] = src[x];
+        }
     }
-    // 32 (cout) x 32 (cin) x T tiles through LDS: the read is contiguous along (ci, tap) of one cout row, the two writes
-    // are contiguous along cout (w_fwd) and along cin (w_bwd) -- a direct scatter runs at ~1 TB/s, 175 us per step
-    const int nct = (Cout + TS - 1) / TS, nit = (Cin + TS - 1) / TS;
-    for (int t = blockIdx.x; t < nct * nit; t += gridDim.x) {
-        const int co0 = (t / nit) * TS, ci0 = (t % nit) * TS;
-        const int nci = min(TS, Cin - ci0), nco = min(TS, Cout - co0);
-        const int row = nci * T;                              // contiguous floats of one cout row inside the tile
-        for (int e = threadIdx.x; e < nco * row; e += 256) {
-            const int co_l = e / row, rem = e - co_l * row;
-            const int ci_l = rem / T, tap = rem - ci_l * T;
-            tile[tap][co_l][ci_l] = w[((int64_t)(co0 + co_l) * Cin + ci0) * T + rem];
+    __syncthreads();
+    const int l32 = threadIdx.x & 31, g = threadIdx.x >> 5;
+    // A quad that straddles the ragged edge of the tile (co_l + 3 >= nco, ci_l + 3 >= nci) READS LDS rows / columns this tile never staged
+    // -- inside the array (largest column 32 T - 1 < R), holding whatever an earlier tile left -- and drops them in the per-element guard of
+    // the store: the guard must stay on the store, the padded columns of w_fwd / w_bwd are never written.
+    if (wf) {                                                 // 128-byte runs along cout; padded columns (>= Cout) are never written
+        const int co_l = (l32 & 7) * 4, ci_l = g * 4 + (l32 >> 3);
+        if (ci_l < nci && co_l < nco) {
+            const bool quad = co_l + 4 <= nco && (((uintptr_t)wf | (uintptr_t)(ldf * 4)) & 15) == 0;
+            const float* s = tile + co_l * R + ci_l * T;
+#pragma unroll
+            for (int tap = 0; tap < T; ++tap) {
+                const f4v v = {s[tap], s[R + tap], s[2 * R + tap], s[3 * R + tap]};
+                float* o = wf + ((int64_t)tap * Cin + ci0 + ci_l) * ldf + co0 + co_l;
+                if (quad) *(f4v*)o = v;
+                else
+#pragma unroll
+                    for (int k = 0; k < 4; ++k)
+                        if (co_l + k < nco) o[k] = v[k];
+            }
         }
-        __syncthreads();
-        if (wf)
-            for (int e = threadIdx.x; e < T * nci * nco; e += 256) {
-                const int co_l = e % nco, r = e / nco;
-                const int ci_l = r % nci, tap = r / nci;
-                wf[((int64_t)tap * Cin + ci0 + ci_l) * ldf + co0 + co_l] = tile[tap][co_l][ci_l];
+    }
+    if (wb) {                                                 // 128-byte runs along cin
+        const int ci_l = (l32 & 7) * 4, co_l = g * 4 + (l32 >> 3);
+        if (co_l < nco && ci_l < nci) {
+            const bool quad = ci_l + 4 <= nci && (((uintptr_t)wb | (uintptr_t)(ldb * 4)) & 15) == 0;
+            const float sc = bsc ? bsc[co0 + co_l] : 1.f;
+            const float* s = tile + co_l * R + ci_l * T;
+#pragma unroll
+            for (int tap = 0; tap < T; ++tap) {
+                f4v v = {s[tap], s[T + tap], s[2 * T + tap], s[3 * T + tap]};
+                if (bsc) v *= sc;
+                float* o = wb + ((int64_t)tap * Cout + co0 + co_l) * ldb + ci0 + ci_l;
+                if (quad) *(f4v*)o = v;
+                else
+#pragma unroll
+                    for (int k = 0; k < 4; ++k)
+                        if (ci_l + k < nci) o[k] = v[k];
             }
-        if (wb)
-            for (int e = threadIdx.x; e < T * nco * nci; e += 256) {
-                const int ci_l = e % nci, r = e / nci;
-                const int co_l = r % nco, tap = r / nco;
-                wb[((int64_t)tap * Cout + co0 + co_l) * ldb + ci0 + ci_l] = bsc ? tile[tap][co_l][ci_l] * bsc[co0 + co_l] : tile[tap][co_l][ci_l];
+        }
+    }
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(256) void k_weight_layouts_batched(const long long* __restrict__ desc, int nlayers) {
+    __shared__ float tile[WL_TS * (WL_TS * 9 + 1)];
+    __shared__ int cnt[WL_MAXL], pre[WL_MAXL + 1];
+    for (int i = threadIdx.x; i < nlayers; i += 256) {
+        const long long* d = desc + (int64_t)i * 10;
+        const int Cout = (int)d[3], Cin = (int)d[4], T = (int)d[5] * (int)d[6];
+        cnt[i] = (T == 1 || T == 9) ? ((Cout + WL_TS - 1) / WL_TS) * ((Cin + WL_TS - 1) / WL_TS) : (int)(((int64_t)Cout * Cin * T + WL_ELEMS - 1) / WL_ELEMS);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i <= nlayers; i += 256) {
+        int s = 0;
+        for (int j = 0; j < i; ++j) s += cnt[j];
+        pre[i] = s;
+    }
+    __syncthreads();
+    const int total = pre[nlayers];
+    for (int t = blockIdx.x; t < total; t += gridDim.x) {
+        int lo = 0, hi = nlayers - 1;                         // last layer whose first work item <= t (workgroup-uniform)
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (pre[mid] <= t) lo = mid; else hi = mid - 1;
+        }
+        lo = __builtin_amdgcn_readfirstlane(lo);
+        const int local = t - pre[lo];
+        const long long* d = desc + (int64_t)lo * 10;
+        const float* __restrict__ w = (const float*)d[0];
+        float* __restrict__ wf = (float*)d[1];
+        float* __restrict__ wb = (float*)d[2];
+        const int Cout = (int)d[3], Cin = (int)d[4], KH = (int)d[5], KW = (int)d[6], ldf = (int)d[7], ldb = (int)d[8];
+        const float* __restrict__ bsc = (const float*)d[9];
+        const int T = KH * KW;
+        if (T == 1 || T == 9) {
+            const int nit = (Cin + WL_TS - 1) / WL_TS;
+            const int co0 = (local / nit) * WL_TS, ci0 = (local % nit) * WL_TS;
+            if (T == 9) weight_layout_tile<9>(w, wf, wb, bsc, Cout, Cin, ldf, ldb, co0, ci0, tile);
+            else weight_layout_tile<1>(w, wf, wb, bsc, Cout, Cin, ldf, ldb, co0, ci0, tile);
+        } else {                                              // element-wise, it is tiny
+            const int64_t total_e = (int64_t)Cout * Cin * T;
+            for (int64_t i = (int64_t)local * WL_ELEMS + threadIdx.x; i < min(total_e, (int64_t)(local + 1) * WL_ELEMS); i += 256) {
+                const int tap = (int)(i % T);
+                const int64_t r = i / T;
+                const int ci = (int)(r % Cin), co = (int)(r / Cin);
+                const float v = w[i];
+                if (wf) wf[((int64_t)tap * Cin + ci) * ldf + co] = v;
+                if (wb) wb[((int64_t)tap * Cout + co) * ldb + ci] = bsc ? v * bsc[co] : v;
             }
-        __syncthreads();
+        }
     }
 }
 
@@ -2803,9 +2887,26 @@ int e2e_conv_weight_layouts(const float* w, int Cout, int Cin, int KH, int KW, f
     return E2E_OK;
 }
 
+// compute units of the current device (asked once; 256 on the MI355X)
+static int device_cus() {
+    static const int cus = [] {
+        int dev = 0, n = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+        return n;
+    }();
+    return cus;
+}
+
 int e2e_conv_weight_layouts_batched(const long long* desc, int nlayers, void* stream) {
-    E2E_REQUIRE(desc && nlayers > 0 && nlayers <= 65535, E2E_ERR_ARG, "e2e_conv_weight_layouts_batched: bad argument");
-    hipLaunchKernelGGL(k_weight_layouts_batched, dim3(256, nlayers), dim3(256), 0, (hipStream_t)stream, desc);
+    E2E_REQUIRE(desc && nlayers > 0, E2E_ERR_ARG, "e2e_conv_weight_layouts_batched: bad argument");
+    // The tile counts are in the device table, so the host cannot size the grid by them: 8 workgroups per CU is one turn of the grid-stride
+    // loop for the depth network (~1200 tiles of its ~40 layers on 2048 workgroups) and the tile's 37 KB of LDS lets 4 of them run on a CU
+    // at a time.  A workgroup past the end of the list reads the <= 256 table rows, builds the prefix and leaves.  A tile smaller than
+    // 32 x 32 would shorten the 128-byte runs of w_fwd (along cout) or of w_bwd (along cin) to 64 bytes; neither it nor another
+    // factor than 8 was measured.  Tables longer than the kernel's LDS prefix (WL_MAXL layers) go in several launches.
+    const int grid = device_cus() * 8;
+    for (int l0 = 0; l0 < nlayers; l0 += WL_MAXL)
+        hipLaunchKernelGGL(k_weight_layouts_batched, dim3(grid), dim3(256), 0, (hipStream_t)stream, desc + (int64_t)l0 * 10, nlayers - l0 < WL_MAXL ? nlayers - l0 : WL_MAXL);
     E2E_LAUNCH_CHECK("e2e_conv_weight_layouts_batched");
     return E2E_OK;
 }
