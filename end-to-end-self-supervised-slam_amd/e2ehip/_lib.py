@@ -5,11 +5,13 @@ device the call raises.  The CPU restatement lives in oracle/ and is test infras
 """
 import ctypes
 import os
+import re
 
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(_HERE), "lib", "libe2eslam_hip.so")
+HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "e2eslam.h")
 
 c_fp = ctypes.c_void_p
 c_int = ctypes.c_int
@@ -36,164 +38,69 @@ class E2EError(RuntimeError):
     pass
 
 
-# name -> argtypes (restype int unless listed in _RESTYPE)
-SIGNATURES = {
-    "e2e_version": [],
-    "e2e_last_error": [],
-    "e2e_backproject_fwd": [c_fp, c_fp, c_fp, c_int, c_int, c_int, c_fp],
-    "e2e_backproject_bwd": [c_fp, c_fp, c_fp, c_int, c_int, c_int, c_fp],
-    "e2e_project3d_fwd": [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_fp],
-    "e2e_project3d_bwd": [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_fp],
-    "e2e_grid_sample_fwd": [c_fp, Strides, c_fp, c_fp] + [c_int] * 8 + [c_fp],
-    "e2e_grid_sample_bwd": [c_fp, Strides, c_fp, c_fp, c_fp, c_fp] + [c_int] * 8 + [c_fp],
-    "e2e_grid_sample_bwd_exact": [c_fp, Strides, c_fp, c_fp, c_fp, c_fp, c_fp] + [c_int] * 8 + [c_fp],
-    "e2e_photometric_fwd": [c_fp, Strides, c_fp, Strides, c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp],
-    "e2e_photometric_bwd": [c_fp, Strides, c_fp, Strides, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp],
-    "e2e_warp_photo_workspace_floats": [c_int, c_int, c_int],
-    "e2e_warp_photo_fwd": [c_fp, c_fp, Strides, c_fp, Strides, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int,
-                           c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_fp],
-    "e2e_warp_photo_bwd": [c_fp, c_fp, Strides, c_fp, Strides, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int,
-                           c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_fp],
-    "e2e_warp_photo_lossgrad_workspace_floats": [c_int, c_int, c_int],
-    "e2e_warp_photo_lossgrad": [c_fp, c_fp, Strides, c_fp, Strides, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_fp, c_fp, c_fp,
-                                c_f32, c_f32, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_fp],
-    "e2e_warp_photo_lossgrad_chain": [c_fp, c_fp, Strides, c_fp, Strides, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_fp, c_fp, c_fp,
-                                      c_f32, c_f32, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_fp],
-    "e2e_warp_photo_lossgrad_chain_flush": [c_fp, c_int, c_int, c_fp, c_int, c_int, c_int, c_fp],
-    "e2e_warp_photo_lossgrad_hostgeo": [c_fp, c_fp, Strides, c_fp, Strides, c_fp, c_int, c_int, c_int, c_fp, c_fp, c_fp, c_f32, c_f32,
-                                        c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_fp],
-    "e2e_warp_photo_terms_lossgrad_workspace_floats": [c_int, c_int, c_int],
-    "e2e_warp_photo_terms_lossgrad": [c_fp, c_fp, c_fp, Strides, c_fp, Strides, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_fp, c_fp, c_int, c_fp,
-                                      c_f32, c_f32, c_f32, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_fp],
-    "e2e_smoothness_norm_lossgrad_workspace_floats": [c_int, c_int],
-    "e2e_smoothness_norm_lossgrad": [c_fp, c_fp, Strides, c_f32, c_fp, c_fp, c_fp, c_int, c_int, c_fp],
-    "e2e_vertex_normal_maps": [c_fp, c_fp, c_fp, c_f32, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_fp],
-    "e2e_vertex_maps_bwd": [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_fp],
-    "e2e_transform_points": [c_fp, c_fp, c_fp, c_i64, c_int, c_fp],
-    "e2e_pf_workspace_bytes": [c_i64, c_int, c_int],
-    "e2e_pf_associate": [c_fp, c_fp, c_fp, c_i64, c_fp, c_fp, c_fp, c_fp, c_f32, c_f32, c_fp, c_i64, c_int, c_int, c_fp],
-    "e2e_pf_table": [c_int, c_i64, c_fp, c_i64, c_int, c_int, c_fp, c_fp, c_fp],
-    "e2e_pf_fuse_append": [c_fp, c_fp, c_fp, c_fp, c_i64, c_i64, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_fp, c_fp],
-    "e2e_pf_associate_dev": [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_f32, c_f32, c_fp, c_i64, c_int, c_int, c_fp],
-    "e2e_pf_fuse_append_dev": [c_fp, c_fp, c_fp, c_fp, c_fp, c_i64, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_fp],
-    "e2e_frame_append_dev": [c_fp, c_fp, c_fp, c_fp, c_fp, c_i64, c_fp, c_fp, c_fp, c_fp, c_f32, c_fp, c_int, c_int, c_fp],
-    "e2e_knn1_index_capacity_bytes": [c_i64, c_i64],
-    "e2e_knn1_index_build_dev": [c_fp, c_fp, c_i64, c_i64, c_fp, c_fp],
-    "e2e_knn1_index_query_dev": [c_fp, c_i64, c_i64, c_i64, c_fp, c_fp, c_fp, c_fp],
-    "e2e_knn1_index_query_dev_image": [c_fp, c_i64, c_int, c_i64, c_i64, c_fp, c_fp, c_fp, c_fp],
-    "e2e_knn1_index_query_dev_image_warm": [c_fp, c_i64, c_int, c_fp, c_fp, c_i64, c_i64, c_fp, c_fp, c_fp, c_fp],
-    "e2e_knn1_index_capacity_bytes_res": [c_i64, c_i64, c_int],
-    "e2e_knn1_index_build_dev_res": [c_fp, c_fp, c_i64, c_i64, c_fp, c_int, c_fp],
-    "e2e_knn1_index_query_dev_res": [c_fp, c_i64, c_fp, c_fp, c_i64, c_i64, c_fp, c_int, c_fp, c_fp, c_fp],
-    "e2e_knn1_workspace_bytes": [c_i64, c_i64],
-    "e2e_knn1_fwd": [c_fp, c_i64, c_fp, c_i64, c_fp, c_fp, c_fp, c_int, c_fp],
-    "e2e_knn1_index_build": [c_fp, c_i64, c_i64, c_fp, c_fp],
-    "e2e_knn1_index_query": [c_fp, c_i64, c_i64, c_i64, c_fp, c_fp, c_fp, c_fp],
-    "e2e_knn1_bwd": [c_fp, c_fp, c_fp, c_fp, c_i64, c_fp, c_fp],
-    "e2e_knn1_bwd_ref": [c_fp, c_fp, c_fp, c_fp, c_i64, c_i64, c_fp, c_fp, c_fp],
-    "e2e_median_workspace_bytes": [],
-    "e2e_median_lower": [c_fp, c_i64, c_fp, c_fp, c_fp],
-    "e2e_depth_scale_workspace_bytes": [],
-    "e2e_depth_scale_fwd": [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_i64, c_fp],
-    "e2e_depth_scale_bwd": [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_i64, c_fp],
-    "e2e_depth_scale_bwd_at": [c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_fp, c_fp, c_i64, c_fp],
-    "e2e_depth_fixed_scale_fwd": [c_fp, c_f32, c_fp, c_fp, c_i64, c_fp],
-    "e2e_depth_fixed_scale_bwd": [c_fp, c_fp, c_f32, c_fp, c_i64, c_fp],
-    "e2e_reduce_workspace_floats": [],
-    "e2e_mean_diff_fwd": [c_fp, c_fp, c_i64, c_int, c_fp, c_fp, c_fp],
-    "e2e_mean_diff_bwd": [c_fp, c_fp, c_fp, c_i64, c_int, c_fp, c_fp],
-    "e2e_depth_metrics": [c_fp, c_fp, c_i64, c_int, c_fp, c_fp, c_fp],
-    "e2e_adam_step": [c_fp, c_fp, c_fp, c_fp, c_i64, c_f32, c_f32, c_f32, c_f32, c_int, c_fp],
-    "e2e_adam_step_mean": [c_fp, c_fp, c_fp, c_fp, c_fp, c_i64, c_f32, c_f32, c_f32, c_f32, c_int, c_fp],
-    "e2e_adam_step_resident": [c_fp, c_fp, c_fp, c_fp, c_fp, c_i64, c_f32, c_f32, c_f32, c_fp, c_int, c_fp, c_fp],
-    "e2e_mask_mul": [c_fp, Strides, c_fp, c_int, c_int, c_int, c_int, c_fp, c_fp],
-    "e2e_channel_mean": [c_fp, c_int, c_int, c_int, c_int, c_int, c_fp, c_fp],
-    "e2e_mean_normalize": [c_fp, c_fp, c_int, c_int, c_int, c_fp, c_fp, c_fp],
-    "e2e_masked_mean_lossgrad": [c_fp, c_fp, c_i64, c_f32, c_fp, c_fp, c_fp, c_fp],
-    "e2e_aux_workspace_floats": [],
-    "e2e_smoothness_lossgrad": [c_fp, c_fp, Strides, c_int, c_int, c_int, c_int, c_fp, c_fp, c_fp, c_fp],
-    "e2e_geometric_consistency_lossgrad": [c_fp, c_fp, c_fp, c_i64, c_fp, c_fp, c_fp, c_fp, c_fp],
-    "e2e_masked_l1_lossgrad": [c_fp, c_fp, c_fp, c_i64, c_fp, c_fp, c_fp, c_fp],
-    "e2e_min_reprojection_lossgrad": [c_fp, c_int, c_int, c_int, c_int, c_fp, c_fp, c_fp, c_fp],
-    "e2e_disp_blend_fwd": [c_fp, c_int, c_int, c_fp, c_fp],
-    "e2e_disp_blend_bwd": [c_fp, c_int, c_int, c_fp, c_fp],
-    "e2e_conv_weight_layouts": [c_fp, c_int, c_int, c_int, c_int, c_fp, c_int, c_fp, c_int, c_fp],
-    "e2e_conv_weight_layouts_batched": [c_fp, c_int, c_fp],
-    "e2e_conv2d_fwd": [c_fp, c_fp, c_int, c_int, c_fp, c_int, c_fp, c_fp, c_fp, c_fp] + [c_int] * 11 + [c_f32, c_f32, c_fp, c_fp],
-    "e2e_conv2d_splitk_workspace_floats": [c_i64, c_int, c_int],
-    "e2e_conv2d_bwd_data_workspace_floats": [c_int, c_int, c_int, c_int, c_int, c_int],
-    "e2e_conv2d_fwd_tuned": [c_fp, c_fp, c_int, c_int, c_fp, c_int, c_fp, c_fp, c_fp, c_fp] + [c_int] * 11 + [c_f32, c_f32, c_fp, c_int, c_int, c_int, c_fp],
-    "e2e_conv2d_bwd_data_fused_tuned": [c_fp, c_fp, c_int, c_fp] + [c_int] * 13 + [c_fp, c_int, c_fp, c_fp, c_int, c_int, c_int, c_fp],
-    "e2e_conv2d_bwd_weight_scaled_tuned": [c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_fp, c_fp, c_fp] + [c_int] * 13 + [c_f32, c_f32, c_int, c_fp],
-    "e2e_conv2d_wgrad_tuned_workspace_floats": [c_int] * 9,
-    "e2e_conv_tuned_workspace_floats": [c_i64, c_int],
-    "e2e_conv_workspace_flag_floats": [],
-    "e2e_conv_streamk_error_index": [],
-    "e2e_conv_gemm_choice": [c_i64, c_int, c_int, c_int, c_int, c_fp],
-    "e2e_conv2d_act_bwd": [c_fp, c_fp, c_fp, c_fp, c_i64, c_int, c_int, c_fp],
-    "e2e_conv2d_bwd_data": [c_fp, c_fp, c_int, c_fp] + [c_int] * 12 + [c_fp, c_fp],
-    "e2e_conv2d_bwd_data_acc": [c_fp, c_fp, c_int, c_fp] + [c_int] * 13 + [c_fp, c_fp],
-    "e2e_conv2d_bwd_data_fused": [c_fp, c_fp, c_int, c_fp] + [c_int] * 13 + [c_fp, c_int, c_fp, c_fp, c_fp],
-    "e2e_conv2d_gather_adjoint_act": [c_fp] + [c_int] * 7 + [c_fp, c_fp, c_int, c_int, c_fp, c_int, c_fp, c_int, c_fp],
-    "e2e_conv2d_bwd_weight_scaled": [c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_fp, c_fp, c_fp] + [c_int] * 13 + [c_f32, c_f32, c_fp],
-    "e2e_conv2d_bwd_weight_scaled_deferred": [c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_fp, c_fp, c_fp] + [c_int] * 13 + [c_f32, c_f32, ctypes.POINTER(WgradReduceDesc), c_fp],
-    "e2e_conv2d_bwd_pair_deferred": [c_fp, c_fp, c_int, c_fp] + [c_int] * 13 + [c_fp, c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_fp, c_fp, c_fp,
-                                     c_int, c_f32, c_f32, ctypes.POINTER(WgradReduceDesc), c_int, c_fp],
-    "e2e_wgrad_reduce_batch_prepare": [ctypes.POINTER(WgradReduceDesc), c_int],
-    "e2e_wgrad_reduce_batched": [c_fp, c_int, ctypes.c_longlong, c_fp],
-    "e2e_copy_batch_prepare": [ctypes.POINTER(CopyDesc), c_int],
-    "e2e_copy_batched": [c_fp, c_int, ctypes.c_longlong, c_fp],
-    "e2e_head_bwd_act": [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_int, c_fp],
-    "e2e_conv2d_act_bwd_acc": [c_fp, c_fp, c_fp, c_fp, c_i64, c_int, c_int, c_int, c_fp],
-    "e2e_conv2d_gather_adjoint": [c_fp] + [c_int] * 7 + [c_fp, c_fp, c_int, c_int, c_fp],
-    "e2e_conv2d_wgrad_workspace_floats": [c_int] * 8,
-    "e2e_conv2d_bwd_weight": [c_fp, c_fp, c_fp, c_int, c_int, c_fp, c_fp, c_fp] + [c_int] * 13 + [c_f32, c_f32, c_fp],
-    "e2e_maxpool3x3s2_fwd": [c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp],
-    "e2e_maxpool3x3s2_bwd": [c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_int, c_int, c_fp],
-    "e2e_maxpool3x3s2_fwd_idx": [c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp],
-    "e2e_maxpool3x3s2_bwd_idx": [c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_int, c_int, c_fp],
-    "e2e_bn_fold": [c_fp, c_fp, c_fp, c_fp, c_f32, c_fp, c_fp, c_fp, c_int, c_fp],
-    "e2e_affine_fwd": [c_fp, c_fp, c_fp, c_fp, c_int, c_fp, c_i64, c_int, c_fp],
-    "e2e_affine_bwd_workspace_floats": [c_int],
-    "e2e_affine_bwd": [c_fp, c_fp, c_fp, c_fp, c_i64, c_int, c_fp, c_fp, c_int, c_fp, c_fp],
-    "e2e_upsample2_concat": [c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_int, c_fp],
-    "e2e_head_fwd": [c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_int, c_fp],
-    "e2e_head_workspace_floats": [],
-    "e2e_head_bwd": [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp],
-    "e2e_icp_workspace_bytes": [],
-    "e2e_icp_state_doubles": [],
-    "e2e_icp_state_init": [c_fp, c_fp, c_fp, c_fp, c_fp, ctypes.c_double, c_fp],
-    "e2e_icp_update": [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_fp],
-    "e2e_icp_reduce_update": [c_fp, c_fp, c_fp, c_fp, c_fp, c_f32, c_i64, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int,
-                              ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_fp],
-    "e2e_icp_source_subsample": [c_fp, c_fp, c_int, c_int, c_int, c_fp, c_fp, c_fp],
-    "e2e_pf_active_subsample_dev": [c_fp, c_fp, c_fp, c_i64, c_fp, c_int, c_int, c_int, c_fp, c_fp, c_fp, c_i64, c_fp],
-    "e2e_icp_normal_equations": [c_fp, c_fp, c_fp, c_fp, c_fp, c_f32, c_i64, c_fp, c_fp, c_fp],
-}
-_RESTYPE = {"e2e_last_error": ctypes.c_char_p, "e2e_warp_photo_workspace_floats": c_i64,
-            "e2e_warp_photo_lossgrad_workspace_floats": c_i64, "e2e_pf_workspace_bytes": c_i64,
-            "e2e_warp_photo_terms_lossgrad_workspace_floats": c_i64, "e2e_smoothness_norm_lossgrad_workspace_floats": c_i64,
-            "e2e_knn1_workspace_bytes": c_i64, "e2e_knn1_index_capacity_bytes": c_i64, "e2e_knn1_index_capacity_bytes_res": c_i64, "e2e_median_workspace_bytes": c_i64,
-            "e2e_depth_scale_workspace_bytes": c_i64, "e2e_reduce_workspace_floats": c_i64,
-            "e2e_conv2d_wgrad_workspace_floats": c_i64, "e2e_conv2d_wgrad_tuned_workspace_floats": c_i64, "e2e_conv_tuned_workspace_floats": c_i64, "e2e_conv2d_splitk_workspace_floats": c_i64, "e2e_conv2d_bwd_data_workspace_floats": c_i64,
-            "e2e_head_workspace_floats": c_i64, "e2e_icp_workspace_bytes": c_i64, "e2e_icp_state_doubles": c_i64, "e2e_aux_workspace_floats": c_i64,
-            "e2e_affine_bwd_workspace_floats": c_i64, "e2e_wgrad_reduce_batch_prepare": ctypes.c_longlong, "e2e_copy_batch_prepare": ctypes.c_longlong}
+# the C vocabulary of include/e2eslam.h; every pointer (device or host) is a void*
+_CTYPES = {"int": c_int, "int64_t": c_i64, "long long": ctypes.c_longlong, "float": c_f32, "double": ctypes.c_double,
+           "e2e_strides": Strides}
+_STRUCTS = {"e2e_strides": Strides, "e2e_wgrad_reduce_desc": WgradReduceDesc, "e2e_copy_desc": CopyDesc}
 
+
+def _ctype(decl, what):
+    """'const float* x' -> ('x', c_void_p); raises E2EError naming `what` for a type outside the vocabulary."""
+    m = re.fullmatch(r"(?:const\s+)?(\w+(?:\s+\w+)*?)\s*(\*?)\s*(\w+)", decl.strip())
+    if not m or (not m.group(2) and m.group(1) not in _CTYPES):
+        raise E2EError(f"include/e2eslam.h: cannot bind `{decl.strip()}` in {what}")
+    return m.group(3), c_fp if m.group(2) else _CTYPES[m.group(1)]
+
+
+def parse_header(text):
+    """-> ({entry point: (restype, ((parameter name, ctype), ...))}, {struct name: [(field name, ctype), ...]})."""
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = re.sub(r"^\s*(#|extern\b|\}\s*$).*$", "", text, flags=re.M)
+    structs = {}
+    for body, name in re.findall(r"typedef\s+struct\s+\w+\s*\{(.*?)\}\s*(\w+)\s*;", text, flags=re.S):
+        fields = structs[name] = []
+        for decl in filter(str.strip, body.split(";")):
+            first, *more = decl.split(",")
+            fields.append(_ctype(first, f"struct {name}"))
+            fields += [(n.strip(), fields[-1][1]) for n in more]
+    text = re.sub(r"typedef\s+struct.*?\}\s*\w+\s*;", "", text, flags=re.S)
+    protos = {}
+    for decl in filter(str.strip, text.split(";")):
+        m = re.fullmatch(r"\s*(const char\*|\w+(?:\s+\w+)?)\s+(e2e_\w+)\s*\((.*)\)\s*", decl, flags=re.S)
+        if not m or (m.group(1) != "const char*" and m.group(1) not in _CTYPES):
+            raise E2EError(f"include/e2eslam.h: cannot bind the declaration `{' '.join(decl.split())}`")
+        ret, name, params = m.groups()
+        params = () if params.strip() == "void" else tuple(_ctype(p, name) for p in params.split(","))
+        if len({n for n, _ in params}) != len(params) or name in protos:
+            raise E2EError(f"include/e2eslam.h: duplicate name in the declaration of {name}")
+        protos[name] = (ctypes.c_char_p if ret == "const char*" else _CTYPES[ret], params)
+    return protos, structs
+
+
+SIGNATURES, RESTYPES, PARAMS, _NAMESET = {}, {}, {}, {}     # filled by load(): name -> argtypes / restype / parameter names (in order, as a set)
 _lib = None
 
 
 def load():
-    """Load the shared library (once).  Raises E2EError if it has not been built."""
+    """Load the shared library (once) and give every prototype of the header its ctypes signature.  Raises E2EError if the
+    library has not been built."""
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise E2EError(f"{LIB_PATH} not found: build it with `python __graft_entry__.py build` "
                            "(there is no CPU / PyTorch fallback for the hot path)")
+        with open(HEADER_PATH) as f:
+            protos, structs = parse_header(f.read())
+        for n, cls in _STRUCTS.items():
+            if structs.get(n) != list(cls._fields_):
+                raise E2EError(f"include/e2eslam.h: struct {n} and its ctypes class {cls.__name__} differ")
         lib = ctypes.CDLL(LIB_PATH)
-        for name, args in SIGNATURES.items():
+        for name, (restype, params) in protos.items():
             fn = getattr(lib, name)
-            fn.argtypes = args
-            fn.restype = _RESTYPE.get(name, c_int)
+            fn.argtypes = SIGNATURES[name] = [t for _, t in params]
+            fn.restype = RESTYPES[name] = restype
+            PARAMS[name] = tuple(n for n, _ in params)
+            _NAMESET[name] = frozenset(PARAMS[name])
         _lib = lib
     return _lib
 
@@ -201,12 +108,40 @@ def load():
 PROFILE_HOOK = [None]           # e2ehip.profile.KernelTimer while a timing pass is active
 
 
-def call(name, *args):
+def bind(name, *args, geom=None, **kw):
+    """The argument vector of entry point `name`: a positional prefix, then the remaining parameters by the names the header gives
+    them.  `geom` is a mapping that may hold more names than the prototype declares (a layer's geometry, shared by the forward, the
+    backward forms and the workspace queries): it fills what neither `args` nor `kw` gives.  Every keyword must name a parameter that
+    is not already given positionally, and every parameter must be given: TypeError otherwise, before anything is launched."""
+    load()
+    names = PARAMS[name]
+    if len(args) > len(names):
+        raise TypeError(f"{name}: takes {len(names)} arguments, {len(args)} given")
+    if not kw.keys() <= _NAMESET[name]:
+        raise TypeError(f"{name}: no parameter named {sorted(kw.keys() - _NAMESET[name])}")
+    if args and not kw.keys().isdisjoint(names[:len(args)]):
+        raise TypeError(f"{name}: {sorted(kw.keys() & set(names[:len(args)]))} given both positionally and by name")
+    named = {**geom, **kw} if geom else kw
+    try:
+        return args + tuple(map(named.__getitem__, names[len(args):]))
+    except KeyError as e:
+        raise TypeError(f"{name}: missing parameter {e.args[0]!r}") from None
+
+
+def call(name, *args, **kw):
+    """Launch an entry point that returns a status; see bind() for the keyword form."""
+    if kw:
+        args = bind(name, *args, **kw)
     lib = load()
     hook = PROFILE_HOOK[0]
     rc = getattr(lib, name)(*args) if hook is None else hook.around(name, args, lambda: getattr(lib, name)(*args))
     if rc != 0:
         raise E2EError(f"{name} failed ({rc}): {lib.e2e_last_error().decode()}")
+
+
+def query(name, *args, **kw):
+    """An entry point that returns a value (workspace sizes, the *_batch_prepare totals): no status check, no timing."""
+    return getattr(load(), name)(*(bind(name, *args, **kw) if kw else args))
 
 
 def stream():

@@ -253,8 +253,8 @@ class _Affine(torch.autograd.Function):
             gs = (ss if direct else torch.empty(p_scale.shape, device=g.device, dtype=torch.float32)) if want_s else None
             gb = (sb if direct else torch.empty(p_shift.shape, device=g.device, dtype=torch.float32)) if want_b else None
             ws = torch.empty(L.load().e2e_affine_bwd_workspace_floats(C), device=g.device, dtype=torch.float32)
-            L.call("e2e_affine_bwd", L.ptr(g), L.ptr(z), L.ptr(mean), L.ptr(rstd), z.numel() // C, C, L.ptr(gs), L.ptr(gb), 1 if direct else 0,
-                   L.ptr(ws), st)
+            L.call("e2e_affine_bwd", dy=L.ptr(g), z=L.ptr(z), mean=L.ptr(mean), rstd=L.ptr(rstd), P=z.numel() // C, C=C, dgamma=L.ptr(gs),
+                   dbeta=L.ptr(gb), accumulate=1 if direct else 0, workspace=L.ptr(ws), stream=st)
             if direct:
                 gs = gb = None
         dz = None
@@ -321,7 +321,8 @@ class _Upsample2Concat(torch.autograd.Function):
         g = _cl(g)
         g0 = torch.empty(B, C1, h, w, device=g.device, dtype=torch.float32, memory_format=CL)
         g1 = torch.empty(B, C2, 2 * h, 2 * w, device=g.device, dtype=torch.float32, memory_format=CL) if C2 else None
-        L.call("e2e_conv2d_gather_adjoint", L.ptr(g), B, 2 * h, 2 * w, C1 + C2, C1, 2, 0, L.ptr(g0), L.ptr(g1), 0, 0, L.stream())
+        L.call("e2e_conv2d_gather_adjoint", dxp=L.ptr(g), B=B, Hs=2 * h, Ws=2 * w, Cin=C1 + C2, C1=C1, up=2, padded=0, d_src0=L.ptr(g0),
+               d_src1=L.ptr(g1), accumulate0=0, accumulate1=0, stream=L.stream())
         return g0, g1
 
 
@@ -360,7 +361,8 @@ class _Head(torch.autograd.Function):
         dw = torch.empty_like(w) if ctx.needs_input_grad[1] else None
         db = torch.empty(1, device=g.device, dtype=torch.float32) if (has_bias and ctx.needs_input_grad[2]) else None
         ws = torch.empty(L.load().e2e_head_workspace_floats(), device=g.device, dtype=torch.float32)
-        L.call("e2e_head_bwd", L.ptr(dz), L.ptr(x), L.ptr(w), L.ptr(dx), L.ptr(dw), L.ptr(db), L.ptr(ws), B, H, W, C, st)
+        L.call("e2e_head_bwd", dz=L.ptr(dz), x=L.ptr(x), w=L.ptr(w), dx=L.ptr(dx), dw=L.ptr(dw), dbias=L.ptr(db), workspace=L.ptr(ws),
+               B=B, H=H, W=W, Cin=C, stream=st)
         sw = _sink(ctx.params[0], w.shape) if dw is not None else None
         sb = _sink(ctx.params[1], (1,)) if db is not None else None
         if sw is not None:                          # tiny tensors (145 numbers): add in place, return nothing
@@ -425,27 +427,30 @@ class _Conv2d(torch.autograd.Function):
             residual = _cl(L.dev(residual, "residual"))
         out = torch.empty(B, Cout, Ho, Wo, device=dev, dtype=torch.float32, memory_format=CL)
         isub, imul = in_norm if in_norm is not None else (0.0, 1.0)
+        # the call's geometry under the parameter names of include/e2eslam.h: every entry point below takes what its prototype declares
+        geom = dict(B=B, Hs=Hs, Ws=Ws, Cin=Cin, Cout=Cout, Ho=Ho, Wo=Wo, KH=KH, KW=KW, stride=stride, pad=pad, pad_mode=pad_mode, C1=C1, up=up,
+                    in_sub=float(isub), in_mul=float(imul))
+        operands = dict(src0=L.ptr(src0), src1=L.ptr(src1), w_fwd=L.ptr(wf), ld_fwd=ldf, scale=L.ptr(scale), shift=L.ptr(sh), residual=L.ptr(residual),
+                        out=L.ptr(out), act=act)
         if tune is not None:
             ws = _gemm_workspace(L.load().e2e_conv_tuned_workspace_floats(B * Ho * Wo, Cout), dev)
-            L.call("e2e_conv2d_fwd_tuned", L.ptr(src0), L.ptr(src1), C1, up, L.ptr(wf), ldf, L.ptr(scale), L.ptr(sh), L.ptr(residual), L.ptr(out),
-                   B, Hs, Ws, Cin, Cout, KH, KW, stride, pad, pad_mode, act, float(isub), float(imul), L.ptr(ws), tune[0], tune[1], tune[2], L.stream())
+            L.call("e2e_conv2d_fwd_tuned", geom=geom, workspace=L.ptr(ws), tile_m=tune[0], tile_n=tune[1], ksplit=tune[2], stream=L.stream(), **operands)
             if tune[2] < 0:
                 check_streamk(ws)
         else:
             ws = _gemm_workspace(L.load().e2e_conv2d_splitk_workspace_floats(B * Ho * Wo, Cout, KH * KW * Cin), dev)
-            L.call("e2e_conv2d_fwd", L.ptr(src0), L.ptr(src1), C1, up, L.ptr(wf), ldf, L.ptr(scale), L.ptr(sh), L.ptr(residual), L.ptr(out),
-                   B, Hs, Ws, Cin, Cout, KH, KW, stride, pad, pad_mode, act, float(isub), float(imul), L.ptr(ws), L.stream())
+            L.call("e2e_conv2d_fwd", geom=geom, workspace=L.ptr(ws), stream=L.stream(), **operands)
         ctx.tune = tune
         ctx.save_for_backward(src0, src1, wb, scale, out)
-        ctx.cfg = (B, Hs, Ws, Cin, Cout, Ho, Wo, KH, KW, stride, pad, pad_mode, act, up, C1, ldb, float(isub), float(imul),
-                   bias is not None, residual is not None)
+        ctx.geom, ctx.cfg = geom, (act, ldb, bias is not None, residual is not None)
         return out
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g):
         src0, src1, wb, scale, out = ctx.saved_tensors
-        (B, Hs, Ws, Cin, Cout, Ho, Wo, KH, KW, stride, pad, pad_mode, act, up, C1, ldb, isub, imul, has_bias, has_res) = ctx.cfg
+        geom, (act, ldb, has_bias, has_res) = ctx.geom, ctx.cfg
+        B, Hs, Ws, Cin, Cout, KH, KW, C1, up = (geom[k] for k in ("B", "Hs", "Ws", "Cin", "Cout", "KH", "KW", "C1", "up"))
         dev = g.device
         g = _cl(g)
         st = L.stream()
@@ -467,27 +472,27 @@ class _Conv2d(torch.autograd.Function):
         needs = ctx.needs_input_grad
         g0 = g1 = gw = gb = None
         if needs[0] or needs[1]:
-            pp = pad if pad_mode == 1 else 0
+            pp = geom["pad"] if geom["pad_mode"] == 1 else 0
             direct = pp == 0 and up == 1 and src1 is None
             dxp = torch.empty(B, Cin, Hs + 2 * pp, Ws + 2 * pp, device=dev, dtype=torch.float32, memory_format=CL)
             tune = ctx.tune
             if tune is not None:
                 ws2 = _gemm_workspace(L.load().e2e_conv_tuned_workspace_floats(B * (Hs + 2 * pp) * (Ws + 2 * pp), Cin), dev)
-                L.call("e2e_conv2d_bwd_data_fused_tuned", L.ptr(dZ), L.ptr(wb), ldb, L.ptr(dxp), B, Hs, Ws, Cin, Cout, Ho, Wo, KH, KW, stride, pad, pad_mode,
-                       0, None, 0, None, L.ptr(ws2), tune[0], tune[1], tune[2], st)
+                L.call("e2e_conv2d_bwd_data_fused_tuned", geom=geom, da=L.ptr(dZ), w_bwd=L.ptr(wb), ld_bwd=ldb, dxp=L.ptr(dxp), accumulate=0, x_in=None,
+                       in_act=0, pre_add=None, workspace=L.ptr(ws2), tile_m=tune[0], tile_n=tune[1], ksplit=tune[2], stream=st)
                 if tune[2] < 0:
                     check_streamk(ws2)
             else:
-                ws2 = _gemm_workspace(L.load().e2e_conv2d_bwd_data_workspace_floats(B, Hs + 2 * pp, Ws + 2 * pp, Cin, KH * KW * Cout, stride), dev)
-                L.call("e2e_conv2d_bwd_data", L.ptr(dZ), L.ptr(wb), ldb, L.ptr(dxp), B, Hs, Ws, Cin, Cout, Ho, Wo, KH, KW, stride, pad, pad_mode,
-                       L.ptr(ws2), st)
+                ws2 = _gemm_workspace(L.query("e2e_conv2d_bwd_data_workspace_floats", geom=geom, Hd=Hs + 2 * pp, Wd=Ws + 2 * pp, cols=Cin, K=KH * KW * Cout), dev)
+                L.call("e2e_conv2d_bwd_data", geom=geom, dz=L.ptr(dZ), w_bwd=L.ptr(wb), ld_bwd=ldb, dxp=L.ptr(dxp), workspace=L.ptr(ws2), stream=st)
             if direct:
                 g0 = dxp
             else:
                 g0 = torch.empty(B, C1, Hs // up, Ws // up, device=dev, dtype=torch.float32, memory_format=CL)
                 if src1 is not None:
                     g1 = torch.empty(B, Cin - C1, Hs, Ws, device=dev, dtype=torch.float32, memory_format=CL)
-                L.call("e2e_conv2d_gather_adjoint", L.ptr(dxp), B, Hs, Ws, Cin, C1, up, 1 if pp else 0, L.ptr(g0), L.ptr(g1), 0, 0, st)
+                L.call("e2e_conv2d_gather_adjoint", geom=geom, dxp=L.ptr(dxp), padded=1 if pp else 0, d_src0=L.ptr(g0), d_src1=L.ptr(g1), accumulate0=0,
+                       accumulate1=0, stream=st)
         if needs[2]:
             want_b = has_bias and needs[3]
             sw = _sink(ctx.params[0], (Cout, Cin, KH, KW))
@@ -495,8 +500,7 @@ class _Conv2d(torch.autograd.Function):
             direct = sw is not None and (sb is not None or not want_b)     # both into the flat gradient buffer, or neither
             gw = sw if direct else torch.empty(Cout, Cin, KH, KW, device=dev, dtype=torch.float32)
             gb = (sb if direct else torch.empty(Cout, device=dev, dtype=torch.float32)) if want_b else None
-            ws = torch.empty(L.load().e2e_conv2d_wgrad_workspace_floats(B, Ho, Wo, Cin, Cout, KH, KW, 1 if gb is not None else 0),
-                             device=dev, dtype=torch.float32)
+            ws = torch.empty(L.query("e2e_conv2d_wgrad_workspace_floats", geom=geom, has_bias=1 if gb is not None else 0), device=dev, dtype=torch.float32)
             st_w = st
             side = _overlap_stream(ctx.params[0]) if direct else None
             if side is not None:
@@ -505,8 +509,8 @@ class _Conv2d(torch.autograd.Function):
                     if t is not None:
                         t.record_stream(side)
                 st_w = ctypes.c_void_p(side.cuda_stream)
-            L.call("e2e_conv2d_bwd_weight", L.ptr(dZ), L.ptr(src0), L.ptr(src1), C1, up, L.ptr(gw), L.ptr(gb), L.ptr(ws), B, Hs, Ws, Cin,
-                   Cout, Ho, Wo, KH, KW, stride, pad, pad_mode, 1 if direct else 0, isub, imul, st_w)
+            L.call("e2e_conv2d_bwd_weight", geom=geom, dz=L.ptr(dZ), src0=L.ptr(src0), src1=L.ptr(src1), dw=L.ptr(gw), dbias=L.ptr(gb), workspace=L.ptr(ws),
+                   accumulate=1 if direct else 0, stream=st_w)
             if direct:
                 gw = gb = None
         return g0, g1, gw, gb, None, None, d_res, None, None, None, None, None, None, None, None, None

@@ -45,21 +45,23 @@ class WarpPhotoPlan:
         self.t = (depth_tgt, depth_src, init_tgt, init_src, src, tgt, K, inv_K, T)
         return self
 
-    def forward(self, pmap=None):
+    def _operands(self):
+        """What every launch form of the step shares, under the parameter names of include/e2eslam.h: the bound tensors, the flags, the
+        sizes and the stream.  Each call passes it as `geom` (L.bind takes what the prototype declares) and names only what differs."""
         dt, ds, it, is_, src, tgt, K, iK, T = self.t
-        L.call("e2e_warp_photo_fwd", L.ptr(dt), L.ptr(src), L.strides4(src), L.ptr(tgt), L.strides4(tgt), L.ptr(K), L.ptr(iK),
-               L.ptr(T), L.ptr(self.synth), L.ptr(self.valid), L.ptr(pmap), self.use_mask, self.pad, self.reg,
-               L.ptr(it) if self.reg else None, L.ptr(is_) if self.reg else None, L.ptr(ds) if self.reg else None,
-               L.ptr(self.loss), L.ptr(self.ws), self.B, self.H, self.W, L.stream())
+        reg = self.reg
+        return dict(depth_tgt=L.ptr(dt), src=L.ptr(src), src_strides=L.strides4(src), tgt=L.ptr(tgt), tgt_strides=L.strides4(tgt), K=L.ptr(K),
+                    inv_K=L.ptr(iK), T=L.ptr(T), use_mask=self.use_mask, padding_mode=self.pad, reg_kind=reg, reg_init_tgt=L.ptr(it) if reg else None,
+                    reg_init_src=L.ptr(is_) if reg else None, depth_src=L.ptr(ds) if reg else None, B=self.B, H=self.H, W=self.W, stream=L.stream())
+
+    def forward(self, pmap=None):
+        L.call("e2e_warp_photo_fwd", geom=self._operands(), synth=L.ptr(self.synth), valid=L.ptr(self.valid), pmap=L.ptr(pmap), loss_out=L.ptr(self.loss),
+               workspace=L.ptr(self.ws))
         return self.loss
 
     def backward(self):
-        dt, ds, it, is_, src, tgt, K, iK, T = self.t
-        L.call("e2e_warp_photo_bwd", L.ptr(dt), L.ptr(src), L.strides4(src), L.ptr(tgt), L.strides4(tgt), L.ptr(K), L.ptr(iK),
-               L.ptr(T), L.ptr(self.synth), L.ptr(self.valid), self.use_mask, self.pad, self.reg,
-               L.ptr(it) if self.reg else None, L.ptr(is_) if self.reg else None, L.ptr(ds) if self.reg else None,
-               L.ptr(self.g_loss), L.ptr(self.g_depth_tgt), L.ptr(self.g_depth_src) if self.reg else None,
-               self.B, self.H, self.W, L.stream())
+        L.call("e2e_warp_photo_bwd", geom=self._operands(), synth=L.ptr(self.synth), valid=L.ptr(self.valid), g_loss=L.ptr(self.g_loss),
+               g_depth_tgt=L.ptr(self.g_depth_tgt), g_depth_src=L.ptr(self.g_depth_src) if self.reg else None)
         return self.g_depth_tgt, self.g_depth_src
 
 
@@ -90,14 +92,11 @@ class LossGradPlan(WarpPhotoPlan):
         """One kernel for the whole step: the loss sums go to slot set `set_cur` (0..7) and the previous chained launch's
         set `set_prev` is finalised into `loss_prev` (a 2-float tensor).  Finish the last step with flush_chain().
         -> (g_depth_tgt, g_depth_src)."""
-        dt, ds, it, is_, src, tgt, K, iK, T = self.t
         geo = getattr(self, "_geo", None)
-        L.call("e2e_warp_photo_lossgrad_chain", L.ptr(dt), L.ptr(src), L.strides4(src), L.ptr(tgt), L.strides4(tgt),
-               None if geo is not None else L.ptr(K), None if geo is not None else L.ptr(iK), None if geo is not None else L.ptr(T),
-               ctypes.cast(geo, ctypes.c_void_p) if geo is not None else None, self.use_mask, self.pad, self.reg,
-               L.ptr(it) if self.reg else None, L.ptr(is_) if self.reg else None, L.ptr(ds) if self.reg else None, self.w_photo, self.w_reg,
-               int(set_cur), int(set_prev), L.ptr(loss_prev) if set_prev >= 0 else None, L.ptr(self.g_depth_tgt),
-               L.ptr(self.g_depth_src) if self.reg else None, L.ptr(self.ws), self.B, self.H, self.W, L.stream())
+        matrices = dict(geometry12_host=None) if geo is None else dict(K=None, inv_K=None, T=None, geometry12_host=ctypes.cast(geo, ctypes.c_void_p))
+        L.call("e2e_warp_photo_lossgrad_chain", geom=self._operands(), w_photo=self.w_photo, w_reg=self.w_reg, set_cur=int(set_cur), set_prev=int(set_prev),
+               loss_prev_out=L.ptr(loss_prev) if set_prev >= 0 else None, g_depth_tgt=L.ptr(self.g_depth_tgt),
+               g_depth_src=L.ptr(self.g_depth_src) if self.reg else None, workspace=L.ptr(self.ws), **matrices)
         return self.g_depth_tgt, self.g_depth_src
 
     def flush_chain(self, set_last, loss_out):
@@ -107,18 +106,12 @@ class LossGradPlan(WarpPhotoPlan):
     def step(self, want_loss=True):
         """-> (loss[2], g_depth_tgt, g_depth_src); gradients are of w_photo*loss[0] + w_reg*loss[1].
         want_loss=False launches the main kernel only (no second-stage reduction of the loss)."""
-        dt, ds, it, is_, src, tgt, K, iK, T = self.t
-        loss_ptr = L.ptr(self.loss) if want_loss else None
+        outputs = dict(w_photo=self.w_photo, w_reg=self.w_reg, loss_out=L.ptr(self.loss) if want_loss else None, g_depth_tgt=L.ptr(self.g_depth_tgt),
+                       g_depth_src=L.ptr(self.g_depth_src) if self.reg else None, workspace=L.ptr(self.ws))
         if getattr(self, "_geo", None) is not None:
-            L.call("e2e_warp_photo_lossgrad_hostgeo", L.ptr(dt), L.ptr(src), L.strides4(src), L.ptr(tgt), L.strides4(tgt),
-                   ctypes.cast(self._geo, ctypes.c_void_p), self.use_mask, self.pad, self.reg, L.ptr(it) if self.reg else None,
-                   L.ptr(is_) if self.reg else None, L.ptr(ds) if self.reg else None, self.w_photo, self.w_reg, loss_ptr,
-                   L.ptr(self.g_depth_tgt), L.ptr(self.g_depth_src) if self.reg else None, L.ptr(self.ws), self.H, self.W, L.stream())
-            return self.loss, self.g_depth_tgt, self.g_depth_src
-        L.call("e2e_warp_photo_lossgrad", L.ptr(dt), L.ptr(src), L.strides4(src), L.ptr(tgt), L.strides4(tgt), L.ptr(K), L.ptr(iK),
-               L.ptr(T), self.use_mask, self.pad, self.reg, L.ptr(it) if self.reg else None, L.ptr(is_) if self.reg else None,
-               L.ptr(ds) if self.reg else None, self.w_photo, self.w_reg, loss_ptr, L.ptr(self.g_depth_tgt),
-               L.ptr(self.g_depth_src) if self.reg else None, L.ptr(self.ws), self.B, self.H, self.W, L.stream())
+            L.call("e2e_warp_photo_lossgrad_hostgeo", geom=self._operands(), geometry12_host=ctypes.cast(self._geo, ctypes.c_void_p), **outputs)
+        else:
+            L.call("e2e_warp_photo_lossgrad", geom=self._operands(), **outputs)
         return self.loss, self.g_depth_tgt, self.g_depth_src
 
 
@@ -171,13 +164,10 @@ class TermsLossGradPlan(LossGradPlan):
         The smoothness term is a function of the DISPARITY: see smoothness_step."""
         if not self.flagged:
             return super().step(want_loss)
-        dt, ds, it, is_, src, tgt, K, iK, T = self.t
         need_src = self.writes_g_depth_src
-        L.call("e2e_warp_photo_terms_lossgrad", L.ptr(dt), L.ptr(ds) if need_src else None, L.ptr(src), L.strides4(src), L.ptr(tgt),
-               L.strides4(tgt), L.ptr(K), L.ptr(iK), L.ptr(T), self.use_mask, self.pad, self.reg, L.ptr(it) if self.reg else None,
-               L.ptr(is_) if self.reg else None, self.terms, L.ptr(self.noise), self.w_photo, self.w_reg, self.w_geometric,
-               L.ptr(self.loss5), L.ptr(self.g_depth_tgt), L.ptr(self.g_depth_src) if need_src else None, L.ptr(self.ws_terms),
-               self.B, self.H, self.W, L.stream())
+        L.call("e2e_warp_photo_terms_lossgrad", geom=self._operands(), depth_src=L.ptr(self.t[1]) if need_src else None, terms=self.terms,
+               tie_noise=L.ptr(self.noise), w_photo=self.w_photo, w_reg=self.w_reg, w_geometric=self.w_geometric, loss_out=L.ptr(self.loss5),
+               g_depth_tgt=L.ptr(self.g_depth_tgt), g_depth_src=L.ptr(self.g_depth_src) if need_src else None, workspace=L.ptr(self.ws_terms))
         return self.loss, self.g_depth_tgt, self.g_depth_src
 
     def smoothness_step(self, disp_src, g_disp_src):

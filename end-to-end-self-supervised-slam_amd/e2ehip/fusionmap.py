@@ -93,9 +93,9 @@ class FusionMap:
         return vertex_normal_maps(depth.reshape(1, self.H, self.W), K.reshape(1, 4, 4), pose.reshape(1, 4, 4), self.sigma)
 
     def associate(self, maps, K, pose):
-        L.call("e2e_pf_associate", L.ptr(self.points), L.ptr(self.normals), L.ptr(self.ccounts), self.M, L.ptr(K.contiguous()),
-               L.ptr(pose.contiguous()), L.ptr(maps["Vg"]), L.ptr(maps["ng"]), self.dist_th, self.dot_th, L.ptr(self.ws), self.cap,
-               self.H, self.W, L.stream())
+        L.call("e2e_pf_associate", map_points=L.ptr(self.points), map_normals=L.ptr(self.normals), map_ccounts=L.ptr(self.ccounts), M=self.M,
+               K=L.ptr(K.contiguous()), pose=L.ptr(pose.contiguous()), Vg=L.ptr(maps["Vg"]), Ng=L.ptr(maps["ng"]), dist_th=self.dist_th,
+               dot_th=self.dot_th, workspace=L.ptr(self.ws), map_capacity=self.cap, H=self.H, W=self.W, stream=L.stream())
         self._assoc_M = self.M
 
     def table(self, which):
@@ -109,9 +109,10 @@ class FusionMap:
     def fuse_append(self, maps, rgb, depth):
         rgb = L.dev(rgb, "rgb").contiguous()
         depth = L.dev(depth, "depth").contiguous()
-        L.call("e2e_pf_fuse_append", L.ptr(self.points), L.ptr(self.normals), L.ptr(self.colors), L.ptr(self.ccounts), self.M,
-               self.cap, L.ptr(depth), L.ptr(maps["Vg"]), L.ptr(maps["ng"]), L.ptr(rgb), L.ptr(maps["alpha"]), L.ptr(self.ws),
-               self.H, self.W, L.ptr(self._count), L.stream())
+        L.call("e2e_pf_fuse_append", map_points=L.ptr(self.points), map_normals=L.ptr(self.normals), map_colors=L.ptr(self.colors),
+               map_ccounts=L.ptr(self.ccounts), M=self.M, map_capacity=self.cap, depth=L.ptr(depth), Vg=L.ptr(maps["Vg"]), Ng=L.ptr(maps["ng"]),
+               rgb=L.ptr(rgb), alpha=L.ptr(maps["alpha"]), workspace=L.ptr(self.ws), H=self.H, W=self.W, new_count_out=L.ptr(self._count),
+               stream=L.stream())
         new_m = int(self._count.item())                     # one host sync per map step (module path; the driver uses step_resident)
         if new_m > self.cap:
             raise RuntimeError(f"PointFusion map capacity exceeded ({new_m} > {self.cap}); size it for the sequence")
@@ -140,12 +141,14 @@ class FusionMap:
         for n, t in (("rgb", rgb), ("depth", depth), ("K", K), ("pose", pose)):
             if not L.dev(t, n).is_contiguous():
                 raise ValueError(f"step_resident: {n} must be contiguous")
-        L.call("e2e_vertex_normal_maps", L.ptr(depth), L.ptr(K), L.ptr(pose), self._alpha_den, None, None, L.ptr(m["Vg"]), L.ptr(m["ng"]),
-               L.ptr(m["alpha"]), 1, self.H, self.W, st)
-        L.call("e2e_pf_associate_dev", L.ptr(self.points), L.ptr(self.normals), L.ptr(self.ccounts), L.ptr(self.count), L.ptr(K), L.ptr(pose),
-               L.ptr(m["Vg"]), L.ptr(m["ng"]), self.dist_th, self.dot_th, L.ptr(self.ws), self.cap, self.H, self.W, st)
-        L.call("e2e_pf_fuse_append_dev", L.ptr(self.points), L.ptr(self.normals), L.ptr(self.colors), L.ptr(self.ccounts), L.ptr(self.count),
-               self.cap, L.ptr(depth), L.ptr(m["Vg"]), L.ptr(m["ng"]), L.ptr(rgb), L.ptr(m["alpha"]), L.ptr(self.ws), self.H, self.W, st)
+        L.call("e2e_vertex_normal_maps", depth=L.ptr(depth), K=L.ptr(K), pose=L.ptr(pose), alpha_den=self._alpha_den, V=None, Nm=None, Vg=L.ptr(m["Vg"]),
+               Ng=L.ptr(m["ng"]), alpha=L.ptr(m["alpha"]), B=1, H=self.H, W=self.W, stream=st)
+        L.call("e2e_pf_associate_dev", map_points=L.ptr(self.points), map_normals=L.ptr(self.normals), map_ccounts=L.ptr(self.ccounts),
+               map_count_dev=L.ptr(self.count), K=L.ptr(K), pose=L.ptr(pose), Vg=L.ptr(m["Vg"]), Ng=L.ptr(m["ng"]), dist_th=self.dist_th,
+               dot_th=self.dot_th, workspace=L.ptr(self.ws), map_capacity=self.cap, H=self.H, W=self.W, stream=st)
+        L.call("e2e_pf_fuse_append_dev", map_points=L.ptr(self.points), map_normals=L.ptr(self.normals), map_colors=L.ptr(self.colors),
+               map_ccounts=L.ptr(self.ccounts), map_count_dev=L.ptr(self.count), map_capacity=self.cap, depth=L.ptr(depth), Vg=L.ptr(m["Vg"]),
+               Ng=L.ptr(m["ng"]), rgb=L.ptr(rgb), alpha=L.ptr(m["alpha"]), workspace=L.ptr(self.ws), H=self.H, W=self.W, stream=st)
         self._M = None                                      # the device knows; the host asks when it needs to
         self._assoc_M = None
         self._knn_dirty = True
@@ -161,8 +164,9 @@ class FusionMap:
         for n, t in (("rgb", rgb), ("depth", depth), ("K", K), ("pose", pose)):
             if not L.dev(t, n).is_contiguous():
                 raise ValueError(f"append_resident: {n} must be contiguous")
-        L.call("e2e_frame_append_dev", L.ptr(self.points), L.ptr(self.normals), L.ptr(self.colors), L.ptr(self.ccounts), L.ptr(self.count),
-               self.cap, L.ptr(depth), L.ptr(rgb), L.ptr(K), L.ptr(pose), self._alpha_den, L.ptr(self.ws), self.H, self.W, L.stream())
+        L.call("e2e_frame_append_dev", map_points=L.ptr(self.points), map_normals=L.ptr(self.normals), map_colors=L.ptr(self.colors),
+               map_ccounts=L.ptr(self.ccounts), map_count_dev=L.ptr(self.count), map_capacity=self.cap, depth=L.ptr(depth), rgb=L.ptr(rgb),
+               K=L.ptr(K), pose=L.ptr(pose), alpha_den=self._alpha_den, workspace=L.ptr(self.ws), H=self.H, W=self.W, stream=L.stream())
         self._M = None
         self._assoc_M = None
         self._knn_dirty = True
@@ -195,8 +199,8 @@ class ResidentKnnIndex:
         warm: int64 indices of an earlier query of nearby points against the same map state (may be `idx` itself): an upper bound the
         search starts from; the result is exact either way (e2e_knn1_index_query_dev_image_warm)."""
         if warm is not None:
-            L.call("e2e_knn1_index_query_dev_image_warm", L.ptr(p1), int(n1), int(row_len), L.ptr(self.ref), L.ptr(warm), self.map.cap, self.max_queries, L.ptr(self.ws),
-                   L.ptr(dists), L.ptr(idx), stream)
+            L.call("e2e_knn1_index_query_dev_image_warm", p1=L.ptr(p1), n1=int(n1), row_len=int(row_len), ref_points=L.ptr(self.ref), warm_idx=L.ptr(warm),
+                   n2_capacity=self.map.cap, max_queries=self.max_queries, index=L.ptr(self.ws), dists=L.ptr(dists), idx=L.ptr(idx), stream=stream)
         elif row_len:
             L.call("e2e_knn1_index_query_dev_image", L.ptr(p1), int(n1), int(row_len), self.map.cap, self.max_queries, L.ptr(self.ws), L.ptr(dists), L.ptr(idx), stream)
         else:

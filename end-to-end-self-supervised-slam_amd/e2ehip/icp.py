@@ -113,7 +113,7 @@ class ResidentOdometry:
             raise ValueError(f"unknown odometry mode {mode}")
         self.map, self.ds, self.numiters, self.mode = fmap, int(dsratio), int(numiters), mode
         self.damp, self.dist_thresh = float(damp), dist_thresh
-        self.lm = (float(lambda_max), float(B), float(B2), float(nu))
+        self.lm = dict(lambda_max=float(lambda_max), B=float(B), B2=float(B2), nu=float(nu))
         H, W, dev = fmap.H, fmap.W, fmap.device
         self.n_src = ((H + self.ds - 1) // self.ds) * ((W + self.ds - 1) // self.ds)
         # active points are map points that project into ONE frame: a few per pixel at most
@@ -142,11 +142,13 @@ class ResidentOdometry:
     def _search_reduce_update(self, pts, st, warm, phase, prev_pose):
         # every search after the first of a keyframe starts from the previous search's neighbours (same source points, moved by one small
         # step; same targets): a real target point's distance bounds the ball from the start -- exact for any candidate
-        L.call("e2e_knn1_index_query_dev_res", L.ptr(pts), self.n_src, L.ptr(self.tgt) if warm else None, L.ptr(self.idx) if warm else None, self.tcap,
-               self.n_src, L.ptr(self.index), self.cells, L.ptr(self.d), L.ptr(self.idx), st)
-        L.call("e2e_icp_reduce_update", L.ptr(pts), L.ptr(self.tgt), L.ptr(self.tgt_n), L.ptr(self.idx), L.ptr(self.d),
-               -1.0 if self.dist_thresh is None else float(self.dist_thresh), self.n_src, L.ptr(self.ws), L.ptr(self.state), L.ptr(self.T32),
-               L.ptr(self.step32), L.ptr(prev_pose), L.ptr(self.pose), 1 if self.mode == "gradicp" else 0, phase, *self.lm, st)
+        L.call("e2e_knn1_index_query_dev_res", p1=L.ptr(pts), n1=self.n_src, ref_points=L.ptr(self.tgt) if warm else None,
+               warm_idx=L.ptr(self.idx) if warm else None, n2_capacity=self.tcap, max_queries=self.n_src, index=L.ptr(self.index),
+               cells_per_axis=self.cells, dists=L.ptr(self.d), idx=L.ptr(self.idx), stream=st)
+        L.call("e2e_icp_reduce_update", src=L.ptr(pts), tgt=L.ptr(self.tgt), tgt_normals=L.ptr(self.tgt_n), idx=L.ptr(self.idx), dists=L.ptr(self.d),
+               dist_thresh=-1.0 if self.dist_thresh is None else float(self.dist_thresh), n=self.n_src, workspace=L.ptr(self.ws), state=L.ptr(self.state),
+               T32=L.ptr(self.T32), step32=L.ptr(self.step32), prev_pose=L.ptr(prev_pose), pose_out=L.ptr(self.pose),
+               mode=1 if self.mode == "gradicp" else 0, phase=phase, stream=st, **self.lm)
 
     def run(self, depth, K, prev_pose):
         """depth (H,W) of the live frame, K (4,4), prev_pose (4,4): contiguous device tensors (resident buffers when this is captured).
@@ -157,12 +159,14 @@ class ResidentOdometry:
             if not L.dev(t, n).is_contiguous():
                 raise ValueError(f"ResidentOdometry.run: {n} must be contiguous")
         # the live frame placed with the PREVIOUS pose (initial guess), and the map points active in that view
-        L.call("e2e_vertex_normal_maps", L.ptr(depth), L.ptr(K), L.ptr(prev_pose), self._alpha_den, None, None, L.ptr(self.Vg), L.ptr(self.Ng),
-               L.ptr(self.alpha), 1, H, W, st)
-        L.call("e2e_pf_associate_dev", L.ptr(m.points), L.ptr(m.normals), L.ptr(m.ccounts), L.ptr(m.count), L.ptr(K), L.ptr(prev_pose),
-               L.ptr(self.Vg), L.ptr(self.Ng), m.dist_th, m.dot_th, L.ptr(m.ws), m.cap, H, W, st)
-        L.call("e2e_pf_active_subsample_dev", L.ptr(m.points), L.ptr(m.normals), L.ptr(m.count), m.cap, L.ptr(m.ws), H, W, self.ds,
-               L.ptr(self.tgt), L.ptr(self.tgt_n), L.ptr(self.tcount), self.tcap, st)
+        L.call("e2e_vertex_normal_maps", depth=L.ptr(depth), K=L.ptr(K), pose=L.ptr(prev_pose), alpha_den=self._alpha_den, V=None, Nm=None,
+               Vg=L.ptr(self.Vg), Ng=L.ptr(self.Ng), alpha=L.ptr(self.alpha), B=1, H=H, W=W, stream=st)
+        L.call("e2e_pf_associate_dev", map_points=L.ptr(m.points), map_normals=L.ptr(m.normals), map_ccounts=L.ptr(m.ccounts), map_count_dev=L.ptr(m.count),
+               K=L.ptr(K), pose=L.ptr(prev_pose), Vg=L.ptr(self.Vg), Ng=L.ptr(self.Ng), dist_th=m.dist_th, dot_th=m.dot_th, workspace=L.ptr(m.ws),
+               map_capacity=m.cap, H=H, W=W, stream=st)
+        L.call("e2e_pf_active_subsample_dev", map_points=L.ptr(m.points), map_normals=L.ptr(m.normals), map_count_dev=L.ptr(m.count), map_capacity=m.cap,
+               workspace=L.ptr(m.ws), H=H, W=W, dsratio=self.ds, tgt=L.ptr(self.tgt), tgt_normals=L.ptr(self.tgt_n), tgt_count_dev=L.ptr(self.tcount),
+               tgt_capacity=self.tcap, stream=st)
         L.call("e2e_icp_source_subsample", L.ptr(self.Vg), L.ptr(depth), H, W, self.ds, L.ptr(self.src), L.ptr(self.status), st)
         L.call("e2e_knn1_index_build_dev_res", L.ptr(self.tgt), L.ptr(self.tcount), self.tcap, self.n_src, L.ptr(self.index), self.cells, st)
         L.call("e2e_icp_state_init", L.ptr(self.state), L.ptr(self.T32), L.ptr(self.step32), L.ptr(prev_pose), L.ptr(self.pose), self.damp, st)

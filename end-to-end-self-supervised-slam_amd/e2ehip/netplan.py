@@ -94,18 +94,21 @@ class _Conv:
             with torch.no_grad():
                 self.scale = (w / torch.sqrt(rv + eps)).contiguous()
                 self.shift = (b - rm * self.scale).contiguous()
-        lib = L.load()
+        # the layer's geometry under the parameter names of include/e2eslam.h: the forward, the backward forms and the workspace queries
+        # each take what their prototype declares (L.bind)
+        self.geom = dict(B=B, Hs=self.Hs, Ws=self.Ws, Cin=self.Cin, Cout=self.Cout, Ho=self.Ho, Wo=self.Wo, KH=self.KH, KW=self.KW, stride=stride,
+                         pad=pad, pad_mode=self.pm, C1=self.C1, up=up, in_sub=float(self.isub), in_mul=float(self.imul))
         # (a forward of ONE batch slot -- NetPlan.forward_one -- picks its own K split: sized for the larger of the two)
-        n = max(lib.e2e_conv2d_splitk_workspace_floats(b * self.Ho * self.Wo, self.Cout, self.KH * self.KW * self.Cin) for b in {B, 1})
+        n = max(L.query("e2e_conv2d_splitk_workspace_floats", b * self.Ho * self.Wo, self.Cout, self.KH * self.KW * self.Cin) for b in {B, 1})
         self.ws_f = torch.zeros(n, device=dev, dtype=_f32) if n else None           # zeroed once: its head holds the stream-K hand-off flags
         self.pp = pad if self.pm == 1 else 0
         self.direct = self.pp == 0 and up == 1 and src1 is None
         if self.need_dx:
-            n = lib.e2e_conv2d_bwd_data_workspace_floats(B, self.Hs + 2 * self.pp, self.Ws + 2 * self.pp, self.Cin, self.KH * self.KW * self.Cout, stride)
+            n = L.query("e2e_conv2d_bwd_data_workspace_floats", geom=self.geom, Hd=self.Hs + 2 * self.pp, Wd=self.Ws + 2 * self.pp, cols=self.Cin,
+                        K=self.KH * self.KW * self.Cout)
             self.ws_b = torch.zeros(n, device=dev, dtype=_f32) if n else None
             self.dxp = None if self.direct else torch.empty(B, self.Hs + 2 * self.pp, self.Ws + 2 * self.pp, self.Cin, device=dev, dtype=_f32)
-        self.ws_w = torch.empty(lib.e2e_conv2d_wgrad_workspace_floats(B, self.Ho, self.Wo, self.Cin, self.Cout, self.KH, self.KW,
-                                                                      1 if bias is not None else 0), device=dev, dtype=_f32)
+        self.ws_w = torch.empty(L.query("e2e_conv2d_wgrad_workspace_floats", geom=self.geom, has_bias=1 if bias is not None else 0), device=dev, dtype=_f32)
         # residual wiring of a BasicBlock (NetPlan.__init__): `res_via` = the block's first convolution, whose backward-data launch
         # adds this layer's gradient to the block input (pre_add) -- no separate accumulate pass; `res_aliased`: the residual tensor
         # has no activation and no other consumer (downsample branch), its gradient buffer IS this layer's
@@ -119,14 +122,14 @@ class _Conv:
     def fwd(self, plan, st, slot=None):
         """slot None: the whole batch; an int: that image of the batch alone (B = 1 launch on the slot's part of every buffer)."""
         s = self
-        L.call("e2e_conv2d_fwd", _at(s.src0.t, slot), _at(s.src1.t, slot) if s.src1 is not None else None, s.C1, s.up, L.ptr(s.wf), s.ldf, L.ptr(s.scale),
-               L.ptr(s.shift if s.bias is None else s.bias), _at(s.res.t, slot) if s.res is not None else None, _at(s.out.t, slot),
-               s.src0.B if slot is None else 1, s.Hs, s.Ws, s.Cin,
-               s.Cout, s.KH, s.KW, s.stride, s.pad, s.pm, s.act, float(s.isub), float(s.imul), L.ptr(s.ws_f), st)
+        L.call("e2e_conv2d_fwd", geom=s.geom, B=s.src0.B if slot is None else 1, src0=_at(s.src0.t, slot),
+               src1=_at(s.src1.t, slot) if s.src1 is not None else None, w_fwd=L.ptr(s.wf), ld_fwd=s.ldf, scale=L.ptr(s.scale),
+               shift=L.ptr(s.shift if s.bias is None else s.bias), residual=_at(s.res.t, slot) if s.res is not None else None,
+               out=_at(s.out.t, slot), act=s.act, workspace=L.ptr(s.ws_f), stream=st)
 
     def bwd(self, plan, st):
         s = self
-        B, n = s.src0.B, s.out.t.numel()
+        n = s.out.t.numel()
         g = s.out.g                                 # d loss / d (pre-activation of this layer)
         if s.res is not None and s.res_via is None and not s.res_aliased:
             # residual branch: its tensor's pre-activation gradient (+)= g * act_res'(.)
@@ -135,11 +138,10 @@ class _Conv:
         if s.need_dx and plan.paired and not plan.overlap:
             # backward-data and backward-weight of this layer as one launch (e2e_conv2d_bwd_pair_deferred: bit-identical to the two calls below)
             pre = s.pre_from.out.g if (s.direct and s.pre_from is not None) else None
-            L.call("e2e_conv2d_bwd_pair_deferred", L.ptr(g), L.ptr(s.wb), s.ldb, L.ptr(s.src0.g if s.direct else s.dxp), B, s.Hs, s.Ws, s.Cin, s.Cout,
-                   s.Ho, s.Wo, s.KH, s.KW, s.stride, s.pad, s.pm, (1 if s.src0.written else 0) if s.direct else 0, L.ptr(s.src0.t) if s.direct else None,
-                   s.src0.act if s.direct else 0, L.ptr(pre), L.ptr(s.ws_b), L.ptr(s.scale), L.ptr(s.src0.t), L.ptr(s.src1.t) if s.src1 is not None else None,
-                   s.C1, s.up, L.ptr(plan.sink(s.weight)), L.ptr(plan.sink(s.bias)) if s.bias is not None else None, L.ptr(s.ws_w), 0, float(s.isub),
-                   float(s.imul), ctypes.byref(s.reduce_desc), PAIR_WGRAD_FIRST, st)
+            L.call("e2e_conv2d_bwd_pair_deferred", geom=s.geom, da=L.ptr(g), w_bwd=L.ptr(s.wb), ld_bwd=s.ldb, dxp=L.ptr(s.src0.g if s.direct else s.dxp),
+                   accumulate=(1 if s.src0.written else 0) if s.direct else 0, x_in=L.ptr(s.src0.t) if s.direct else None,
+                   in_act=s.src0.act if s.direct else 0, pre_add=L.ptr(pre), workspace=L.ptr(s.ws_b), workspace_w=L.ptr(s.ws_w), accumulate_w=0,
+                   wgrad_first=PAIR_WGRAD_FIRST, stream=st, **s._wgrad_operands(plan))
             if s.direct:
                 s.src0.written = True
             else:
@@ -148,26 +150,30 @@ class _Conv:
         if s.need_dx:
             if s.direct:
                 pre = s.pre_from.out.g if s.pre_from is not None else None       # the block's residual gradient: same tensor, same act'
-                L.call("e2e_conv2d_bwd_data_fused", L.ptr(g), L.ptr(s.wb), s.ldb, L.ptr(s.src0.g), B, s.Hs, s.Ws, s.Cin, s.Cout, s.Ho, s.Wo, s.KH, s.KW,
-                       s.stride, s.pad, s.pm, 1 if s.src0.written else 0, L.ptr(s.src0.t), s.src0.act, L.ptr(pre), L.ptr(s.ws_b), st)
+                L.call("e2e_conv2d_bwd_data_fused", geom=s.geom, da=L.ptr(g), w_bwd=L.ptr(s.wb), ld_bwd=s.ldb, dxp=L.ptr(s.src0.g),
+                       accumulate=1 if s.src0.written else 0, x_in=L.ptr(s.src0.t), in_act=s.src0.act, pre_add=L.ptr(pre), workspace=L.ptr(s.ws_b), stream=st)
                 s.src0.written = True
             else:
-                L.call("e2e_conv2d_bwd_data", L.ptr(g), L.ptr(s.wb), s.ldb, L.ptr(s.dxp), B, s.Hs, s.Ws, s.Cin, s.Cout, s.Ho, s.Wo, s.KH, s.KW, s.stride,
-                       s.pad, s.pm, L.ptr(s.ws_b), st)
+                L.call("e2e_conv2d_bwd_data", geom=s.geom, dz=L.ptr(g), w_bwd=L.ptr(s.wb), ld_bwd=s.ldb, dxp=L.ptr(s.dxp), workspace=L.ptr(s.ws_b), stream=st)
                 self._gather_adjoint(st)
         st_w = plan.fork(st)
         # the GEMM leaves its partial slabs in this layer's own workspace; the ~30 slab reductions of a pass are ONE launch at its end
         # (NetPlan._reduce_weight_gradients): each was 5 - 15 us of launch latency on an almost empty GPU
-        L.call("e2e_conv2d_bwd_weight_scaled_deferred", L.ptr(g), L.ptr(s.scale), L.ptr(s.src0.t), L.ptr(s.src1.t) if s.src1 is not None else None, s.C1, s.up,
-               L.ptr(plan.sink(s.weight)), L.ptr(plan.sink(s.bias)) if s.bias is not None else None, L.ptr(s.ws_w), B, s.Hs, s.Ws, s.Cin, s.Cout, s.Ho,
-               s.Wo, s.KH, s.KW, s.stride, s.pad, s.pm, 0, float(s.isub), float(s.imul), ctypes.byref(s.reduce_desc), st_w)
+        L.call("e2e_conv2d_bwd_weight_scaled_deferred", geom=s.geom, da=L.ptr(g), workspace=L.ptr(s.ws_w), accumulate=0, stream=st_w, **s._wgrad_operands(plan))
+
+    def _wgrad_operands(self, plan):
+        """What the two deferred backward-weight forms take under the same names: the layer's sources, its gradient sinks, the descriptor."""
+        s = self
+        return dict(out_scale=L.ptr(s.scale), src0=L.ptr(s.src0.t), src1=L.ptr(s.src1.t) if s.src1 is not None else None, dw=L.ptr(plan.sink(s.weight)),
+                    dbias=L.ptr(plan.sink(s.bias)) if s.bias is not None else None, desc_out_host=ctypes.byref(s.reduce_desc))
 
     def _gather_adjoint(self, st):
         """dxp (the padded / upsampled / concatenated input domain) -> the gradients of the layer's sources."""
         s, s1 = self, self.src1
-        L.call("e2e_conv2d_gather_adjoint_act", L.ptr(s.dxp), s.src0.B, s.Hs, s.Ws, s.Cin, s.C1, s.up, 1 if s.pp else 0, L.ptr(s.src0.g),
-               L.ptr(s1.g) if s1 is not None else None, 1 if s.src0.written else 0, 1 if (s1 is not None and s1.written) else 0,
-               L.ptr(s.src0.t), s.src0.act, L.ptr(s1.t) if s1 is not None else None, s1.act if s1 is not None else 0, st)
+        L.call("e2e_conv2d_gather_adjoint_act", geom=s.geom, dxp=L.ptr(s.dxp), padded=1 if s.pp else 0, d_src0=L.ptr(s.src0.g),
+               d_src1=L.ptr(s1.g) if s1 is not None else None, accumulate0=1 if s.src0.written else 0,
+               accumulate1=1 if (s1 is not None and s1.written) else 0, src0=L.ptr(s.src0.t), act0=s.src0.act,
+               src1=L.ptr(s1.t) if s1 is not None else None, act1=s1.act if s1 is not None else 0, stream=st)
         s.src0.written = True
         if s1 is not None:
             s1.written = True
@@ -191,8 +197,9 @@ class _Head:
         L.call("e2e_conv2d_act_bwd", L.ptr(self.out.g), L.ptr(self.out.t), None, L.ptr(self.dz), n, 1, self.act, st)
         if s.written:
             raise RuntimeError("the disparity head's input has a single consumer")
-        L.call("e2e_head_bwd_act", L.ptr(self.dz), L.ptr(s.t), L.ptr(self.weight), L.ptr(s.g), L.ptr(plan.sink(self.weight)),
-               L.ptr(plan.sink(self.bias)) if self.bias is not None else None, L.ptr(self.ws), s.B, s.h, s.w, s.C, s.act, st)
+        L.call("e2e_head_bwd_act", dz=L.ptr(self.dz), x=L.ptr(s.t), w=L.ptr(self.weight), dx=L.ptr(s.g), dw=L.ptr(plan.sink(self.weight)),
+               dbias=L.ptr(plan.sink(self.bias)) if self.bias is not None else None, workspace=L.ptr(self.ws), B=s.B, H=s.h, W=s.w, Cin=s.C,
+               in_act=s.act, stream=st)
         s.written = True
 
 
@@ -210,8 +217,8 @@ class _MaxPool:
         s = self.src
         if s.act not in (0, ACT["relu"]):
             raise NotImplementedError("launch plan: the max-pool follows a ReLU (ResNet stem)")
-        L.call("e2e_maxpool3x3s2_bwd_idx", L.ptr(s.t), L.ptr(self.argmax), L.ptr(self.out.g), L.ptr(s.g), s.B, s.h, s.w, s.C, 1 if s.written else 0,
-               1 if s.act else 0, st)
+        L.call("e2e_maxpool3x3s2_bwd_idx", x=L.ptr(s.t), argmax=L.ptr(self.argmax), dy=L.ptr(self.out.g), dx=L.ptr(s.g), B=s.B, H=s.h, W=s.w, C=s.C,
+               accumulate=1 if s.written else 0, mul_relu=1 if s.act else 0, stream=st)
         s.written = True
 
 
@@ -235,8 +242,8 @@ class _BNAffine:
     def bwd(self, plan, st):
         b, s = self.bn, self.src
         n = s.t.numel()
-        L.call("e2e_affine_bwd", L.ptr(self.out.g), L.ptr(s.t), L.ptr(b.running_mean), L.ptr(self.rstd), n // s.C, s.C, L.ptr(plan.sink(b.weight)),
-               L.ptr(plan.sink(b.bias)), 0, L.ptr(self.ws), st)
+        L.call("e2e_affine_bwd", dy=L.ptr(self.out.g), z=L.ptr(s.t), mean=L.ptr(b.running_mean), rstd=L.ptr(self.rstd), P=n // s.C, C=s.C,
+               dgamma=L.ptr(plan.sink(b.weight)), dbeta=L.ptr(plan.sink(b.bias)), accumulate=0, workspace=L.ptr(self.ws), stream=st)
         if s.act != 0:
             raise NotImplementedError("launch plan: a trainable BatchNorm follows a plain convolution")
         L.call("e2e_conv2d_act_bwd_acc", L.ptr(self.out.g), L.ptr(self.out.g), L.ptr(self.scale), L.ptr(s.g), n, s.C, 0, 1 if s.written else 0, st)

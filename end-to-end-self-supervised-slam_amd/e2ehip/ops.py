@@ -97,7 +97,8 @@ class _GridSample(torch.autograd.Function):
         inp = L.dev(inp, "input")
         grid = L.dev(grid, "grid").contiguous()
         out = torch.empty(B, C, Ho, Wo, device=inp.device, dtype=torch.float32)
-        L.call("e2e_grid_sample_fwd", L.ptr(inp), L.strides4(inp), L.ptr(grid), L.ptr(out), B, C, Hi, Wi, Ho, Wo, pad, int(align), L.stream())
+        L.call("e2e_grid_sample_fwd", input=L.ptr(inp), in_strides=L.strides4(inp), grid=L.ptr(grid), out=L.ptr(out), B=B, C=C, Hi=Hi, Wi=Wi, Ho=Ho, Wo=Wo,
+               padding_mode=pad, align_corners=int(align), stream=L.stream())
         ctx.save_for_backward(inp, grid)
         ctx.cfg = (pad, int(align))
         return out
@@ -111,14 +112,14 @@ class _GridSample(torch.autograd.Function):
         _, Ho, Wo, _ = grid.shape
         g = g.contiguous()
         gg = torch.empty_like(grid)
+        common = dict(input=L.ptr(inp), in_strides=L.strides4(inp), grid=L.ptr(grid), g_out=L.ptr(g), g_grid=L.ptr(gg), B=B, C=C, Hi=Hi, Wi=Wi, Ho=Ho, Wo=Wo,
+                      padding_mode=pad, align_corners=align, stream=L.stream())
         if ctx.needs_input_grad[0]:      # gradient wrt the sampled image: a scatter -- fixed-point integer accumulation, bitwise reproducible
             gi = torch.empty(B, C, Hi, Wi, device=g.device, dtype=torch.float32)
             fx = torch.empty(B * C * Hi * Wi + 1, device=g.device, dtype=torch.int64)      # + the poison word (non-finite / out-of-range contributions)
-            L.call("e2e_grid_sample_bwd_exact", L.ptr(inp), L.strides4(inp), L.ptr(grid), L.ptr(g), L.ptr(gg), L.ptr(fx), L.ptr(gi),
-                   B, C, Hi, Wi, Ho, Wo, pad, align, L.stream())
+            L.call("e2e_grid_sample_bwd_exact", g_input_fixed=L.ptr(fx), g_input=L.ptr(gi), **common)
             return gi, gg, None, None
-        L.call("e2e_grid_sample_bwd", L.ptr(inp), L.strides4(inp), L.ptr(grid), L.ptr(g), L.ptr(gg), None,
-               B, C, Hi, Wi, Ho, Wo, pad, align, L.stream())
+        L.call("e2e_grid_sample_bwd", g_input=None, **common)
         return None, gg, None, None
 
 
@@ -140,7 +141,8 @@ class _Photometric(torch.autograd.Function):
         x, y = L.dev(x, "prediction"), L.dev(y, "target")
         ssim = torch.empty(B, C, H, W, device=x.device, dtype=torch.float32) if want_ssim else None
         pmap = torch.empty(B, 1, H, W, device=x.device, dtype=torch.float32) if want_pmap else None
-        L.call("e2e_photometric_fwd", L.ptr(x), L.strides4(x), L.ptr(y), L.strides4(y), L.ptr(ssim), L.ptr(pmap), B, C, H, W, L.stream())
+        L.call("e2e_photometric_fwd", x=L.ptr(x), xs=L.strides4(x), y=L.ptr(y), ys=L.strides4(y), ssim_out=L.ptr(ssim), pmap_out=L.ptr(pmap), B=B, C=C, H=H, W=W,
+               stream=L.stream())
         ctx.save_for_backward(x, y)
         return ssim, pmap
 
@@ -156,10 +158,12 @@ class _Photometric(torch.autograd.Function):
             return None, None, None, None
         if ctx.needs_input_grad[0]:
             gx = torch.empty(B, C, H, W, device=x.device, dtype=torch.float32)
-            L.call("e2e_photometric_bwd", L.ptr(x), L.strides4(x), L.ptr(y), L.strides4(y), L.ptr(g_pmap), L.ptr(g_ssim), L.ptr(gx), B, C, H, W, L.stream())
+            L.call("e2e_photometric_bwd", x=L.ptr(x), xs=L.strides4(x), y=L.ptr(y), ys=L.strides4(y), g_pmap=L.ptr(g_pmap), g_ssim=L.ptr(g_ssim), g_x=L.ptr(gx),
+                   B=B, C=C, H=H, W=W, stream=L.stream())
         if ctx.needs_input_grad[1]:
             gy = torch.empty(B, C, H, W, device=x.device, dtype=torch.float32)
-            L.call("e2e_photometric_bwd", L.ptr(y), L.strides4(y), L.ptr(x), L.strides4(x), L.ptr(g_pmap), L.ptr(g_ssim), L.ptr(gy), B, C, H, W, L.stream())
+            L.call("e2e_photometric_bwd", x=L.ptr(y), xs=L.strides4(y), y=L.ptr(x), ys=L.strides4(x), g_pmap=L.ptr(g_pmap), g_ssim=L.ptr(g_ssim), g_x=L.ptr(gy),
+                   B=B, C=C, H=H, W=W, stream=L.stream())       # gradient wrt the target: the operands swapped
         return gx, gy, None, None
 
 
@@ -198,9 +202,10 @@ class _WarpPhotometric(torch.autograd.Function):
         pmap = torch.empty(B, 1, H, W, device=dev, dtype=torch.float32) if want_pmap else None
         loss = torch.zeros(2, device=dev, dtype=torch.float32)
         ws = torch.empty(L.load().e2e_warp_photo_workspace_floats(B, H, W), device=dev, dtype=torch.float32)
-        L.call("e2e_warp_photo_fwd", L.ptr(dt), L.ptr(src), L.strides4(src), L.ptr(tgt), L.strides4(tgt), L.ptr(K), L.ptr(inv_K),
-               L.ptr(T), L.ptr(synth), L.ptr(valid), L.ptr(pmap), int(use_mask), pad, reg_kind, L.ptr(it), L.ptr(is_), L.ptr(ds),
-               L.ptr(loss), L.ptr(ws), B, H, W, L.stream())
+        L.call("e2e_warp_photo_fwd", depth_tgt=L.ptr(dt), src=L.ptr(src), src_strides=L.strides4(src), tgt=L.ptr(tgt), tgt_strides=L.strides4(tgt), K=L.ptr(K),
+               inv_K=L.ptr(inv_K), T=L.ptr(T), synth=L.ptr(synth), valid=L.ptr(valid), pmap=L.ptr(pmap), use_mask=int(use_mask), padding_mode=pad,
+               reg_kind=reg_kind, reg_init_tgt=L.ptr(it), reg_init_src=L.ptr(is_), depth_src=L.ptr(ds), loss_out=L.ptr(loss), workspace=L.ptr(ws),
+               B=B, H=H, W=W, stream=L.stream())
         ctx.save_for_backward(dt, ds, it, is_, src, tgt, K, inv_K, T, synth, valid)
         ctx.cfg = (pad, int(use_mask), reg_kind, B, H, W)
         ctx.mark_non_differentiable(synth, valid)
@@ -217,9 +222,10 @@ class _WarpPhotometric(torch.autograd.Function):
         gl = torch.stack([g0 if g0 is not None else z, g1 if g1 is not None else z]).contiguous()
         gdt = torch.empty(B, 1, H, W, device=dt.device, dtype=torch.float32)
         gds = torch.empty(B, 1, H, W, device=dt.device, dtype=torch.float32) if reg_kind else None
-        L.call("e2e_warp_photo_bwd", L.ptr(dt), L.ptr(src), L.strides4(src), L.ptr(tgt), L.strides4(tgt), L.ptr(K), L.ptr(inv_K),
-               L.ptr(T), L.ptr(synth), L.ptr(valid), use_mask, pad, reg_kind, L.ptr(it), L.ptr(is_), L.ptr(ds), L.ptr(gl),
-               L.ptr(gdt), L.ptr(gds), B, H, W, L.stream())
+        L.call("e2e_warp_photo_bwd", depth_tgt=L.ptr(dt), src=L.ptr(src), src_strides=L.strides4(src), tgt=L.ptr(tgt), tgt_strides=L.strides4(tgt), K=L.ptr(K),
+               inv_K=L.ptr(inv_K), T=L.ptr(T), synth=L.ptr(synth), valid=L.ptr(valid), use_mask=use_mask, padding_mode=pad, reg_kind=reg_kind,
+               reg_init_tgt=L.ptr(it), reg_init_src=L.ptr(is_), depth_src=L.ptr(ds), g_loss=L.ptr(gl), g_depth_tgt=L.ptr(gdt), g_depth_src=L.ptr(gds),
+               B=B, H=H, W=W, stream=L.stream())
         return (gdt, gds) + (None,) * 11
 
 
@@ -266,8 +272,8 @@ class _VertexMaps(torch.autograd.Function):
         f = dict(device=d.device, dtype=torch.float32)
         V, Nm, Vg, Ng = (torch.empty(B, H, W, 3, **f) for _ in range(4))
         alpha = torch.empty(B, H, W, **f)
-        L.call("e2e_vertex_normal_maps", L.ptr(d), L.ptr(K), L.ptr(pose), float(alpha_den), L.ptr(V), L.ptr(Nm), L.ptr(Vg), L.ptr(Ng),
-               L.ptr(alpha), B, H, W, L.stream())
+        L.call("e2e_vertex_normal_maps", depth=L.ptr(d), K=L.ptr(K), pose=L.ptr(pose), alpha_den=float(alpha_den), V=L.ptr(V), Nm=L.ptr(Nm), Vg=L.ptr(Vg),
+               Ng=L.ptr(Ng), alpha=L.ptr(alpha), B=B, H=H, W=W, stream=L.stream())
         ctx.save_for_backward(d, K, pose)
         ctx.mark_non_differentiable(Nm, Ng, alpha)
         return V, Nm, Vg, Ng, alpha
@@ -581,7 +587,8 @@ class _Smoothness(torch.autograd.Function):
             raise ValueError(f"disp {tuple(d.shape)} does not match img {tuple(im.shape)}")
         out = torch.empty(2, device=d.device, dtype=torch.float32)
         g = torch.empty_like(d) if ctx.needs_input_grad[0] else None
-        L.call("e2e_smoothness_lossgrad", L.ptr(d), L.ptr(im), L.strides4(im), B, C, H, W, L.ptr(out), L.ptr(g), L.ptr(_aux_ws(d.device)), L.stream())
+        L.call("e2e_smoothness_lossgrad", disp=L.ptr(d), img=L.ptr(im), img_strides=L.strides4(im), B=B, C=C, H=H, W=W, loss_out=L.ptr(out), g_disp=L.ptr(g),
+               workspace=L.ptr(_aux_ws(d.device)), stream=L.stream())
         ctx.save_for_backward(g)
         return out[0] + out[1]
 

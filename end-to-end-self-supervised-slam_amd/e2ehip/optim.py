@@ -225,5 +225,6 @@ class FusedAdam(torch.optim.Optimizer):
         # the bucket holds the SUM over the data-parallel ranks and its tail the number of contributors (1 on a single GPU);
         # step count and bias corrections are device-resident, so this launch can be captured into a hipGraph and replayed
         sched, counter = self._resident_state()
-        L.call("e2e_adam_step_resident", L.ptr(self.flat.data), L.ptr(self.flat.grad), L.ptr(self.flat.participants()), L.ptr(self.m), L.ptr(self.v),
-               self.flat.numel, float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), L.ptr(sched), self.SCHEDULE_LEN, L.ptr(counter), L.stream())
+        L.call("e2e_adam_step_resident", params=L.ptr(self.flat.data), grad_sums=L.ptr(self.flat.grad), participants=L.ptr(self.flat.participants()),
+               exp_avg=L.ptr(self.m), exp_avg_sq=L.ptr(self.v), n=self.flat.numel, beta1=float(g["betas"][0]), beta2=float(g["betas"][1]),
+               eps=float(g["eps"]), schedule=L.ptr(sched), schedule_len=self.SCHEDULE_LEN, step_counter=L.ptr(counter), stream=L.stream())

@@ -15,60 +15,53 @@ import torch
 from . import _lib as L
 
 
+_CONV = ("e2e_conv2d_fwd", "e2e_conv2d_bwd_data", "e2e_conv2d_bwd_data_acc", "e2e_conv2d_bwd_data_fused", "e2e_conv2d_bwd_weight",
+         "e2e_conv2d_bwd_weight_scaled", "e2e_conv2d_bwd_weight_scaled_deferred")
+_WARP = ("e2e_warp_photo_lossgrad_hostgeo", "e2e_warp_photo_lossgrad", "e2e_warp_photo_lossgrad_chain")
+
+
+def _named(name, a):
+    """The argument vector of one call as {parameter name of include/e2eslam.h: value}."""
+    return dict(zip(L.PARAMS[name], a))
+
+
+def _conv_geometry(name, a):
+    """(B, Hs, Ws, Cin, Cout, Ho, Wo, KH, KW) of one convolution GEMM call, or None for any other entry point."""
+    if name not in _CONV:
+        return None
+    p = _named(name, a)
+    if "Ho" not in p:                                   # the forward takes no output size
+        p["Ho"], p["Wo"] = (p["Hs"] + 2 * p["pad"] - p["KH"]) // p["stride"] + 1, (p["Ws"] + 2 * p["pad"] - p["KW"]) // p["stride"] + 1
+    return tuple(p[k] for k in ("B", "Hs", "Ws", "Cin", "Cout", "Ho", "Wo", "KH", "KW"))
+
+
 def _conv_flops(name, a):
     """Algorithmic FLOPs of one convolution GEMM call from its argument list (2 x pixels x Cout x Cin x KH x KW)."""
-    if name == "e2e_conv2d_fwd":
-        B, Hs, Ws, Cin, Cout, KH, KW, stride, pad = a[10:19]
-        Ho, Wo = (Hs + 2 * pad - KH) // stride + 1, (Ws + 2 * pad - KW) // stride + 1
-        return 2.0 * B * Ho * Wo * Cout * Cin * KH * KW
-    if name in ("e2e_conv2d_bwd_data", "e2e_conv2d_bwd_data_acc", "e2e_conv2d_bwd_data_fused"):
-        B, Hs, Ws, Cin, Cout, Ho, Wo, KH, KW = a[4:13]
-        return 2.0 * B * Ho * Wo * Cout * Cin * KH * KW
-    if name == "e2e_conv2d_bwd_weight":
-        B, Hs, Ws, Cin, Cout, Ho, Wo, KH, KW = a[8:17]
-        return 2.0 * B * Ho * Wo * Cout * Cin * KH * KW
-    if name in ("e2e_conv2d_bwd_weight_scaled", "e2e_conv2d_bwd_weight_scaled_deferred"):
-        B, Hs, Ws, Cin, Cout, Ho, Wo, KH, KW = a[9:18]
-        return 2.0 * B * Ho * Wo * Cout * Cin * KH * KW
-    return 0.0
+    g = _conv_geometry(name, a)
+    if g is None:
+        return 0.0
+    B, Hs, Ws, Cin, Cout, Ho, Wo, KH, KW = g
+    return 2.0 * B * Ho * Wo * Cout * Cin * KH * KW
 
 
 def _conv_bytes(name, a):
     """Algorithmic (compulsory) HBM bytes of one convolution call: every operand once -- the gathered input domain, the weights, the
     result -- in fp32.  (An upsampled / concatenated input counts with its gather domain B x Hs x Ws x Cin: an upper bound of what has to
     be read; the backward-weight form reads dZ and the input and writes dW.)"""
-    if name == "e2e_conv2d_fwd":
-        B, Hs, Ws, Cin, Cout, KH, KW, stride, pad = a[10:19]
-        Ho, Wo = (Hs + 2 * pad - KH) // stride + 1, (Ws + 2 * pad - KW) // stride + 1
-    elif name in ("e2e_conv2d_bwd_data", "e2e_conv2d_bwd_data_acc", "e2e_conv2d_bwd_data_fused"):
-        B, Hs, Ws, Cin, Cout, Ho, Wo, KH, KW = a[4:13]
-    elif name == "e2e_conv2d_bwd_weight":
-        B, Hs, Ws, Cin, Cout, Ho, Wo, KH, KW = a[8:17]
-    elif name in ("e2e_conv2d_bwd_weight_scaled", "e2e_conv2d_bwd_weight_scaled_deferred"):
-        B, Hs, Ws, Cin, Cout, Ho, Wo, KH, KW = a[9:18]
-    else:
+    g = _conv_geometry(name, a)
+    if g is None:
         return 0
+    B, Hs, Ws, Cin, Cout, Ho, Wo, KH, KW = g
     return 4 * (B * Hs * Ws * Cin + Cout * Cin * KH * KW + B * Ho * Wo * Cout)
 
 
 def _warp_bytes(name, a):
     """Algorithmic HBM bytes of one fused warp + photometric (+ regulariser) loss-and-gradient launch:
     reads depth 4N + src 12N + tgt 12N (+ init_t, init_s, depth_s 12N), writes g_tgt 4N (+ g_src 4N)."""
-    if name == "e2e_warp_photo_lossgrad_hostgeo":
-        reg, H, W = a[8], a[18], a[19]
-        return (32 + (16 if reg else 0)) * H * W
-    if name == "e2e_warp_photo_lossgrad":
-        reg, B, H, W = a[10], a[20], a[21], a[22]
-        return (32 + (16 if reg else 0)) * B * H * W
-    if name == "e2e_warp_photo_lossgrad_chain":
-        reg, B, H, W = a[11], a[23], a[24], a[25]
-        return (32 + (16 if reg else 0)) * B * H * W
-    return 0
-
-
-def _stream_of(arg):
-    v = arg.value if isinstance(arg, ctypes.c_void_p) else arg
-    return int(v or 0)
+    if name not in _WARP:
+        return 0
+    p = _named(name, a)
+    return (32 + (16 if p["reg_kind"] else 0)) * p.get("B", 1) * p["H"] * p["W"]
 
 
 class KernelTimer:
@@ -91,12 +84,12 @@ class KernelTimer:
         return s
 
     def around(self, name, args, fn):
-        s = self._stream(_stream_of(args[-1]))
+        plain = [a.value if isinstance(a, ctypes.c_void_p) else a for a in args]
+        s = self._stream(int(_named(name, plain).get("stream") or 0))
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record(s)
         rc = fn()
         e1.record(s)
-        plain = [a.value if isinstance(a, ctypes.c_void_p) else a for a in args]
         self.rows.append((name, e0, e1, _conv_flops(name, plain), _warp_bytes(name, plain) + _conv_bytes(name, plain)))
         return rc
 

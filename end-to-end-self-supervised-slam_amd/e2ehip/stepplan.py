@@ -171,8 +171,8 @@ class RefineStepPlan:
         (reference quirk), pulled to its nearest neighbours in the detached global map."""
         st, N = L.stream(), self.N
         d = self.depth[1:2]
-        L.call("e2e_vertex_normal_maps", L.ptr(d), L.ptr(self.K), L.ptr(self.pose_tgt), float(self.alpha_den), L.ptr(self.V), L.ptr(self.Nm), L.ptr(self.Vg),
-               L.ptr(self.Ng), L.ptr(self.alpha), 1, self.H, self.W, st)
+        L.call("e2e_vertex_normal_maps", depth=L.ptr(d), K=L.ptr(self.K), pose=L.ptr(self.pose_tgt), alpha_den=float(self.alpha_den), V=L.ptr(self.V),
+               Nm=L.ptr(self.Nm), Vg=L.ptr(self.Vg), Ng=L.ptr(self.Ng), alpha=L.ptr(self.alpha), B=1, H=self.H, W=self.W, stream=st)
         L.call("e2e_transform_points", L.ptr(self.Vg), L.ptr(self.T), L.ptr(self.moved), N, 0, st)
         # the previous query's neighbours bound the search from the start: steps 2 and 3 of a keyframe ask about the same pixels against the
         # same map; the FIRST step of a keyframe inherits the last answers of the keyframe before (a neighbouring view: the same pixel looks at

@@ -16,6 +16,12 @@
  *    reference's NHWC frame stack (online_adaption.py:215-220) and its permuted NCHW views
  *    (online_adaption.py:393-394) are read in place, without a layout copy;
  *  - results are deterministic run to run: no floating-point atomics on any parity output.
+ *
+ * This file IS the Python binding (e2ehip/_lib.py parses it when it loads the library).  Grammar it accepts: every prototype is
+ * `ret e2e_name(type name, ...);` or `ret e2e_name(void);` with ret one of int, int64_t, long long, const char*, and each parameter an
+ * int, int64_t, long long, float, double, an e2e_strides by value or a pointer (any pointee, optionally const), always with a name;
+ * structs are `typedef struct tag { fields } tag;` over the same types.  Parameter names are what the package's keyword calls bind to
+ * (L.call(name, Hs=..., stream=...)) and what e2ehip/profile.py accounts by, so renaming one is a change to the package.
  */
 #ifndef E2ESLAM_H
 #define E2ESLAM_H
