@@ -60,7 +60,7 @@ __global__ __launch_bounds__(64) void k_icp_final(const double* __restrict__ par
 // damping update and the pose composition in float64 by one thread, so that the numiters iterations of a keyframe's odometry are a
 // fixed launch sequence with no host round trip (round 3: one 232-byte read-back + np.linalg.solve + upload per reduction, 40 per
 // keyframe, 9.4 ms per refinement step).  Same arithmetic as oracle/icp.py: LU with partial pivoting (what numpy's solve calls),
-// Rodrigues + the V matrix with the small-angle branch below 1e-8.
+// Rodrigues + the V matrix, their three coefficients from the power series below an angle of 1e-2 (there 1 - cos and th - sin cancel).
 // state (float64): [0..15] T (row-major), [16..21] xi, [22] lambda, [23] err/cnt of the first reduction, [24] stopped, [25] iterations
 // done, [26] damp, [32 + 2k], [33 + 2k]: (inlier count, sum r^2) of iteration k (trace, up to ICP_TRACE iterations)
 // ---------------------------------------------------------------------------------------------
@@ -75,7 +75,10 @@ __device__ void icp_se3_exp(const double* xi, double* T) {
     for (int r = 0; r < 3; ++r)
         for (int c = 0; c < 3; ++c) W2[r * 3 + c] = W[r * 3] * W[c] + W[r * 3 + 1] * W[3 + c] + W[r * 3 + 2] * W[6 + c];
     double a, b, c2;       // R = I + a W + b W^2 ; V = I + b W + c2 W^2
-    if (th < 1e-8) { a = 1.0; b = 0.5; c2 = 1.0 / 6.0; }
+    const double t2 = th * th;
+    // below 1e-2 the closed forms lose what 1 - cos(th) and th - sin(th) cancel (all of b and c2 at th ~ 1e-8); the series, cut after
+    // th^4, is then exact to th^6 / 5040 < 2e-16
+    if (th < 1e-2) { a = 1.0 - t2 / 6.0 * (1.0 - t2 / 20.0); b = 0.5 - t2 / 24.0 * (1.0 - t2 / 30.0); c2 = 1.0 / 6.0 - t2 / 120.0 * (1.0 - t2 / 42.0); }
     else { a = sin(th) / th; b = (1.0 - cos(th)) / (th * th); c2 = (th - sin(th)) / (th * th * th); }
     double V[9];
     for (int i = 0; i < 9; ++i) {

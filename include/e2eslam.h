@@ -714,7 +714,9 @@ int e2e_icp_normal_equations(const float* src, const float* tgt, const float* tg
  * mode 1 "gradicp": phase 0 = solve, step32 <- exp(xi), remember err / cnt;  phase 1 (out29 = the reduction at the trial pose):
  *                   delta = err' / cnt' - err / cnt ; lambda *= 1/lmax + (lmax - 1/lmax) / (1 + B exp(-B2 nu delta)) ;
  *                   T <- exp(xi / (1 + exp(clip(nu delta, +-60)))) T.
- * Fewer than 6 inliers stop the iteration for good (later updates leave T alone), as the host loop's `break`. */
+ * Fewer than 6 inliers stop the iteration for good (later updates leave T alone), as the host loop's `break`.
+ * exp is Rodrigues' formula and the V matrix; below an angle of 1e-2 their coefficients come from the power series (the closed forms
+ * cancel there), so exp(xi) is within 2e-14 max(1, |v|) of the true exponential at every angle (tests/test_icp_ref.py). */
 int64_t e2e_icp_state_doubles(void);
 int e2e_icp_state_init(double* state, float* T32, float* step32, const float* prev_pose, float* pose_out,
                        double damp, void* stream);

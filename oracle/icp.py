@@ -30,12 +30,14 @@ def se3_exp(xi):
     v, w = np.asarray(xi[:3], np.float64), np.asarray(xi[3:], np.float64)
     th = np.linalg.norm(w)
     W = so3_hat(w)
-    if th < 1e-8:
-        R = np.eye(3) + W + 0.5 * W @ W
-        V = np.eye(3) + 0.5 * W + W @ W / 6.0
+    t2 = th * th
+    # below 1e-2 the closed forms lose what 1 - cos(th) and th - sin(th) cancel (all of b and c2 at th ~ 1e-8); the series, cut after
+    # th^4, is then exact to th^6 / 5040 < 2e-16
+    if th < 1e-2:
+        a, b, c2 = 1.0 - t2 / 6.0 * (1.0 - t2 / 20.0), 0.5 - t2 / 24.0 * (1.0 - t2 / 30.0), 1.0 / 6.0 - t2 / 120.0 * (1.0 - t2 / 42.0)
     else:
-        R = np.eye(3) + np.sin(th) / th * W + (1 - np.cos(th)) / th ** 2 * W @ W
-        V = np.eye(3) + (1 - np.cos(th)) / th ** 2 * W + (th - np.sin(th)) / th ** 3 * W @ W
+        a, b, c2 = np.sin(th) / th, (1.0 - np.cos(th)) / (th * th), (th - np.sin(th)) / (th * th * th)
+    R, V = np.eye(3) + a * W + b * W @ W, np.eye(3) + b * W + c2 * W @ W       # R = I + a W + b W^2 ; V = I + b W + c2 W^2
     T = np.eye(4)
     T[:3, :3] = R
     T[:3, 3] = V @ v

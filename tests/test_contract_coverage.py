@@ -1,5 +1,6 @@
 """Host-only: every entry point that include/e2eslam.h declares and csrc/depth_ops.hip, aux_losses.hip or nn_misc.hip implements is
-called by one of the two contract modules (tests/test_gpu_depth_aux_contracts.py, tests/test_gpu_nn_misc_contracts.py)."""
+called by one of the two contract modules (tests/test_gpu_depth_aux_contracts.py, tests/test_gpu_nn_misc_contracts.py); the same for
+csrc/icp.hip and tests/test_gpu_icp_contracts.py."""
 import os
 import re
 
@@ -22,4 +23,17 @@ def test_every_entry_point_of_the_three_files_has_a_contract_case():
     assert implemented <= declared, sorted(implemented - declared)
     tests = _read(ROOT, "tests", "test_gpu_depth_aux_contracts.py") + _read(ROOT, "tests", "test_gpu_nn_misc_contracts.py")
     called = set(re.findall(r"[\"'.](e2e_\w+)[\"'(]", tests))
+    assert not names - called, f"no contract case calls {sorted(names - called)}"
+
+
+def test_every_entry_point_of_the_icp_file_has_a_contract_case():
+    """csrc/icp.hip's entry points, and e2e_pf_active_subsample_dev of csrc/pointfusion.hip (the odometry's target selection), are all
+    called by tests/test_gpu_icp_contracts.py."""
+    declared = set(re.findall(r"^(?:int|int64_t|long long)\s+(e2e_\w+)\s*\(", _read(ROOT, "include", "e2eslam.h"), re.M))
+    implemented = set(re.findall(r"^(?:int|int64_t|long long)\s+(e2e_\w+)\s*\(", _read(CSRC, "icp.hip"), re.M))
+    names = (declared & implemented) | {"e2e_pf_active_subsample_dev"}
+    assert len(names) >= 8, sorted(names)                                 # 7 + 1 at the time of writing: the greps still find them
+    assert implemented <= declared, sorted(implemented - declared)
+    assert "e2e_pf_active_subsample_dev" in declared
+    called = set(re.findall(r"[\"'.](e2e_\w+)[\"'(]", _read(ROOT, "tests", "test_gpu_icp_contracts.py")))
     assert not names - called, f"no contract case calls {sorted(names - called)}"

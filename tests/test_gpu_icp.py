@@ -68,6 +68,39 @@ def test_resident_odometry_equals_host_loop_and_oracle(mode):
         odo.check()
 
 
+DIST_THRESH = 0.055        # metres: see test_resident_odometry_with_a_distance_threshold
+
+
+@pytest.mark.parametrize("mode", ["icp", "gradicp"])
+def test_resident_odometry_with_a_distance_threshold(mode):
+    """dist_thresh on the resident path (e2e_icp_reduce_update's `dists` argument, never set by any other test): ResidentOdometry against
+    the host-driven loop of the same search and kernels -- same inlier count in every iteration, pose within 2e-6 -- and against the CPU
+    oracle within 2e-5.  The threshold is chosen on the oracle so that it bites (asserted below: the first iteration keeps 30 % .. 90 %
+    of the sources) and so that no source comes closer than 1.5e-5 m to it in any iteration of either mode: the three paths' poses
+    differ by 1e-6 at most, so they classify every source alike."""
+    from e2ehip import icp
+    from e2ehip.fusionmap import FusionMap
+    colors, depths, K, poses = _scene()
+    H, W = depths.shape[1:]
+    st, _ = opf.pointfusion_step(opf.empty_state(), colors[0], depths[0], K, poses[0])
+    P_ref, tr_ref = oicp.frame_to_model(st["points"], st["normals"], depths[1], K, poses[0], mode=mode, dist_thresh=DIST_THRESH)
+    n_src = ((H + 3) // 4) * ((W + 3) // 4)
+    assert 0.3 * n_src <= tr_ref[0][0] <= 0.9 * n_src and len(tr_ref) == 20
+    _, tr_all = oicp.frame_to_model(st["points"], st["normals"], depths[1], K, poses[0], mode=mode)
+    assert tr_ref[-1][0] < tr_all[-1][0]                                        # it still drops sources at the converged pose
+    fm = FusionMap(3 * H * W, H, W, DEV)
+    fm.load_state(st["points"].to(DEV), st["normals"].to(DEV), st["colors"].to(DEV), st["ccounts"].to(DEV))
+    d1, Kd, p0 = depths[1].to(DEV).contiguous(), K.to(DEV).contiguous(), poses[0].to(DEV).contiguous()
+    P_host, tr_host = icp.frame_to_model(fm, d1, Kd, p0, mode=mode, dist_thresh=DIST_THRESH)
+    odo = icp.ResidentOdometry(fm, dsratio=4, numiters=20, mode=mode, dist_thresh=DIST_THRESH)
+    P = odo.run(d1, Kd, p0).clone()
+    its, tr, _, _ = odo.check()
+    assert its == len(tr_host) == len(tr_ref)
+    assert [c for c, _ in tr] == [c for c, _ in tr_host] == [c for c, _ in tr_ref]
+    np.testing.assert_allclose(P.cpu().numpy(), P_host.cpu().numpy(), atol=2e-6, rtol=0)
+    np.testing.assert_allclose(P.cpu().numpy(), P_ref, atol=2e-5, rtol=0)
+
+
 def test_driver_gradicp_runs_resident_and_reports_ate():
     """configs/config.yaml:30 (odom: gradicp) through the driver's launch plan: the map step with odometry is one captured graph
     (RefineStepPlan.update_map(odometry=...)); the estimated poses stay on the device until the trajectory error is asked for."""
