@@ -1648,16 +1648,32 @@ struct PairGrid {
     unsigned wgx, wgy, wgz;    // the backward-weight tile set
     unsigned first;            // workgroups of the first part, a multiple of 8
     int wgrad_first;           // 1: the backward-weight tiles form the first part
+    unsigned cbeg, cpad;       // the carry part: block ids [cbeg, cbeg + cpad), cpad a multiple of 8 unless the part ends the grid (0: none)
 };
+// Slab reductions of layers whose backward-weight GEMMs ran in EARLIER launches (e2e_conv2d_bwd_pair_carry): items [first, first + items)
+// of a prepared descriptor table, shared out over `wgs` workgroups of the carry part.
+struct CarryArgs { const e2e_wgrad_reduce_desc* d; int n; unsigned wgs; long long first, items; };
+template <int NW>
+__device__ __forceinline__ void wgrad_reduce_item(const e2e_wgrad_reduce_desc* __restrict__ d, int n, long long item, f4v (*part)[64]);
 
 template <int DWM, int DWN, bool TWO>
-__global__ __launch_bounds__(256) void k_conv_bwd_pair(ConvArgs d, WgradArgs w, PairGrid pg) {
+__global__ __launch_bounds__(256) void k_conv_bwd_pair(ConvArgs d, WgradArgs w, PairGrid pg, CarryArgs c) {
     using DL = ConvGemmLds<DWM, DWN, 1, 1, 4, 32>;
     using WL = WgradGemm4Lds<2, 2, 32>;
-    static_assert(64 * DWM * DWN == 256, "both parts run 256 threads");
-    __shared__ union { DL d; WL w; } lds;
-    const bool in_first = blockIdx.x < pg.first;
-    const unsigned l = in_first ? blockIdx.x : blockIdx.x - pg.first;
+    static_assert(64 * DWM * DWN == 256, "all parts run 256 threads");
+    __shared__ union { DL d; WL w; float part[8 * 64 * 4]; } lds;
+    unsigned b = blockIdx.x;                                     // the id this workgroup has in a grid without the carry part
+    if (b >= pg.cbeg) {
+        const unsigned ci = b - pg.cbeg;
+        if (ci < pg.cpad) {
+            if (ci < c.wgs)
+                for (long long item = c.first + ci; item < c.first + c.items; item += c.wgs) wgrad_reduce_item<4>(c.d, c.n, item, reinterpret_cast<f4v(*)[64]>(lds.part));
+            return;
+        }
+        b -= pg.cpad;
+    }
+    const bool in_first = b < pg.first;
+    const unsigned l = in_first ? b : b - pg.first;
     if (in_first == (pg.wgrad_first != 0)) {
         if (l >= pg.wgx * pg.wgy * pg.wgz) return;           // the padding of the first part
         wgrad_gemm4_body<2, 2, 32, TWO>(w, PartIds{l, pg.wgx, pg.wgy, pg.wgz}, lds.w.As, lds.w.Bs);
@@ -2154,9 +2170,10 @@ __global__ __launch_bounds__(TAP_NT) void k_wgrad3x3_taps(TapWgradArgs a) {
 // to the sum (the folded BatchNorm scale, when the GEMM ran on dA instead of dZ = dA * scale).  Measured alone on this network's
 // shapes (scratch/reduce_bench.hip): 4-8 us against 8-11 us for the scalar-load form on the many-slab layers, equal on the
 // few-slab ones (17 us at 512x512x3x3, where the 9.4 MB scatter dominates).
-// one group of 64 quads: lane e of wave w (of ZL) -- `part` is the group's [ZL][64] LDS scratch; every thread of the workgroup calls this the same
-// number of times (two barriers inside)
-template <int ZL>
+// one group of 64 quads: lane e of wave w (of the NW waves that share the group) -- `part` is the group's [ZL][64] LDS scratch; every thread of
+// the workgroup calls this the same number of times (two barriers inside).  The sum has ZL roles (role r adds the slabs z = r, r + ZL, ...);
+// wave w runs the roles w, w + NW, ... one after the other, each into its own part[role] row, so the result does not depend on NW.
+template <int ZL, int NW>
 __device__ __forceinline__ void wgrad_reduce_group(const float* __restrict__ slabs, int S, int Mpad, int Npad, int Cout, int Cin, int KH, int KW, int has_bias,
                                                    float* __restrict__ dw, float* __restrict__ dbias, int accumulate, const float* __restrict__ scale,
                                                    int64_t base, int e, int w, f4v (*part)[64]) {
@@ -2169,17 +2186,22 @@ __device__ __forceinline__ void wgrad_reduce_group(const float* __restrict__ sla
     const bool on = q < totalq;
     const int m = on ? (int)(q / nq) : 0, n = on ? (int)(q - (int64_t)m * nq) * 4 : 0;
     const f4v* src = (const f4v*)(slabs + (int64_t)m * Npad + n);
-    f4v sacc = zero;
-    int z = w;
-    for (; z + 3 * ZL < S; z += 4 * ZL) {
-        f4v v[4];
+    static_assert(ZL % NW == 0, "every wave runs the same number of roles");
 #pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = on ? src[(int64_t)(z + ZL * j) * slab_q] : zero;
+    for (int r = 0; r < ZL / NW; ++r) {
+        const int role = w + r * NW;
+        f4v sacc = zero;
+        int z = role;
+        for (; z + 3 * ZL < S; z += 4 * ZL) {
+            f4v v[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) sacc += v[j];
+            for (int j = 0; j < 4; ++j) v[j] = on ? src[(int64_t)(z + ZL * j) * slab_q] : zero;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) sacc += v[j];
+        }
+        for (; z < S; z += ZL) sacc += on ? src[(int64_t)z * slab_q] : zero;
+        part[role][e] = sacc;
     }
-    for (; z < S; z += ZL) sacc += on ? src[(int64_t)z * slab_q] : zero;
-    part[w][e] = sacc;
     __syncthreads();
     if (w == 0 && on) {
         f4v t = part[0][e];
@@ -2209,7 +2231,7 @@ __global__ __launch_bounds__(64 * ZL) void k_wgrad_reduce(const float* __restric
     __shared__ f4v part[ZL][64];
     const int64_t totalq = (int64_t)Cout * ((KH * KW * Cin + (has_bias ? 1 : 0) + 3) / 4);
     for (int64_t base = (int64_t)blockIdx.x * 64; base < totalq; base += (int64_t)gridDim.x * 64)
-        wgrad_reduce_group<ZL>(slabs, S, Mpad, Npad, Cout, Cin, KH, KW, has_bias, dw, dbias, accumulate, scale, base, threadIdx.x & 63, threadIdx.x >> 6, part);
+        wgrad_reduce_group<ZL, ZL>(slabs, S, Mpad, Npad, Cout, Cin, KH, KW, has_bias, dw, dbias, accumulate, scale, base, threadIdx.x & 63, threadIdx.x >> 6, part);
 }
 
 // The slab reductions of MANY layers in one launch (e2e_wgrad_reduce_batched): a backward pass of the depth network ends ~30 backward-weight GEMMs
@@ -2217,23 +2239,33 @@ __global__ __launch_bounds__(64 * ZL) void k_wgrad_reduce(const float* __restric
 // a 4.9 ms step.  Deferred to the end of the pass they are one grid that fills the chip.  A work item is one workgroup-load of a layer's quads:
 // 64 quads shared by 8 waves (zl = 8, layers with >= 8 slabs) or 4 x 64 quads by 2 waves each (zl = 2), i.e. the SAME association of the sum as
 // the per-layer launch -- the results are bit-identical to e2e_conv2d_bwd_weight_scaled.
-__global__ __launch_bounds__(512) void k_wgrad_reduce_batched(const e2e_wgrad_reduce_desc* __restrict__ d, int n, long long total_items) {
-    __shared__ f4v part[8][64];
+// one work item of a prepared descriptor table on a workgroup of NW waves (8: k_wgrad_reduce_batched; 4: the carry part of k_conv_bwd_pair, where
+// a wave runs two roles of a zl = 8 sum and the four groups of a zl = 2 item take two rounds of two) -- `part` is [8][64]
+template <int NW>
+__device__ __forceinline__ void wgrad_reduce_item(const e2e_wgrad_reduce_desc* __restrict__ d, int n, long long item, f4v (*part)[64]) {
+    static_assert(NW == 8 || NW == 4, "512 or 256 threads");
     const int e = threadIdx.x & 63, w = threadIdx.x >> 6;
-    for (long long item = blockIdx.x; item < total_items; item += gridDim.x) {
-        int lo = 0, hi = n - 1;                                   // last descriptor whose first_item <= item (workgroup-uniform)
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (d[mid].first_item <= item) lo = mid; else hi = mid - 1;
-        }
-        const e2e_wgrad_reduce_desc D = d[lo];
-        const long long local = item - D.first_item;
-        if (D.zl == 8)
-            wgrad_reduce_group<8>(D.slabs, D.S, D.Mpad, D.Npad, D.Cout, D.Cin, D.KH, D.KW, D.has_bias, D.dw, D.dbias, D.accumulate, D.scale, local * 64, e, w, part);
-        else
-            wgrad_reduce_group<2>(D.slabs, D.S, D.Mpad, D.Npad, D.Cout, D.Cin, D.KH, D.KW, D.has_bias, D.dw, D.dbias, D.accumulate, D.scale,
-                                  (local * 4 + (w >> 1)) * 64, e, w & 1, part + 2 * (w >> 1));
+    int lo = 0, hi = n - 1;                                       // last descriptor whose first_item <= item (workgroup-uniform)
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (d[mid].first_item <= item) lo = mid; else hi = mid - 1;
     }
+    const e2e_wgrad_reduce_desc D = d[lo];
+    const long long local = item - D.first_item;
+    if (D.zl == 8) {
+        wgrad_reduce_group<8, NW>(D.slabs, D.S, D.Mpad, D.Npad, D.Cout, D.Cin, D.KH, D.KW, D.has_bias, D.dw, D.dbias, D.accumulate, D.scale, local * 64, e, w, part);
+    } else {
+        constexpr int G = NW / 2;                                 // groups of 2 waves at work at a time
+#pragma unroll
+        for (int r = 0; r < 4 / G; ++r)
+            wgrad_reduce_group<2, 2>(D.slabs, D.S, D.Mpad, D.Npad, D.Cout, D.Cin, D.KH, D.KW, D.has_bias, D.dw, D.dbias, D.accumulate, D.scale,
+                                     (local * 4 + r * G + (w >> 1)) * 64, e, w & 1, part + 2 * (w >> 1));
+    }
+}
+
+__global__ __launch_bounds__(512) void k_wgrad_reduce_batched(const e2e_wgrad_reduce_desc* __restrict__ d, int n, long long first_item, long long items) {
+    __shared__ f4v part[8][64];
+    for (long long item = first_item + blockIdx.x; item < first_item + items; item += gridDim.x) wgrad_reduce_item<8>(d, n, item, part);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -3030,7 +3062,8 @@ int e2e_conv2d_fwd_tuned(const float* src0, const float* src1, int C1, int up, c
 
 // backward-data up to its GEMM: checks the arguments, serves the 16 -> 16 reflection-padded layer with its patch kernel (*done = true), or
 // fills the GEMM's ConvArgs (and zeroes the classes a 1x1 stride-2 kernel does not reach).  Shared by bwd_data_impl and the paired backward.
-static int bwd_data_setup(const BwdDataOps& d, const ConvGeom& g, GemmCfg force, hipStream_t stream, ConvArgs& a, bool& done) {
+// dry: decide only, launch nothing (e2e_conv2d_bwd_pair_is_one_launch).
+static int bwd_data_setup(const BwdDataOps& d, const ConvGeom& g, GemmCfg force, hipStream_t stream, ConvArgs& a, bool& done, bool dry = false) {
     const int B = g.B, Hs = g.Hs, Ws = g.Ws, Cin = g.Cin, Cout = g.Cout, Ho = g.Ho, Wo = g.Wo, KH = g.KH, KW = g.KW, stride = g.stride, pad = g.pad;
     const int pad_mode = g.pad_mode, ld_bwd = d.ld_bwd;
     done = false;
@@ -3044,7 +3077,7 @@ static int bwd_data_setup(const BwdDataOps& d, const ConvGeom& g, GemmCfg force,
     // 16 -> 16 channels on the padded grid of a reflection-padded layer (upconv(0,1)): dXp[q] = sum_t dZ[q - t] Wb[t], patch kernel
     if (!force.bm && KH == 3 && KW == 3 && stride == 1 && pad == 1 && pad_mode == 1 && Cin == 16 && Cout == 16 && !d.accumulate && !d.in_act && !d.pre_add && ld_bwd >= 16) {
         ThinArgs t{d.dz, d.w_bwd, nullptr, d.dxp, B, Ho, Wo, Hs + 2, Ws + 2, ld_bwd, ACT_NONE, 2, 1};
-        hipLaunchKernelGGL((k_conv3x3_thin<16, 1, false, 8>), dim3((Ws + 2 + 63) / 64, (Hs + 2 + 7) / 8, B), dim3(256), 0, stream, t);
+        if (!dry) hipLaunchKernelGGL((k_conv3x3_thin<16, 1, false, 8>), dim3((Ws + 2 + 63) / 64, (Hs + 2 + 7) / 8, B), dim3(256), 0, stream, t);
         done = true;
         return E2E_OK;
     }
@@ -3058,7 +3091,7 @@ static int bwd_data_setup(const BwdDataOps& d, const ConvGeom& g, GemmCfg force,
     // only -- the other three quarters of dxp are zeros, written by a memset node on the same stream.
     // (class lattices of 2^24 rows or more take the plain transposed form: the class epilogue decodes its rows in fp32)
     a.cls = (stride == 2 && cls_rows(B, a.Hd, a.Wd) < (1 << 24)) ? 1 : 0;
-    if (a.cls && (KH < 2 || KW < 2) && !d.accumulate)
+    if (a.cls && (KH < 2 || KW < 2) && !d.accumulate && !dry)
         (void)hipMemsetAsync(d.dxp, 0, (size_t)B * a.Hd * a.Wd * Cin * sizeof(float), stream);
     // accumulate: dxp += result -- the epilogue's residual input reads the element it is about to overwrite (same thread)
     if (d.accumulate) a.res = d.dxp;
@@ -3299,7 +3332,8 @@ struct WgradLaunch { WgradKernel k; dim3 g; int Sz; };
 
 // backward-weight up to its GEMM: checks the arguments, serves the stem / thin / tap layers with their patch kernels and reductions
 // (L.k = WK_DONE), or fills the GEMM's WgradArgs and decomposition (wg_target == 0: an untuned call).  Shared by bwd_weight_impl and the paired backward.
-static int wgrad_setup(const WgradIn& in, const ConvGeom& g, int wg_target, const WgradOut& o, hipStream_t st, WgradArgs& a, WgradLaunch& L) {
+// dry: decide only, launch nothing.
+static int wgrad_setup(const WgradIn& in, const ConvGeom& g, int wg_target, const WgradOut& o, hipStream_t st, WgradArgs& a, WgradLaunch& L, bool dry = false) {
     const int B = g.B, Cin = g.Cin, Cout = g.Cout, Ho = g.Ho, Wo = g.Wo;
     const bool tuned = wg_target != 0;
     if (!tuned) wg_target = WGRAD_TARGET;
@@ -3314,6 +3348,7 @@ static int wgrad_setup(const WgradIn& in, const ConvGeom& g, int wg_target, cons
     a.Ngemm = g.KH * g.KW * Cin + a.has_bias;
     const WgradPlan p = wgrad_choose(g, a.has_bias, in.src1 != nullptr, tuned, wg_target);
     const int S = (int)p.S;
+    if (dry && (p.path == WP_STEM || p.path == WP_THIN || p.path == WP_TAPS)) return E2E_OK;
     if (p.path == WP_STEM) {                                 // the patch kernels: kernel + the common slab reduction
         StemWgradArgs ta{in.dz, in.src0, in.workspace, B, g.Hs, g.Ws, Ho, Wo, 2, p.nxg, g.in_sub, g.in_mul};
         hipLaunchKernelGGL(k_wgrad7x7_stem, dim3(p.nxg, p.ny, B), dim3(256), 0, st, ta);
@@ -3400,6 +3435,87 @@ int e2e_conv2d_bwd_weight_scaled_deferred(const float* da, const float* out_scal
     return bwd_weight_impl(WgradIn{da, src0, src1, workspace}, g, WgradOut{dw, dbias, out_scale, accumulate, desc_out}, stream);
 }
 
+struct PairOps {
+    const float *da, *w_bwd; int ld_bwd; float* dxp; int accumulate; const float* x_in; int in_act; const float* pre_add; float* workspace;
+    const float *out_scale, *src0, *src1; float *dw, *dbias, *workspace_w; int accumulate_w; e2e_wgrad_reduce_desc* desc_out;
+};
+// the carried slab reductions of a paired launch: items [first, first + items) of a prepared table; place: 0 after both tile sets, 1 between
+// them, 2 first in the grid
+struct PairCarry { const e2e_wgrad_reduce_desc* descs; int n; long long first, items; int place; };
+#ifndef CARRY_WGS
+#define CARRY_WGS 2048                      // workgroups of the carry part at most: 256 (one per CU) LOST 1 % against the separate reduction launches, 2048 and 4096
+                                            // gain 1.8 % alike -- the items are bound by memory and want the loads of many waves in flight (profiles/pair_carry_kernel_stats.txt)
+#endif
+
+// What a paired backward call will run: both setups, the backward-data plan, and whether the two main launches are ONE k_conv_bwd_pair launch.
+struct PairPlan { ConvArgs ad; bool data_done; WgradArgs aw; WgradLaunch lw; GemmLaunch pd; bool paired, d14; };
+
+static int bwd_pair_plan(const PairOps& q, const ConvGeom& g, const WgradOut& o, hipStream_t st, PairPlan& P, bool dry) {
+    int rc = bwd_data_setup(BwdDataOps{q.da, q.w_bwd, q.ld_bwd, q.dxp, q.accumulate, q.x_in, q.in_act, q.pre_add}, g, GemmCfg{0, 0, 0}, st, P.ad, P.data_done, dry);
+    if (rc != E2E_OK) return rc;
+    rc = wgrad_setup(WgradIn{q.da, q.src0, q.src1, q.workspace_w}, g, 0, o, st, P.aw, P.lw, dry);
+    if (rc != E2E_OK) return rc;
+    P.pd = GemmLaunch{};
+    if (!P.data_done) P.pd = plan_gemm<true>(P.ad, 4, q.workspace, GemmCfg{0, 0, 0});
+    P.d14 = P.pd.c.bm == 32 && P.pd.c.bn == 128;
+    const bool d22 = P.pd.c.bm == 64 && P.pd.c.bn == 64;
+    P.paired = !P.data_done && P.pd.kind == GK_TILE && P.pd.cb == 32 && (P.d14 || d22) && P.lw.k == WK_GEMM4_64;
+    return E2E_OK;
+}
+
+static int wgrad_reduce_range(const e2e_wgrad_reduce_desc* descs_dev, int n, long long first_item, long long items, hipStream_t st) {
+    hipLaunchKernelGGL(k_wgrad_reduce_batched, dim3((unsigned)(items < 4096 ? items : 4096)), dim3(512), 0, st, descs_dev, n, first_item, items);
+    return E2E_OK;
+}
+
+static int bwd_pair_impl(const PairOps& q, const ConvGeom& g, int wgrad_first, const PairCarry& cy, const char* who, void* stream) {
+    E2E_REQUIRE(q.desc_out, E2E_ERR_ARG, "%s: desc_out is NULL", who);
+    E2E_REQUIRE(cy.items >= 0 && cy.first >= 0 && (cy.items == 0 || (cy.descs && cy.n > 0)) && cy.place >= 0 && cy.place <= 2, E2E_ERR_ARG,
+                "%s: bad carry range", who);
+    const hipStream_t st = (hipStream_t)stream;
+    const WgradOut o{q.dw, q.dbias, q.out_scale, q.accumulate_w, q.desc_out};
+    PairPlan P;
+    const int rc = bwd_pair_plan(q, g, o, st, P, false);
+    if (rc != E2E_OK) return rc;
+    ConvArgs& ad = P.ad;
+    const WgradArgs& aw = P.aw;
+    const WgradLaunch& lw = P.lw;
+    if (P.paired) {
+        PairGrid pg;
+        pg.dgx = P.pd.g.x; pg.dgy = P.pd.g.y; pg.dgz = P.pd.g.z;
+        pg.wgx = lw.g.x; pg.wgy = lw.g.y; pg.wgz = lw.g.z;
+        const unsigned nd = pg.dgx * pg.dgy * pg.dgz, nw = pg.wgx * pg.wgy * pg.wgz;
+        pg.wgrad_first = wgrad_first ? 1 : 0;
+        pg.first = ((wgrad_first ? nw : nd) + 7u) / 8u * 8u;
+        const unsigned second = wgrad_first ? nd : nw;
+        // the carry part: in front of a tile set it is padded to a multiple of 8, so that the tile sets keep their XCDs (and, after the
+        // subtraction in the kernel, their ids)
+        CarryArgs ca{cy.descs, cy.n, (unsigned)(cy.items < CARRY_WGS ? cy.items : CARRY_WGS), cy.first, cy.items};
+        pg.cbeg = 0xffffffffu; pg.cpad = 0;
+        if (ca.wgs) {
+            pg.cbeg = cy.place == 0 ? pg.first + second : cy.place == 1 ? pg.first : 0u;
+            pg.cpad = cy.place == 0 ? ca.wgs : (ca.wgs + 7u) / 8u * 8u;
+        }
+        const dim3 grid(pg.first + second + pg.cpad);
+        const bool two = aw.src1 != nullptr;
+        if (P.d14) {
+            if (two) hipLaunchKernelGGL((k_conv_bwd_pair<1, 4, true>), grid, dim3(256), 0, st, ad, aw, pg, ca);
+            else hipLaunchKernelGGL((k_conv_bwd_pair<1, 4, false>), grid, dim3(256), 0, st, ad, aw, pg, ca);
+        } else {
+            if (two) hipLaunchKernelGGL((k_conv_bwd_pair<2, 2, true>), grid, dim3(256), 0, st, ad, aw, pg, ca);
+            else hipLaunchKernelGGL((k_conv_bwd_pair<2, 2, false>), grid, dim3(256), 0, st, ad, aw, pg, ca);
+        }
+    } else {
+        if (!P.data_done) launch_gemm_main<true>(ad, P.pd, q.workspace, st);
+        if (lw.k != WK_DONE) wgrad_launch_gemm(aw, lw, st);
+    }
+    if (!P.data_done) launch_gemm_tail(ad, P.pd, st);
+    if (lw.k != WK_DONE) wgrad_reduce(aw, o, lw.Sz, aw.Mpad, aw.Npad, lw.Sz >= 8 ? 8 : 2, st);
+    if (!P.paired && cy.items > 0) wgrad_reduce_range(cy.descs, cy.n, cy.first, cy.items, st);      // correct, gains nothing: callers ask is_one_launch first
+    E2E_LAUNCH_CHECK(who);
+    return E2E_OK;
+}
+
 /* A layer's backward-data (e2e_conv2d_bwd_data_fused; accumulate = 0, x_in = pre_add = NULL, in_act = 0 is e2e_conv2d_bwd_data) and its
  * backward-weight (e2e_conv2d_bwd_weight_scaled_deferred) on the same gradient `da`.  Each half takes the decomposition its own entry point
  * takes; where both main GEMM launches are ones k_conv_bwd_pair carries, they run as ONE launch (wgrad_first: which tile set comes first
@@ -3410,46 +3526,42 @@ int e2e_conv2d_bwd_pair_deferred(const float* da, const float* w_bwd, int ld_bwd
                                  float* workspace, const float* out_scale, const float* src0, const float* src1, int C1, int up, float* dw, float* dbias,
                                  float* workspace_w, int accumulate_w, float in_sub, float in_mul, e2e_wgrad_reduce_desc* desc_out, int wgrad_first,
                                  void* stream) {
-    E2E_REQUIRE(desc_out, E2E_ERR_ARG, "e2e_conv2d_bwd_pair_deferred: desc_out is NULL");
-    const hipStream_t st = (hipStream_t)stream;
-    ConvArgs ad;
-    bool data_done;
     GEOM_BWD_WEIGHT(g);
-    int rc = bwd_data_setup(BwdDataOps{da, w_bwd, ld_bwd, dxp, accumulate, x_in, in_act, pre_add}, g, GemmCfg{0, 0, 0}, st, ad, data_done);
-    if (rc != E2E_OK) return rc;
-    const WgradOut o{dw, dbias, out_scale, accumulate_w, desc_out};
-    WgradArgs aw;
-    WgradLaunch lw;
-    rc = wgrad_setup(WgradIn{da, src0, src1, workspace_w}, g, 0, o, st, aw, lw);
-    if (rc != E2E_OK) return rc;
-    GemmLaunch pd{};
-    if (!data_done) pd = plan_gemm<true>(ad, 4, workspace, GemmCfg{0, 0, 0});
-    const bool d14 = pd.c.bm == 32 && pd.c.bn == 128, d22 = pd.c.bm == 64 && pd.c.bn == 64;
-    const bool paired = !data_done && pd.kind == GK_TILE && pd.cb == 32 && (d14 || d22) && lw.k == WK_GEMM4_64;
-    if (paired) {
-        PairGrid pg;
-        pg.dgx = pd.g.x; pg.dgy = pd.g.y; pg.dgz = pd.g.z;
-        pg.wgx = lw.g.x; pg.wgy = lw.g.y; pg.wgz = lw.g.z;
-        const unsigned nd = pg.dgx * pg.dgy * pg.dgz, nw = pg.wgx * pg.wgy * pg.wgz;
-        pg.wgrad_first = wgrad_first ? 1 : 0;
-        pg.first = ((wgrad_first ? nw : nd) + 7u) / 8u * 8u;
-        const dim3 grid(pg.first + (wgrad_first ? nd : nw));
-        const bool two = aw.src1 != nullptr;
-        if (d14) {
-            if (two) hipLaunchKernelGGL((k_conv_bwd_pair<1, 4, true>), grid, dim3(256), 0, st, ad, aw, pg);
-            else hipLaunchKernelGGL((k_conv_bwd_pair<1, 4, false>), grid, dim3(256), 0, st, ad, aw, pg);
-        } else {
-            if (two) hipLaunchKernelGGL((k_conv_bwd_pair<2, 2, true>), grid, dim3(256), 0, st, ad, aw, pg);
-            else hipLaunchKernelGGL((k_conv_bwd_pair<2, 2, false>), grid, dim3(256), 0, st, ad, aw, pg);
-        }
-    } else {
-        if (!data_done) launch_gemm_main<true>(ad, pd, workspace, st);
-        if (lw.k != WK_DONE) wgrad_launch_gemm(aw, lw, st);
-    }
-    if (!data_done) launch_gemm_tail(ad, pd, st);
-    if (lw.k != WK_DONE) wgrad_reduce(aw, o, lw.Sz, aw.Mpad, aw.Npad, lw.Sz >= 8 ? 8 : 2, st);
-    E2E_LAUNCH_CHECK("e2e_conv2d_bwd_pair_deferred");
-    return E2E_OK;
+    return bwd_pair_impl(PairOps{da, w_bwd, ld_bwd, dxp, accumulate, x_in, in_act, pre_add, workspace, out_scale, src0, src1, dw, dbias, workspace_w, accumulate_w, desc_out},
+                         g, wgrad_first, PairCarry{nullptr, 0, 0, 0, 0}, "e2e_conv2d_bwd_pair_deferred", stream);
+}
+
+/* e2e_conv2d_bwd_pair_deferred whose ONE launch also runs slab reductions left by EARLIER backward-weight GEMMs on the stream: the work items
+ * [carry_first_item, carry_first_item + carry_items) of a prepared descriptor table in device memory (e2e_wgrad_reduce_batch_prepare), as a
+ * third part of the grid (carry_place: 0 after both tile sets, 1 between them, 2 first).  The items are memory-bound and fill the launch's
+ * tile-quantisation tail; each does the arithmetic it does in e2e_wgrad_reduce_batched, so results are bit-identical.  The slabs the
+ * range reads must be complete when this launch starts, and the range must not include this layer's own descriptor.  Where the layer's
+ * two GEMMs do not pair (e2e_conv2d_bwd_pair_is_one_launch), the range runs as a reduction launch of its own after them. */
+int e2e_conv2d_bwd_pair_carry(const float* da, const float* w_bwd, int ld_bwd, float* dxp, int B, int Hs, int Ws, int Cin, int Cout, int Ho, int Wo,
+                              int KH, int KW, int stride, int pad, int pad_mode, int accumulate, const float* x_in, int in_act, const float* pre_add,
+                              float* workspace, const float* out_scale, const float* src0, const float* src1, int C1, int up, float* dw, float* dbias,
+                              float* workspace_w, int accumulate_w, float in_sub, float in_mul, e2e_wgrad_reduce_desc* desc_out, int wgrad_first,
+                              const e2e_wgrad_reduce_desc* carry_descs_dev, int carry_n, long long carry_first_item, long long carry_items, int carry_place,
+                              void* stream) {
+    GEOM_BWD_WEIGHT(g);
+    return bwd_pair_impl(PairOps{da, w_bwd, ld_bwd, dxp, accumulate, x_in, in_act, pre_add, workspace, out_scale, src0, src1, dw, dbias, workspace_w, accumulate_w, desc_out},
+                         g, wgrad_first, PairCarry{carry_descs_dev, carry_n, carry_first_item, carry_items, carry_place}, "e2e_conv2d_bwd_pair_carry", stream);
+}
+
+/* 1 where the pair entry points run this layer's two GEMMs as ONE k_conv_bwd_pair launch (the launch that can carry), 0 where they fall back
+ * to two launch sequences or the arguments are refused.  Host only; the flags stand for the operands the decision looks at. */
+int e2e_conv2d_bwd_pair_is_one_launch(int ld_bwd, int B, int Hs, int Ws, int Cin, int Cout, int Ho, int Wo, int KH, int KW, int stride, int pad, int pad_mode,
+                                      int accumulate, int in_act, int has_pre_add, int has_workspace, int has_src1, int C1, int up, int has_bias) {
+    static float nowhere[4];                                 // stands for every operand: the plan looks at which pointers are NULL, never through them
+    float* const x = nowhere;
+    const float in_sub = 0.f, in_mul = 1.f;
+    GEOM_BWD_WEIGHT(g);
+    e2e_wgrad_reduce_desc desc;
+    const PairOps q{x, x, ld_bwd, x, accumulate, in_act ? x : nullptr, in_act, has_pre_add ? x : nullptr, has_workspace ? x : nullptr, nullptr, x, has_src1 ? x : nullptr,
+                    x, has_bias ? x : nullptr, x, 0, &desc};
+    PairPlan P;
+    if (bwd_pair_plan(q, g, WgradOut{q.dw, q.dbias, nullptr, 0, &desc}, nullptr, P, true) != E2E_OK) return 0;
+    return P.paired ? 1 : 0;
 }
 
 /* fills first_item of n descriptors in HOST memory (running total of work items); returns the total, or -1 on a malformed descriptor */
@@ -3469,8 +3581,16 @@ long long e2e_wgrad_reduce_batch_prepare(e2e_wgrad_reduce_desc* descs_host, int 
 
 int e2e_wgrad_reduce_batched(const e2e_wgrad_reduce_desc* descs_dev, int n, long long total_items, void* stream) {
     E2E_REQUIRE(descs_dev && n > 0 && total_items > 0, E2E_ERR_ARG, "e2e_wgrad_reduce_batched: bad argument");
-    hipLaunchKernelGGL(k_wgrad_reduce_batched, dim3((unsigned)(total_items < 4096 ? total_items : 4096)), dim3(512), 0, (hipStream_t)stream, descs_dev, n, total_items);
+    wgrad_reduce_range(descs_dev, n, 0, total_items, (hipStream_t)stream);
     E2E_LAUNCH_CHECK("e2e_wgrad_reduce_batched");
+    return E2E_OK;
+}
+
+/* the work items [first_item, first_item + items) of the same table: the layers whose first_item falls in the range, nothing else */
+int e2e_wgrad_reduce_batched_range(const e2e_wgrad_reduce_desc* descs_dev, int n, long long first_item, long long items, void* stream) {
+    E2E_REQUIRE(descs_dev && n > 0 && first_item >= 0 && items > 0, E2E_ERR_ARG, "e2e_wgrad_reduce_batched_range: bad argument");
+    wgrad_reduce_range(descs_dev, n, first_item, items, (hipStream_t)stream);
+    E2E_LAUNCH_CHECK("e2e_wgrad_reduce_batched_range");
     return E2E_OK;
 }
 

@@ -35,6 +35,9 @@ _f32 = torch.float32
 # the paired backward (e2e_conv2d_bwd_pair_deferred) puts the backward-data tiles first in its grid: 6.5 % against 4.3 % for the other
 # order over the backward GEMMs of a pass (tools/bwd_pair_ab.py, profiles/r05_bwd_pair_ab.txt)
 PAIR_WGRAD_FIRST = 0
+# where the carried slab reductions sit in a paired launch's grid (e2e_conv2d_bwd_pair_carry: 0 after both tile sets, 1 between them, 2 in front):
+# behind the tiles they fill the launch's tail, +1.8 % steps/s; between them +0.3 %, in front -0.2 % (profiles/pair_carry_kernel_stats.txt)
+PAIR_CARRY_PLACE = 0
 
 
 class Buf:
@@ -138,10 +141,15 @@ class _Conv:
         if s.need_dx and plan.paired and not plan.overlap:
             # backward-data and backward-weight of this layer as one launch (e2e_conv2d_bwd_pair_deferred: bit-identical to the two calls below)
             pre = s.pre_from.out.g if (s.direct and s.pre_from is not None) else None
-            L.call("e2e_conv2d_bwd_pair_deferred", geom=s.geom, da=L.ptr(g), w_bwd=L.ptr(s.wb), ld_bwd=s.ldb, dxp=L.ptr(s.src0.g if s.direct else s.dxp),
-                   accumulate=(1 if s.src0.written else 0) if s.direct else 0, x_in=L.ptr(s.src0.t) if s.direct else None,
-                   in_act=s.src0.act if s.direct else 0, pre_add=L.ptr(pre), workspace=L.ptr(s.ws_b), workspace_w=L.ptr(s.ws_w), accumulate_w=0,
-                   wgrad_first=PAIR_WGRAD_FIRST, stream=st, **s._wgrad_operands(plan))
+            acc, in_act = (1 if s.src0.written else 0) if s.direct else 0, s.src0.act if s.direct else 0
+            # ... and, where that IS one launch, the slab reductions of the layers before it in this half ride in its grid (NetPlan.carry_for)
+            carry = plan.carry_for(s, lambda: L.query("e2e_conv2d_bwd_pair_is_one_launch", geom=s.geom, ld_bwd=s.ldb, accumulate=acc, in_act=in_act,
+                                                      has_pre_add=1 if pre is not None else 0, has_workspace=1 if s.ws_b is not None else 0,
+                                                      has_src1=1 if s.src1 is not None else 0, has_bias=1 if s.bias is not None else 0))
+            L.call("e2e_conv2d_bwd_pair_carry" if carry else "e2e_conv2d_bwd_pair_deferred", geom=s.geom, da=L.ptr(g), w_bwd=L.ptr(s.wb), ld_bwd=s.ldb,
+                   dxp=L.ptr(s.src0.g if s.direct else s.dxp), accumulate=acc, x_in=L.ptr(s.src0.t) if s.direct else None, in_act=in_act, pre_add=L.ptr(pre),
+                   workspace=L.ptr(s.ws_b), workspace_w=L.ptr(s.ws_w), accumulate_w=0, wgrad_first=PAIR_WGRAD_FIRST, stream=st, **s._wgrad_operands(plan),
+                   **(carry or {}))
             if s.direct:
                 s.src0.written = True
             else:
@@ -156,6 +164,7 @@ class _Conv:
             else:
                 L.call("e2e_conv2d_bwd_data", geom=s.geom, dz=L.ptr(g), w_bwd=L.ptr(s.wb), ld_bwd=s.ldb, dxp=L.ptr(s.dxp), workspace=L.ptr(s.ws_b), stream=st)
                 self._gather_adjoint(st)
+        plan.carry_for(s, None)
         st_w = plan.fork(st)
         # the GEMM leaves its partial slabs in this layer's own workspace; the ~30 slab reductions of a pass are ONE launch at its end
         # (NetPlan._reduce_weight_gradients): each was 5 - 15 us of launch latency on an almost empty GPU
@@ -259,6 +268,8 @@ class NetPlan:
         # one-stream plan: each layer's backward-data and backward-weight GEMMs run as one launch; E2E_PAIRED_BWD=0 issues them separately
         # (A/B comparison, bisecting -- results are bit-identical either way)
         self.paired = os.environ.get("E2E_PAIRED_BWD", "1") != "0"
+        # ... and the paired launches carry the slab reductions of the layers before them (E2E_CARRY_REDUCE=0: one batched launch per half, as before)
+        self.carry = self.paired and not overlap and os.environ.get("E2E_CARRY_REDUCE", "1") != "0"
         self.B, self.H, self.W = B, H, W
         if H % 32 or W % 32:
             raise ValueError(f"launch plan: the encoder halves the image five times and the decoder doubles it back before every skip "
@@ -320,7 +331,8 @@ class NetPlan:
         self._desc_key = None
         self._retired_tables = []
         self._move_tables = {}                               # (src slot, dst slot) -> (copy descriptor table on the device, copies, work items)
-        self._reduce_tables = {}                             # "late" / "early" -> (descriptor bytes, device copy, work items)
+        self._reduce_tables = {}                             # "late" / "early" -> (descriptor bytes, device copy, work items, first items, pointer key)
+        self._carrying = None                                # the half in flight, when its paired launches carry: [table entry, its layers, issued, items assigned]
 
     def _add(self, op):
         self.ops.append(op)
@@ -470,6 +482,7 @@ class NetPlan:
         st = L.stream()
         for op in self.ops:
             op.out.written = False
+        self._begin_half("late", self.ops[self.split_index:])
         for op in reversed(self.ops[self.split_index:]):
             op.bwd(self, st)
         self.join()
@@ -487,16 +500,57 @@ class NetPlan:
             raise RuntimeError("launch plan: backward_early_layers() follows backward_late_layers()")
         for op, w in zip(self.ops, state):
             op.out.written = w
+        self._begin_half("early", self.ops[:self.split_index])
         for op in reversed(self.ops[:self.split_index]):
             op.bwd(self, st)
         self.join()
         self._reduce_weight_gradients("early", self.ops[:self.split_index])
 
+    @staticmethod
+    def _half_convs(ops):
+        """The convolutions of a backward half in the order their backward-weight GEMMs are issued: the order of the half's descriptor table."""
+        return [op for op in reversed(ops) if isinstance(op, _Conv)]
+
+    def _table_key(self, convs):
+        """Every POINTER a half's descriptors hold -- gradient sinks (the optimiser may re-home them), slab workspace, scale vector.  The other
+        fields (slab count, padded sizes, zl) follow from the layer's geometry and has_bias, which are fixed for the plan's lifetime."""
+        return tuple((self.sink(op.weight).data_ptr(), self.sink(op.bias).data_ptr() if op.bias is not None else 0, op.ws_w.data_ptr(),
+                      op.scale.data_ptr() if op.scale is not None else 0) for op in convs)
+
+    def _begin_half(self, which, ops):
+        """The paired launches of a half carry reductions once the half's descriptor table exists on the device and still names the buffers
+        in use (_table_key, checked here, BEFORE anything is carried) -- from the second pass on.
+        The first pass (and the one after the optimiser re-homed a sink) ends with the one batched launch, which builds the table; under capture the launch arguments are those of the eager pass before."""
+        self._carrying = None
+        held = self._reduce_tables.get(which) if self.carry else None
+        if held is not None:
+            convs = self._half_convs(ops)
+            if held[4] == self._table_key(convs):
+                self._carrying = [held, convs, 0, 0]
+
+    def carry_for(self, conv, one_launch):
+        """Called once by every convolution's backward, in table order.  one_launch: None (the layer does not go through the pair entry point), or
+        the query that says whether its launch can carry.  Returns the carry arguments of e2e_conv2d_bwd_pair_carry -- the work items of all
+        layers issued before this one in the half and not yet assigned -- or None.  Never crosses the boundary between the halves: a half's
+        left-overs are reduced at its end (_reduce_weight_gradients)."""
+        c = self._carrying
+        if c is None:
+            return None
+        (_, table, _, firsts, _), convs, i, done = c
+        if i >= len(convs) or convs[i] is not conv:
+            raise RuntimeError("launch plan: backward order differs from the reduction table's")
+        c[2] = i + 1
+        if one_launch is None or firsts[i] == done or not one_launch():
+            return None
+        c[3] = firsts[i]
+        return dict(carry_descs_dev=L.ptr(table), carry_n=len(convs), carry_first_item=done, carry_items=firsts[i] - done, carry_place=PAIR_CARRY_PLACE)
+
     def _reduce_weight_gradients(self, which, ops):
-        """ONE launch for the slab reductions the backward-weight GEMMs of `ops` deferred (e2e_wgrad_reduce_batched).  The descriptor table
-        lives on the device; it is rebuilt when a descriptor changed (the optimiser re-homed a gradient sink) -- never under stream capture,
-        where the table the graph would keep pointing at must already exist (a plan runs eagerly at least once before it is captured)."""
-        convs = [op for op in ops if isinstance(op, _Conv)]
+        """The slab reductions the backward-weight GEMMs of `ops` deferred and no paired launch carried: ONE launch (e2e_wgrad_reduce_batched,
+        or its range form over the left-overs).  The descriptor table lives on the device, in backward order; it is rebuilt when a descriptor
+        changed (the optimiser re-homed a gradient sink) -- never under stream capture, where the table the graph would keep pointing at must
+        already exist (a plan runs eagerly at least once before it is captured)."""
+        convs = self._half_convs(ops)
         if not convs:
             return
         arr = (L.WgradReduceDesc * len(convs))(*[op.reduce_desc for op in convs])
@@ -505,13 +559,20 @@ class NetPlan:
             raise RuntimeError("launch plan: malformed backward-weight reduction descriptor")
         raw = bytes(arr)
         held = self._reduce_tables.get(which)
+        c, self._carrying = self._carrying, None
+        if c is not None:
+            if held is not c[0] or held[0] != raw or c[2] != len(convs):
+                raise RuntimeError("launch plan: the backward-weight reduction table changed while its reductions were being carried")
+            if c[3] < total:
+                L.call("e2e_wgrad_reduce_batched_range", L.ptr(held[1]), len(convs), c[3], total - c[3], L.stream())
+            return
         if held is None or held[0] != raw:
             if torch.cuda.is_current_stream_capturing():
                 raise RuntimeError("launch plan: the backward-weight reduction table changed under stream capture; run the plan eagerly once first")
             table = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(self.dev)
             if held is not None:
                 self._retired_tables.append(held[1])        # a graph captured earlier may still name the old table: it stays allocated
-            held = self._reduce_tables[which] = (raw, table, total)
+            held = self._reduce_tables[which] = (raw, table, total, [d.first_item for d in arr], self._table_key(convs))
         L.call("e2e_wgrad_reduce_batched", L.ptr(held[1]), len(convs), held[2], L.stream())
 
     def split_offset(self, flat):

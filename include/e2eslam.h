@@ -623,8 +623,34 @@ int e2e_conv2d_bwd_pair_deferred(const float* da, const float* w_bwd, int ld_bwd
                                  float* dbias, float* workspace_w, int accumulate_w, float in_sub,
                                  float in_mul, e2e_wgrad_reduce_desc* desc_out_host, int wgrad_first,
                                  void* stream);
+/* e2e_conv2d_bwd_pair_deferred whose ONE launch also runs slab reductions that EARLIER backward-weight GEMMs on the stream left to do: the
+ * work items [carry_first_item, carry_first_item + carry_items) of a prepared descriptor table in device memory, as a third part of the
+ * grid (carry_place: 0 after both tile sets, 1 between them, 2 in front of them).  The items are bound by memory and fill the tail of a
+ * launch bound by the matrix pipe; each does the arithmetic it does in e2e_wgrad_reduce_batched, so the results are bit-identical.  The
+ * range must not include this layer's own descriptor, and the slabs it reads must be complete when the launch starts (stream order
+ * guarantees that for earlier launches).  carry_items == 0 is e2e_conv2d_bwd_pair_deferred.  Where the two GEMMs do not pair
+ * (e2e_conv2d_bwd_pair_is_one_launch == 0) the range runs as a reduction launch of its own after them. */
+int e2e_conv2d_bwd_pair_carry(const float* da, const float* w_bwd, int ld_bwd, float* dxp, int B, int Hs,
+                              int Ws, int Cin, int Cout, int Ho, int Wo, int KH, int KW, int stride,
+                              int pad, int pad_mode, int accumulate, const float* x_in, int in_act,
+                              const float* pre_add, float* workspace, const float* out_scale,
+                              const float* src0, const float* src1, int C1, int up, float* dw,
+                              float* dbias, float* workspace_w, int accumulate_w, float in_sub,
+                              float in_mul, e2e_wgrad_reduce_desc* desc_out_host, int wgrad_first,
+                              const e2e_wgrad_reduce_desc* carry_descs_dev, int carry_n,
+                              long long carry_first_item, long long carry_items, int carry_place,
+                              void* stream);
+/* Host only: 1 where the two pair entry points run this layer's GEMMs as ONE launch (decided by the code the calls themselves use), 0 where
+ * they run two launch sequences or refuse the arguments (a refusal sets e2e_last_error like the calls' own, although nothing failed).  The
+ * has_* flags stand for the operands the decision looks at (non-NULL or not). */
+int e2e_conv2d_bwd_pair_is_one_launch(int ld_bwd, int B, int Hs, int Ws, int Cin, int Cout, int Ho, int Wo,
+                                      int KH, int KW, int stride, int pad, int pad_mode, int accumulate,
+                                      int in_act, int has_pre_add, int has_workspace, int has_src1, int C1,
+                                      int up, int has_bias);
 long long e2e_wgrad_reduce_batch_prepare(e2e_wgrad_reduce_desc* descs_host, int n);
 int e2e_wgrad_reduce_batched(const e2e_wgrad_reduce_desc* descs_dev, int n, long long total_items, void* stream);
+/* the work items [first_item, first_item + items) of a prepared table: the layers (or parts of layers) in that range and nothing else */
+int e2e_wgrad_reduce_batched_range(const e2e_wgrad_reduce_desc* descs_dev, int n, long long first_item, long long items, void* stream);
 
 /* Many device-to-device copies in one launch (launch economy of the static plan; the reference has no counterpart): n descriptors
  * {src, dst, bytes (a positive multiple of 16, both pointers 16-byte aligned), first_item} in device memory, prepared on the host. */
