@@ -6,6 +6,7 @@ exponential are float64 on the host (one 232-byte copy per iteration; odometry r
 refinement step)."""
 import numpy as np
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _lib as L
 from . import ops
@@ -42,60 +43,218 @@ def _unpack(v):
     return AtA, v[21:27], int(round(v[27])), float(v[28])
 
 
+def se3_exp_bwd(xi, Tbar):
+    """Adjoint of se3_exp: Tbar (4,4) (its top three rows count) -> xibar (6,), float64, same branch as the forward."""
+    v, w = np.asarray(xi[:3], np.float64), np.asarray(xi[3:], np.float64)
+    t2 = float(w @ w)
+    th = np.sqrt(t2)
+    W = _so3_hat(w)
+    W2 = W @ W
+    if th < 1e-2:                                                              # the series and its derivatives with respect to th^2
+        b, c2 = 0.5 - t2 / 24.0 * (1.0 - t2 / 30.0), 1.0 / 6.0 - t2 / 120.0 * (1.0 - t2 / 42.0)
+        a = 1.0 - t2 / 6.0 * (1.0 - t2 / 20.0)
+        da, db, dc = -1.0 / 6.0 + t2 / 60.0, -1.0 / 24.0 + t2 / 360.0, -1.0 / 120.0 + t2 / 2520.0
+    else:
+        sn, cs = np.sin(th), np.cos(th)
+        a, b, c2 = sn / th, (1.0 - cs) / t2, (th - sn) / (t2 * th)
+        # d/d(th^2) = (d/dth) / (2 th)
+        da = (th * cs - sn) / t2 / (2.0 * th)
+        db = (th * sn - 2.0 * (1.0 - cs)) / (t2 * th) / (2.0 * th)
+        dc = ((1.0 - cs) * th - 3.0 * (th - sn)) / (t2 * t2) / (2.0 * th)
+    V = np.eye(3) + b * W + c2 * W2
+    Rb, tb = np.asarray(Tbar[:3, :3], np.float64), np.asarray(Tbar[:3, 3], np.float64)
+    Vb = np.outer(tb, v)
+    ab, bb, cb = np.sum(Rb * W), np.sum(Rb * W2) + np.sum(Vb * W), np.sum(Vb * W2)
+    Wb = a * Rb + b * (Rb @ W.T + W.T @ Rb) + b * Vb + c2 * (Vb @ W.T + W.T @ Vb)
+    wb = np.array([Wb[2, 1] - Wb[1, 2], Wb[0, 2] - Wb[2, 0], Wb[1, 0] - Wb[0, 1]]) + 2.0 * w * (ab * da + bb * db + cb * dc)
+    return np.concatenate([V.T @ tb, wb])
+
+
 def _reduce(cur, tgt, tgt_n, dist_thresh, out, ws, index=None):
     d, idx = ops.knn1(cur, index if index is not None else tgt)
     L.call("e2e_icp_normal_equations", L.ptr(cur), L.ptr(tgt), L.ptr(tgt_n), L.ptr(idx), L.ptr(d),
            -1.0 if dist_thresh is None else float(dist_thresh), cur.shape[0], L.ptr(out), L.ptr(ws), L.stream())
-    return _unpack(out.cpu().numpy())
+    return _unpack(out.cpu().numpy()) + (idx, d)
 
 
-def point_to_plane_icp(src, tgt, tgt_n, numiters=20, damp=1e-8, dist_thresh=None, mode="icp", lambda_max=2.0, B=1.0, B2=1.0, nu=200.0):
-    """src (Ns,3), tgt / tgt_n (Nt,3) device tensors -> 4x4 float64 numpy transform aligning src to tgt, plus a trace."""
-    if mode not in ("icp", "gradicp"):
-        raise ValueError(f"unknown odometry mode {mode}")
-    src, tgt, tgt_n = (L.dev(t, n).contiguous() for t, n in ((src, "src"), (tgt, "tgt"), (tgt_n, "tgt_normals")))
+class Trace(list):
+    """[(inliers, sum r^2)] per iteration, as ever; a differentiable run also keeps, in `iterations`, what its backward walks: per
+    iteration a dict with T (the transform the step started from), xi, lam, AtA, Atb, cnt, err, idx and dists of the search (device), and
+    for gradicp idx2 / dists2 / cnt2 / err2 of the trial step, delta and y (the gated twist)."""
+    iterations = ()
+
+
+def _icp_loop(src, tgt, tgt_n, numiters, damp, dist_thresh, mode, lambda_max, B, B2, nu, record=False):
     dev = src.device
     out = torch.empty(29, device=dev, dtype=torch.float64)
     ws = torch.empty(L.load().e2e_icp_workspace_bytes(), device=dev, dtype=torch.uint8)
     T = np.eye(4)
     lam = float(damp)
-    trace = []
+    trace = Trace()
+    recs = []
     index = ops.KnnIndex(tgt, src.shape[0])               # the target cloud is fixed: one grid for all iterations
     for _ in range(numiters):
         cur = ops.transform_points(src, torch.from_numpy(T).float().to(dev))
-        AtA, Atb, cnt, err = _reduce(cur, tgt, tgt_n, dist_thresh, out, ws, index)
+        AtA, Atb, cnt, err, idx, d = _reduce(cur, tgt, tgt_n, dist_thresh, out, ws, index)
         if cnt < 6:
             break
         xi = np.linalg.solve(AtA + lam * np.eye(6), Atb)
         step = se3_exp(xi)
+        rec = dict(T=T, xi=xi, lam=lam, AtA=AtA, Atb=Atb.copy(), cnt=cnt, err=err, idx=idx, dists=d, y=xi) if record else None
         if mode == "gradicp":
             nxt = ops.transform_points(cur, torch.from_numpy(step).float().to(dev))
-            _, _, cnt2, err2 = _reduce(nxt, tgt, tgt_n, dist_thresh, out, ws, index)
+            _, _, cnt2, err2, idx2, d2 = _reduce(nxt, tgt, tgt_n, dist_thresh, out, ws, index)
             delta = (err2 / max(cnt2, 1)) - (err / max(cnt, 1))
             lam = lam * (1.0 / lambda_max + (lambda_max - 1.0 / lambda_max) / (1.0 + B * np.exp(-B2 * nu * delta)))
-            step = se3_exp(xi / (1.0 + np.exp(np.clip(nu * delta, -60, 60))))
+            y = xi / (1.0 + np.exp(np.clip(nu * delta, -60, 60)))
+            step = se3_exp(y)
+            if record:
+                rec.update(idx2=idx2, dists2=d2, cnt2=cnt2, err2=err2, delta=delta, y=y)
         T = step @ T
         trace.append((cnt, err))
+        if record:
+            recs.append(rec)
+    trace.iterations = recs
+    return T, trace
+
+
+def _icp_backward(src, tgt, tgt_n, recs, Tbar, dist_thresh, mode, lambda_max, B, B2, nu):
+    """The iterations in reverse (the rule of include/e2eslam.h: searches, keep masks and counts fixed; targets constant).  Tbar (4,4)
+    float64: the adjoint of the final transform.  -> d/d src (n,3) fp32."""
+    dev, n, st = src.device, src.shape[0], L.stream()
+    thresh = -1.0 if dist_thresh is None else float(dist_thresh)
+    g_src = torch.zeros_like(src)
+    cur, nxt, g_cur, g_nxt, tmp = (torch.empty_like(src) for _ in range(5))
+    lambar = 0.0
+    Tbar = np.array(Tbar, np.float64)
+
+    def ne_bwd(pts, idx, d, adj, g, accumulate):
+        adj = torch.from_numpy(adj).to(dev)
+        L.call("e2e_icp_normal_equations_bwd", src=L.ptr(pts), tgt=L.ptr(tgt), tgt_normals=L.ptr(tgt_n), n_tgt=tgt.shape[0], idx=L.ptr(idx),
+               dists=L.ptr(d), dist_thresh=thresh, adj28=L.ptr(adj), n=n, g_src=L.ptr(g), accumulate=int(accumulate), stream=st)
+
+    def dT(g, pts):
+        full = np.zeros((4, 4))
+        full[:3] = ops.transform_points_bwd_T(g, pts).cpu().numpy()
+        return full
+
+    for rec in reversed(recs):
+        Tk, xi, y, lam_k = rec["T"], rec["xi"], rec["y"], rec["lam"]
+        T32 = torch.from_numpy(Tk).float().to(dev)
+        L.call("e2e_transform_points", L.ptr(src), L.ptr(T32), L.ptr(cur), n, 0, st)
+        S = se3_exp(y)
+        ybar = se3_exp_bwd(y, Tbar @ Tk.T)
+        Tbar = S.T @ Tbar
+        errbar, have_cur = 0.0, False
+        if mode == "gradicp":
+            delta, cnt, cnt2 = rec["delta"], rec["cnt"], rec["cnt2"]
+            z = nu * delta
+            gate = 1.0 / (1.0 + np.exp(np.clip(z, -60, 60)))
+            xibar = gate * ybar
+            dgate = -nu * gate * (1.0 - gate) if -60.0 < z < 60.0 else 0.0         # the clipped region has zero derivative
+            e = B * np.exp(-B2 * nu * delta)
+            q = 1.0 / lambda_max + (lambda_max - 1.0 / lambda_max) / (1.0 + e)
+            dq = (lambda_max - 1.0 / lambda_max) * e * B2 * nu / (1.0 + e) ** 2
+            deltabar = float(ybar @ xi) * dgate + lambar * lam_k * dq
+            lambar = lambar * q
+            err2bar, errbar = deltabar / max(cnt2, 1), -deltabar / max(cnt, 1)
+            if err2bar != 0.0:
+                step32 = torch.from_numpy(se3_exp(xi)).float().to(dev)
+                L.call("e2e_transform_points", L.ptr(cur), L.ptr(step32), L.ptr(nxt), n, 0, st)
+                adj = np.zeros(28)
+                adj[27] = err2bar
+                ne_bwd(nxt, rec["idx2"], rec["dists2"], adj, g_nxt, 0)
+                L.call("e2e_transform_points", L.ptr(g_nxt), L.ptr(step32), L.ptr(g_cur), n, 1, st)
+                xibar = xibar + se3_exp_bwd(xi, dT(g_nxt, cur))
+                have_cur = True
+        else:
+            xibar = ybar
+        gbar = np.linalg.solve((rec["AtA"] + lam_k * np.eye(6)).T, xibar)
+        Gbar = -np.outer(gbar, xi)
+        lambar += float(np.trace(Gbar))
+        adj = np.zeros(28)
+        k = 0
+        for r in range(6):
+            for c in range(r, 6):
+                adj[k] = Gbar[r, c] if r == c else Gbar[r, c] + Gbar[c, r]
+                k += 1
+        adj[21:27], adj[27] = gbar, errbar
+        ne_bwd(cur, rec["idx"], rec["dists"], adj, g_cur, have_cur)
+        Tbar = Tbar + dT(g_cur, src)
+        L.call("e2e_transform_points", L.ptr(g_cur), L.ptr(T32), L.ptr(tmp), n, 1, st)
+        g_src += tmp
+    return g_src
+
+
+class _DifferentiableICP(torch.autograd.Function):
+    """forward: the launch sequence and host arithmetic of _icp_loop (values bit-identical to the plain call), recording each iteration;
+    backward: _icp_backward.  Output: T (4,4) float64, or with prev_pose the pose fl32(T . prev_pose)."""
+
+    @staticmethod
+    def forward(ctx, src, tgt, tgt_n, prev_pose, cfg, holder):
+        T, trace = _icp_loop(src, tgt, tgt_n, record=True, **cfg)
+        holder.append(trace)
+        ctx.save_for_backward(src, tgt, tgt_n)
+        ctx.recs, ctx.cfg = trace.iterations, cfg
+        ctx.prev = None if prev_pose is None else prev_pose.detach().double().cpu().numpy()
+        if prev_pose is None:
+            return torch.from_numpy(T).to(src.device)
+        return torch.from_numpy(T @ ctx.prev).float().to(src.device)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        src, tgt, tgt_n = ctx.saved_tensors
+        Tbar = g.double().cpu().numpy()
+        if ctx.prev is not None:
+            Tbar = Tbar @ ctx.prev.T
+        c = ctx.cfg
+        g_src = _icp_backward(src, tgt, tgt_n, ctx.recs, Tbar, c["dist_thresh"], c["mode"], c["lambda_max"], c["B"], c["B2"], c["nu"])
+        return g_src, None, None, None, None, None
+
+
+def point_to_plane_icp(src, tgt, tgt_n, numiters=20, damp=1e-8, dist_thresh=None, mode="icp", lambda_max=2.0, B=1.0, B2=1.0, nu=200.0,
+                       prev_pose=None):
+    """src (Ns,3), tgt / tgt_n (Nt,3) device tensors -> 4x4 float64 numpy transform aligning src to tgt, plus a trace.
+    When src requires grad (and grad mode is on) the transform is a (4,4) float64 DEVICE tensor of the same values that carries the
+    gradient to src (the adjoint stated in include/e2eslam.h; targets are constants), and the trace holds the recorded iterations
+    (Trace.iterations).  prev_pose (4,4): return the pose fl32(T . prev_pose) as a float32 device tensor instead of T."""
+    if mode not in ("icp", "gradicp"):
+        raise ValueError(f"unknown odometry mode {mode}")
+    cfg = dict(numiters=numiters, damp=damp, dist_thresh=dist_thresh, mode=mode, lambda_max=lambda_max, B=B, B2=B2, nu=nu)
+    differentiable = torch.is_grad_enabled() and src.requires_grad
+    src, tgt, tgt_n = (L.dev(t, n).contiguous() for t, n in ((src, "src"), (tgt, "tgt"), (tgt_n, "tgt_normals")))
+    if differentiable:
+        holder = []
+        out = _DifferentiableICP.apply(src, tgt.detach(), tgt_n.detach(), prev_pose, cfg, holder)
+        return out, holder[0]
+    with torch.no_grad():
+        T, trace = _icp_loop(src, tgt, tgt_n, **cfg)
+    if prev_pose is not None:
+        return torch.from_numpy(T @ prev_pose.detach().double().cpu().numpy()).float().to(src.device), trace
     return T, trace
 
 
 def frame_to_model(fmap, depth, K, prev_pose, dsratio=4, **kw):
     """PointFusion._localize: pose of the live frame (depth (H,W)) given the resident map `fmap` (e2ehip.FusionMap)
-    and the previous frame's pose.  Returns a (4,4) float32 device tensor and the iteration trace."""
+    and the previous frame's pose.  Returns a (4,4) float32 device tensor and the iteration trace.  When depth requires grad (and grad
+    mode is on) the pose carries the gradient to the depth: through the source points only -- the map and prev_pose are constants."""
     H, W = fmap.H, fmap.W
     if fmap.M == 0:
         raise ValueError("frame-to-model odometry needs a non-empty map")
-    with torch.no_grad():
+    differentiable = torch.is_grad_enabled() and depth.requires_grad
+    K, prev_pose = K.detach(), prev_pose.detach()
+    with torch.set_grad_enabled(differentiable):
         maps = fmap.frame_maps(depth, K, prev_pose)
         sub = torch.zeros(H, W, dtype=torch.bool, device=depth.device)
         sub[::dsratio, ::dsratio] = True
-        src = maps["Vg"][0][maps["valid"][0] & sub]
+        keep = maps["valid"][0] & sub
+        src = ops.select_rows(maps["Vg"][0].reshape(-1, 3), keep.reshape(-1)) if differentiable else maps["Vg"][0][keep]
         fmap.associate(maps, K, prev_pose)
         sel = fmap.table("active")[::dsratio, 0]
         if sel.numel() < 6 or src.shape[0] < 6:
             raise RuntimeError("too few points for frame-to-model ICP (no overlap between the live frame and the map)")
-        T, trace = point_to_plane_icp(src, fmap.points[sel], fmap.normals[sel], **kw)
-        pose = torch.from_numpy(T @ prev_pose.detach().double().cpu().numpy()).float().to(depth.device)
+        pose, trace = point_to_plane_icp(src, fmap.points[sel].detach(), fmap.normals[sel].detach(), prev_pose=prev_pose, **kw)
     return pose, trace
 
 

@@ -77,9 +77,16 @@ class _Project3D(torch.autograd.Function):
         g_z = rest[0] if len(rest) == 2 else None
         g_grid = (g_grid if g_grid is not None else torch.zeros(B, H, W, 2, device=p.device)).contiguous()
         g_z = g_z.contiguous() if g_z is not None else None
-        gp = torch.empty_like(p)
-        L.call("e2e_project3d_bwd", L.ptr(p), L.ptr(K), L.ptr(T), L.ptr(g_grid), L.ptr(g_z), L.ptr(gp), B, H, W, L.stream())
-        return gp, None, None, None, None, None
+        gp = gT = None
+        if ctx.needs_input_grad[0]:
+            gp = torch.empty_like(p)
+            L.call("e2e_project3d_bwd", L.ptr(p), L.ptr(K), L.ptr(T), L.ptr(g_grid), L.ptr(g_z), L.ptr(gp), B, H, W, L.stream())
+        if ctx.needs_input_grad[2]:          # the pose carries a graph (differentiable odometry, e2ehip.icp): d/dT through P = (K T)[:3]
+            gT = torch.empty_like(T)
+            ws = torch.empty(L.load().e2e_project3d_bwd_t_workspace_bytes(B), device=p.device, dtype=torch.uint8)
+            L.call("e2e_project3d_bwd_t", points=L.ptr(p), K=L.ptr(K), T=L.ptr(T), g_grid=L.ptr(g_grid), g_z=L.ptr(g_z), g_T=L.ptr(gT),
+                   workspace=L.ptr(ws), B=B, H=H, W=W, stream=L.stream())
+        return gp, None, gT, None, None, None
 
 
 def project3d(points, K, T, height, width, geometric=False):
@@ -308,17 +315,30 @@ class _TransformPoints(torch.autograd.Function):
         T = L.dev(T, "transform").contiguous()
         out = torch.empty_like(p)
         L.call("e2e_transform_points", L.ptr(p), L.ptr(T), L.ptr(out), p.shape[0], 0, L.stream())
-        ctx.save_for_backward(T)
+        ctx.save_for_backward(T, p if ctx.needs_input_grad[1] else None)
         return out
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g):
-        T, = ctx.saved_tensors
+        T, p = ctx.saved_tensors
         g = g.contiguous()
-        gp = torch.empty_like(g)
-        L.call("e2e_transform_points", L.ptr(g), L.ptr(T), L.ptr(gp), g.shape[0], 1, L.stream())
-        return gp, None
+        gp = gT = None
+        if ctx.needs_input_grad[0]:
+            gp = torch.empty_like(g)
+            L.call("e2e_transform_points", L.ptr(g), L.ptr(T), L.ptr(gp), g.shape[0], 1, L.stream())
+        if ctx.needs_input_grad[1]:
+            gT = torch.zeros(4, 4, device=g.device, dtype=torch.float32)
+            gT[:3] = transform_points_bwd_T(g, p).float()
+        return gp, gT
+
+
+def transform_points_bwd_T(g, points):
+    """g, points (n,3) -> (3,4) float64 device tensor [sum_i g_i p_i^T | sum_i g_i]: the top rows of d/dT of sum(g . (R p + t))."""
+    out = torch.empty(3, 4, device=g.device, dtype=torch.float64)
+    ws = torch.empty(L.load().e2e_transform_points_bwd_t_workspace_bytes(), device=g.device, dtype=torch.uint8)
+    L.call("e2e_transform_points_bwd_t", L.ptr(g), L.ptr(points), g.shape[0], L.ptr(out), L.ptr(ws), L.stream())
+    return out
 
 
 def transform_points(points, T):

@@ -3,8 +3,9 @@ re-implemented for MI355X: vertex/normal maps, PointFusion association / fusion 
 HIP kernels (include/e2eslam.h); these classes only carry tensors and call them.
 
 Semantics follow SURVEY.md Appendix A (gradslam is not vendored in the reference: parity unpinned).
-Supported: batch size 1 (OPTIMIZATION.batch_size, configs/config.yaml:60), odom "gt" (or prev_frame=None).
-ICP / GradICP odometry is the next scope row and raises NotImplementedError.
+Supported: batch size 1 (OPTIMIZATION.batch_size, configs/config.yaml:60); odom "gt" (or prev_frame=None), "icp" and "gradicp"
+(frame-to-model point-to-plane ICP, e2ehip.icp).  The estimated pose is differentiable with respect to the live
+frame's depth when that depth requires grad (says what is and is not differentiated).
 """
 from .structures import Pointclouds, RGBDImages  # noqa: F401
 from . import datasets, geometry, slam  # noqa: F401

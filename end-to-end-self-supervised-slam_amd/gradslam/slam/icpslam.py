@@ -18,6 +18,7 @@ class ICPSLAM(nn.Module):
         self.odom, self.dsratio, self.numiters = odom, dsratio, numiters
         self.damp, self.dist_thresh, self.lambda_max, self.B, self.B2, self.nu = damp, dist_thresh, lambda_max, B, B2, nu
         self.device = torch.device(device) if device is not None else torch.device("cpu")
+        self.pose_gradient = True         # False: localise on the detached depth (the pose is a constant of the step)
 
     # -- odometry ------------------------------------------------------------------------------------
     def _localize(self, pointclouds, live_frame, prev_frame):
@@ -42,7 +43,11 @@ class ICPSLAM(nn.Module):
         if not pointclouds.has_points:
             raise ValueError("frame-to-model odometry needs a non-empty map")
         fm = self._resident_map(pointclouds, live_frame)
-        pose, self.last_trace = icp.frame_to_model(fm, live_frame.depth_image[0, 0, ..., 0].detach(), live_frame.intrinsics[0, 0],
+        depth = live_frame.depth_image[0, 0, ..., 0]
+        if not (self.pose_gradient and torch.is_grad_enabled() and depth.requires_grad):
+            depth = depth.detach()
+        # with a depth that requires grad the pose carries the gradient back into it (through the ICP / GradICP iterations)
+        pose, self.last_trace = icp.frame_to_model(fm, depth, live_frame.intrinsics[0, 0],
                                                    prev_frame.poses[0, 0], dsratio=self.dsratio, numiters=self.numiters, damp=self.damp,
                                                    dist_thresh=self.dist_thresh, mode=self.odom, lambda_max=self.lambda_max, B=self.B,
                                                    B2=self.B2, nu=self.nu)

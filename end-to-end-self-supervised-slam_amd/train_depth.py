@@ -59,6 +59,9 @@ class Depth_Estimation:
         if getattr(self.args.VIZ, "tensorboard", False):
             raise NotImplementedError("out of scope: SURVEY.md section 5.5 -- TensorBoard gradient hooks (VIZ.tensorboard)")
         self._sequence, self._state_dict, self.fused_losses = sequence, state_dict, fused_losses
+        # DATA.use_gt_pose: False -- the estimated poses carry the gradient of the loss through the odometry into the predicted depth, as
+        # the reference's do (train_depth.py:381-382, :395).  E2E_POSE_GRAD=0 (or pose_gradient = False): the poses are constants.
+        self.pose_gradient = os.environ.get("E2E_POSE_GRAD", "1") != "0"
         self.dataset_init()
         self.model_init()
         self.view_reconstruction_init()
@@ -220,6 +223,7 @@ class Depth_Estimation:
                     noisy_reconstruction, _ = self.models["SLAM"](noisy_rgbd)
                     new_transform = transform
                 else:
+                    self.models["SLAM"].pose_gradient = self.pose_gradient
                     noisy_reconstruction, new_poses = self.models["SLAM"](noisy_rgbd)
                     new_transform = torch_poses_to_transforms(new_poses)
                 if noisy_reconstruction is not None:
@@ -242,7 +246,7 @@ class Depth_Estimation:
     def depth_refinement(self, colors, inputs, intrinsics, poses):
         outputs = {}
         inputs.update(self.process_inputs(colors, inputs, intrinsics, poses))
-        if self._fused_ok():
+        if self._fused_ok(poses):
             return self.compute_losses_fused(inputs)
         outputs.update(self.novel_view_synthesis(inputs))
         return self.compute_losses(inputs, outputs)
@@ -303,8 +307,10 @@ class Depth_Estimation:
         return outputs
 
     # ---------------------------------------------------------------------------------------------------------------------------
-    def _fused_ok(self):
+    def _fused_ok(self, poses=None):
         lo = self.args.LOSS
+        if poses is not None and poses.requires_grad:      # the fused warp kernel has no gradient for T: poses with a graph take the operators
+            return False
         return self.fused_losses and self.sequence_length == 2 and lo.photometric_mask is not None and not (
             lo.min_reprojection or lo.auto_masking or lo.geometric)
 

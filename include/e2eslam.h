@@ -68,6 +68,13 @@ int e2e_project3d_fwd(const float* points, const float* K, const float* T, float
 /* autograd of the above: g_grid (B,H,W,2), g_z (B,H,W) or NULL -> g_points (B,4,H*W). */
 int e2e_project3d_bwd(const float* points, const float* K, const float* T, const float* g_grid,
                       const float* g_z, float* g_points, int B, int H, int W, void* stream);
+/* the same adjoint with respect to T (entry-point names are lower case throughout this header, hence _bwd_t):
+ * g_T (B,4,4) = d/dT of sum(g_grid . grid) + sum(g_z . z_out).  T enters through P = (K T)[:3,:] only, with the forward's eps, /(W-1), /(H-1) and clamp(1e-3) conventions (no gradient through z_out at or below the
+ * clamp).  The per-pixel terms are the fp32 expressions of e2e_project3d_bwd; their sums are float64 in a fixed order (per-workgroup
+ * partials, then one wave per sum; no atomics).  workspace: e2e_project3d_bwd_t_workspace_bytes(B) bytes. */
+int64_t e2e_project3d_bwd_t_workspace_bytes(int B);
+int e2e_project3d_bwd_t(const float* points, const float* K, const float* T, const float* g_grid,
+                        const float* g_z, float* g_T, void* workspace, int B, int H, int W, void* stream);
 
 /* F.grid_sample(input, grid, mode="bilinear", padding_mode, align_corners) as called at
  * online_adaption.py:431-439,450-453.  input (B,C,Hi,Wi) via strides, grid (B,Ho,Wo,2) contiguous,
@@ -261,6 +268,12 @@ int e2e_vertex_maps_bwd(const float* depth, const float* K, const float* pose, c
  * (n,3) points, T (4,4).  transpose_rotation_only=1 gives R^T p (its autograd wrt the points). */
 int e2e_transform_points(const float* points, const float* T, float* out, int64_t n,
                          int transpose_rotation_only, void* stream);
+/* its autograd wrt T: g (n,3), points (n,3) -> out12 (device float64, a row-major 3x4 block) = [sum_i g_i p_i^T | sum_i g_i], the top
+ * three rows of d/dT (the bottom row of T does not enter).  Float64 sums in a fixed order, no atomics.
+ * workspace: e2e_transform_points_bwd_t_workspace_bytes() bytes. */
+int64_t e2e_transform_points_bwd_t_workspace_bytes(void);
+int e2e_transform_points_bwd_t(const float* g, const float* points, int64_t n, double* out12, void* workspace,
+                               void* stream);
 
 /* PointFusion map step (gradslam update_map_fusion) for ONE live frame against ONE resident map.
  * The map is four capacity-sized arrays (points/normals/colors (cap,3), ccounts (cap)) of which
@@ -727,6 +740,22 @@ int64_t e2e_icp_workspace_bytes(void);
 int e2e_icp_normal_equations(const float* src, const float* tgt, const float* tgt_normals,
                              const long long* idx, const float* dists, float dist_thresh, int64_t n,
                              double* out29, void* workspace, void* stream);
+
+/* THE ADJOINT OF THE ODOMETRY (differentiable ICP / GradICP; the reference back-propagates the photometric loss through the pose into
+ * the live frame's depth, train_depth.py:381-382, :395).  The rule, for the whole iteration sequence:
+ *   - it is taken with respect to the SOURCE points only; target points, target normals and prev_pose are constants;
+ *   - the nearest-neighbour indices, the dist_thresh keep mask and the inlier counts of every search are held fixed;
+ *   - the clipped region of GradICP's gate (|nu delta| >= 60) has zero derivative;
+ *   - the fp32 roundings of the running transform and of the pose are passed straight through.
+ * This entry point is the per-point part for ONE reduction: adj28 (device float64) holds the adjoints of the 21 packed A^T A entries,
+ * of A^T b (6) and of sum b^2, in out29's order (the count has none).  With U the upper-triangular unpacking of adj28[0..20],
+ * Abar_i = (U + U^T) A_i + b_i gbar, bbar_i = gbar . A_i + 2 ebar b_i:   g_src_i = -bbar_i n_i + n_i x Abar_i[3:6]   (n,3) fp32,
+ * added to g_src when accumulate != 0.  A row the forward skipped contributes zero; so does a row whose idx is outside [0, n_tgt), which
+ * reads nothing of the target.  Pointwise: nothing to reduce, bitwise reproducible.  The 6x6 part of the adjoint (solve, exp, damping
+ * update, gate) is float64 on the host, as the forward's is (e2ehip/icp.py). */
+int e2e_icp_normal_equations_bwd(const float* src, const float* tgt, const float* tgt_normals, int64_t n_tgt,
+                                 const long long* idx, const float* dists, float dist_thresh, const double* adj28,
+                                 int64_t n, float* g_src, int accumulate, void* stream);
 
 /* The rest of an odometry iteration ON THE DEVICE (gradslam odometry providers "icp" / "gradicp" behind PointFusion.step,
  * online_adaption.py:111-122,362; configs/config.yaml:30-35 ships odom: gradicp): solve (A^T A + lambda I) xi = A^T b, the
