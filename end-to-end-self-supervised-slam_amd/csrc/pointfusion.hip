@@ -11,10 +11,7 @@
 // capacity-sized arrays points/normals/colors (cap,3) + ccounts (cap) that stay resident in HBM
 // (60 frames x 307 200 px x 40 B = 737 MB << 288 GB), appended in place.
 #include "e2e_common.h"
-
-#define PF_T 256
-#define PF_NONE 0xFFFFFFFFu
-#define PF_KEY_NONE 0xFFFFFFFFFFFFFFFFull
+#include "pf_workspace.h"
 
 struct Pose {          // row-major 4x4 pieces
     float R[9], t[3];
@@ -299,9 +296,6 @@ __global__ __launch_bounds__(PF_T) void k_pf_fuse(float* __restrict__ pts, float
 //   count pass -> k_scan_counts (1 workgroup, exclusive scan + total) -> scatter pass.
 // `pred(i)` is recomputed in both passes from the per-item arrays (cheap), so no flag array is stored.
 // ---------------------------------------------------------------------------------------------
-#define CP_ITEMS 4
-#define CP_BLOCK (PF_T * CP_ITEMS)
-
 enum { PRED_ACTIVE = 0, PRED_SIMILAR = 1, PRED_PIX_MATCHED = 2, PRED_PIX_NEW = 3 };
 
 template <int PRED>
@@ -639,28 +633,6 @@ int64_t e2e_pf_workspace_bytes(int64_t map_capacity, int H, int W) {
     // pix_key u64[N] | pix_best u32[N] | pix_of_point u32[cap] | counts u32[max(nbm,nbp)] | flags u8[cap]
     int64_t b = 8 * N + 4 * N + 4 * map_capacity + 4 * ((nbm > nbp ? nbm : nbp) + 4) + map_capacity;
     return (b + 255) & ~255ll;
-}
-
-struct PfWs {
-    unsigned long long* pix_key;
-    unsigned int* pix_best;
-    unsigned int* pix_of_point;
-    unsigned int* counts;
-    unsigned int* any_match;
-    unsigned char* flags;
-};
-static PfWs pf_ws(void* ws, int64_t cap, int H, int W) {
-    const int64_t N = (int64_t)H * W;
-    const int64_t nbm = (cap + CP_BLOCK - 1) / CP_BLOCK + 1, nbp = (N + CP_BLOCK - 1) / CP_BLOCK + 1;
-    PfWs w;
-    char* p = (char*)ws;
-    w.pix_key = (unsigned long long*)p; p += 8 * N;
-    w.pix_best = (unsigned int*)p; p += 4 * N;
-    w.pix_of_point = (unsigned int*)p; p += 4 * cap;
-    w.counts = (unsigned int*)p; p += 4 * (nbm > nbp ? nbm : nbp);
-    w.any_match = (unsigned int*)p; p += 16;
-    w.flags = (unsigned char*)p;
-    return w;
 }
 
 int e2e_pf_associate(const float* map_points, const float* map_normals, const float* map_ccounts, int64_t M,

@@ -1,0 +1,71 @@
+"""The differentiable form of the PointFusion map step (FusionMap.step_differentiable): the kernels of FusionMap.step plus one tape
+launch in the forward, csrc/pointfusion_grad.hip in the backward.  The differentiation rule is stated in include/e2eslam.h: the
+association, the validity mask, the append order, the pose and the intrinsics are constants, the normals carry no gradient.
+
+Opt-in (gradslam.slam.PointFusion(map_gradient=True)); FusionMap.step, step_resident and the captured driver do not come here."""
+import torch
+from torch.autograd.function import once_differentiable
+
+from . import _lib as L
+from .ops import vertex_normal_maps
+
+
+class _FuseStep(torch.autograd.Function):
+    """(Vg, rgb, alpha of the live frame; points, colors, ccounts of the map before the step) -> the same three of the map after it.
+    The resident map `fm` holds the values of the previous map (the three tensors are its autograd handles) and is advanced in place;
+    the outputs are copies of its live rows, so a later step cannot change what autograd or the caller holds."""
+
+    @staticmethod
+    def forward(ctx, Vg, rgb, alpha, prev_points, prev_colors, prev_ccounts, fm, maps, depth, K, pose):
+        M0, H, W = fm.M, fm.H, fm.W
+        for n, t, shape in (("prev_points", prev_points, (M0, 3)), ("prev_colors", prev_colors, (M0, 3)), ("prev_ccounts", prev_ccounts, (M0,))):
+            if tuple(t.shape) != shape:
+                raise ValueError(f"{n}: expected {shape} (the resident map has {M0} rows), got {tuple(t.shape)}")
+        rgb, depth = L.dev(rgb, "rgb").contiguous(), L.dev(depth, "depth").contiguous()
+        tape = torch.empty(L.query("e2e_pf_fuse_tape_bytes", H, W), device=fm.device, dtype=torch.uint8)
+        fm.associate(maps, K, pose)
+        L.call("e2e_pf_fuse_tape", map_points=L.ptr(fm.points), map_colors=L.ptr(fm.colors), map_ccounts=L.ptr(fm.ccounts), M=M0,
+               map_capacity=fm.cap, depth=L.ptr(depth), workspace=L.ptr(fm.ws), H=H, W=W, tape=L.ptr(tape), stream=L.stream())
+        fm.fuse_append(maps, rgb, depth)
+        P, C, cc = fm.points[:fm.M].clone(), fm.colors[:fm.M].clone(), fm.ccounts[:fm.M].clone()
+        ctx.save_for_backward(tape, maps["Vg"], rgb, maps["alpha"], cc)
+        ctx.sizes = (M0, fm.M, H, W)
+        ctx.set_materialize_grads(False)
+        return P, C, cc
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gP, gC, gcc):
+        tape, Vg, rgb, alpha, cc = ctx.saved_tensors
+        M0, M1, H, W = ctx.sizes
+        if gP is None and gC is None and gcc is None:
+            return (None,) * 11
+        f = dict(device=Vg.device, dtype=torch.float32)
+        need = ctx.needs_input_grad
+        out = [torch.empty(shape, **f) if n else None
+               for n, shape in zip(need[:6], ((H, W, 3), (H, W, 3), (H, W), (M0, 3), (M0, 3), (M0,)))]
+        if any(o is not None for o in out):
+            gP, gC, gcc = (g.contiguous() if g is not None else None for g in (gP, gC, gcc))
+            L.call("e2e_pf_fuse_bwd", tape=L.ptr(tape), Vg=L.ptr(Vg), rgb=L.ptr(rgb), alpha=L.ptr(alpha), g_points=L.ptr(gP), g_colors=L.ptr(gC),
+                   g_ccounts=L.ptr(gcc), ccounts_after=L.ptr(cc), M_before=M0, M_after=M1, g_Vg=L.ptr(out[0]), g_rgb=L.ptr(out[1]),
+                   g_alpha=L.ptr(out[2]), g_prev_points=L.ptr(out[3]), g_prev_colors=L.ptr(out[4]), g_prev_ccounts=L.ptr(out[5]), H=H, W=W,
+                   stream=L.stream())
+        return (*out, None, None, None, None, None)
+
+
+def step_differentiable(self, rgb, depth, K, pose, prev=None):
+    """FusionMap.step_differentiable (self: the FusionMap): step() with a graph.  rgb (H,W,3), depth (H,W), K / pose (4,4);
+    prev = (points (M,3), colors (M,3), ccounts (M,) or (M,1)): the tensors that stand for the map before the step in the caller's
+    graph (their VALUES are the resident rows; None: the map is a constant).  -> points, normals, colors (M',3), ccounts (M'): tensors of
+    their own, copied out of the live rows; forward values and the resident state are those of step(), bit for bit.  points / colors /
+    ccounts carry the gradient to depth, rgb and prev; the normals carry none."""
+    M0 = self.M
+    if prev is None:
+        prev = (self.points[:M0], self.colors[:M0], self.ccounts[:M0])
+    prev_points, prev_colors, prev_ccounts = prev
+    maps = vertex_normal_maps(depth.reshape(1, self.H, self.W), K.reshape(1, 4, 4), pose.reshape(1, 4, 4), self.sigma, alpha_grad=True)
+    detached = {k: v.detach() for k, v in maps.items()}
+    P, C, cc = _FuseStep.apply(maps["Vg"][0], rgb, maps["alpha"][0], prev_points, prev_colors, prev_ccounts.reshape(-1), self, detached,
+                               depth.detach(), K, pose)
+    return P, self.normals[:self.M].clone(), C, cc
+

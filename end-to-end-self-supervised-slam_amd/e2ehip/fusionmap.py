@@ -127,6 +127,12 @@ class FusionMap:
             self.fuse_append(maps, rgb, depth)
         return maps
 
+    def step_differentiable(self, rgb, depth, K, pose, prev=None):
+        """step() as an autograd Function (e2ehip/fusion_grad.py): -> points, normals, colors, ccounts after the step as tensors of their
+        own; points / colors / ccounts carry the gradient to depth, rgb and `prev` (the previous map's tensors in the caller's graph)."""
+        from .fusion_grad import step_differentiable
+        return step_differentiable(self, rgb, depth, K, pose, prev)
+
     def step_resident(self, rgb, depth, K, pose):
         """The same map step without any host read or allocation: frame maps into preallocated buffers, association / fusion /
         append with the live size taken from (and written back to) `count` on the device.  rgb (H,W,3), depth (H,W), K / pose (4,4):

@@ -272,7 +272,7 @@ def fusion_alpha_den(sigma, eps=1e-7):
 
 class _VertexMaps(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, depth, K, pose, alpha_den):
+    def forward(ctx, depth, K, pose, alpha_den, alpha_grad=False):
         B, H, W = depth.shape
         d = L.dev(depth, "depth").contiguous()
         K, pose = _mat(K, "intrinsics", B), _mat(pose, "poses", B)
@@ -281,30 +281,43 @@ class _VertexMaps(torch.autograd.Function):
         alpha = torch.empty(B, H, W, **f)
         L.call("e2e_vertex_normal_maps", depth=L.ptr(d), K=L.ptr(K), pose=L.ptr(pose), alpha_den=float(alpha_den), V=L.ptr(V), Nm=L.ptr(Nm), Vg=L.ptr(Vg),
                Ng=L.ptr(Ng), alpha=L.ptr(alpha), B=B, H=H, W=W, stream=L.stream())
-        ctx.save_for_backward(d, K, pose)
-        ctx.mark_non_differentiable(Nm, Ng, alpha)
+        ctx.alpha_den = float(alpha_den) if alpha_grad else None
+        if alpha_grad:
+            ctx.save_for_backward(d, K, pose, alpha)
+            ctx.mark_non_differentiable(Nm, Ng)
+            ctx.set_materialize_grads(False)              # a map step that only moves confidences sends no g_Vg
+        else:
+            ctx.save_for_backward(d, K, pose)
+            ctx.mark_non_differentiable(Nm, Ng, alpha)
         return V, Nm, Vg, Ng, alpha
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gV, gN, gVg, gNg, ga):
-        d, K, pose = ctx.saved_tensors
+        d, K, pose = ctx.saved_tensors[:3]
         B, H, W = d.shape
-        if gV is None and gVg is None:
-            return None, None, None, None
-        gV = gV.contiguous() if gV is not None else None
-        gVg = gVg.contiguous() if gVg is not None else None
+        if ctx.alpha_den is None:
+            ga = None
+        if gV is None and gVg is None and ga is None:
+            return None, None, None, None, None
         gd = torch.empty_like(d)
-        L.call("e2e_vertex_maps_bwd", L.ptr(d), L.ptr(K), L.ptr(pose), L.ptr(gV), L.ptr(gVg), L.ptr(gd), B, H, W, L.stream())
-        return gd, None, None, None
+        if gV is not None or gVg is not None:
+            gV = gV.contiguous() if gV is not None else None
+            gVg = gVg.contiguous() if gVg is not None else None
+            L.call("e2e_vertex_maps_bwd", L.ptr(d), L.ptr(K), L.ptr(pose), L.ptr(gV), L.ptr(gVg), L.ptr(gd), B, H, W, L.stream())
+        if ga is not None:
+            L.call("e2e_vertex_alpha_bwd", depth=L.ptr(d), K=L.ptr(K), alpha=L.ptr(ctx.saved_tensors[3]), g_alpha=L.ptr(ga.contiguous()),
+                   alpha_den=ctx.alpha_den, g_depth=L.ptr(gd), accumulate=int(gV is not None or gVg is not None), B=B, H=H, W=W, stream=L.stream())
+        return gd, None, None, None, None
 
 
-def vertex_normal_maps(depth, K, pose, sigma=0.6):
+def vertex_normal_maps(depth, K, pose, sigma=0.6, alpha_grad=False):
     """depth (B,H,W), K/pose (B,4,4) -> dict V, n, Vg, ng (B,H,W,3), alpha (B,H,W), valid (B,H,W) bool.
-    gradslam RGBDImages maps; differentiable wrt depth through V and Vg."""
+    gradslam RGBDImages maps; differentiable wrt depth through V and Vg, and -- with alpha_grad=True only --
+    through the fusion confidence alpha (e2e_vertex_alpha_bwd).  The normals are not differentiated."""
     if depth.dim() != 3:
         raise ValueError(f"depth: expected (B,H,W), got {tuple(depth.shape)}")
-    V, Nm, Vg, Ng, alpha = _VertexMaps.apply(depth, K, pose, fusion_alpha_den(sigma))
+    V, Nm, Vg, Ng, alpha = _VertexMaps.apply(depth, K, pose, fusion_alpha_den(sigma), bool(alpha_grad))
     return {"V": V, "n": Nm, "Vg": Vg, "ng": Ng, "alpha": alpha, "valid": depth.detach() != 0}
 
 

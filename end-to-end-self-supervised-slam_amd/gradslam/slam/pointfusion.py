@@ -1,15 +1,17 @@
+import torch
+
 from ..structures import Pointclouds
 from .icpslam import ICPSLAM
 
 
-def frame_as_pointcloud(frame):
+def frame_as_pointcloud(frame, alpha_grad=False):
     """All valid-depth pixels of a 1-frame RGBDImages as a Pointclouds (row-major order), differentiable wrt
-    depth through the global vertex map.  This is what PointFusion.step returns for an EMPTY map
-    (online_adaption.py:461-469) and what ICPSLAM's aggregation appends."""
+    depth through the global vertex map (alpha_grad: and through the confidences in features_list).  This is what
+    PointFusion.step returns for an EMPTY map (online_adaption.py:461-469) and what ICPSLAM's aggregation appends."""
     B, L, H, W = frame.shape
     if L != 1:
         raise ValueError(f"Expected a frame with sequence length 1. Got {L}.")
-    m = frame._maps()
+    m = frame._maps(alpha_grad=True) if alpha_grad else frame._maps()
     pts, nrm, col, feat = [], [], [], []
     for b in range(B):
         keep = m["valid"][b, 0, ..., 0] if m["valid"].dim() == 5 else m["valid"][b, 0]
@@ -25,10 +27,16 @@ class PointFusion(ICPSLAM):
 
     The global map lives in a resident e2ehip.FusionMap (capacity-sized HBM arrays, appended in place); the
     returned Pointclouds exposes zero-copy views of its live rows.  `map_capacity` points are reserved on
-    first use (default: 64 frames' worth)."""
+    first use (default: 64 frames' worth).
+
+    map_gradient (default False): the map update is differentiable (FusionMap.step_differentiable; the rule is stated in
+    include/e2eslam.h).  Points, colours and confidences of the returned cloud then carry a gradient to the live frame's depth and
+    rgb and, through the incoming cloud's lists, to the frames fused before; they are tensors of their own instead of views.  The
+    association, the poses and the intrinsics are constants, the normals carry no gradient.  Taken only while grad mode is on and the
+    live depth, the live rgb or one of the incoming lists requires grad; otherwise, and with the switch off, the step is the plain one."""
 
     def __init__(self, *, odom="gradicp", dist_th=0.05, angle_th=20, sigma=0.6, dsratio=4, numiters=20, damp=1e-8, dist_thresh=None,
-                 lambda_max=2.0, B=1.0, B2=1.0, nu=200.0, device=None, map_capacity=None):
+                 lambda_max=2.0, B=1.0, B2=1.0, nu=200.0, device=None, map_capacity=None, map_gradient=False):
         super().__init__(odom=odom, dsratio=dsratio, numiters=numiters, damp=damp, dist_thresh=dist_thresh, lambda_max=lambda_max,
                          B=B, B2=B2, nu=nu, device=device)
         if not isinstance(dist_th, (float, int)):
@@ -41,17 +49,27 @@ class PointFusion(ICPSLAM):
             raise ValueError(f"Angle threshold must be in [0, 90]: {angle_th}")
         self.dist_th, self.angle_th, self.sigma = dist_th, angle_th, sigma
         self.map_capacity = map_capacity
+        self.map_gradient = bool(map_gradient)
 
     def _map(self, pointclouds, live_frame, inplace=False):
         if len(pointclouds) > 1 or live_frame.shape[0] != 1:
             raise NotImplementedError("batch size 1 only (OPTIMIZATION.batch_size, configs/config.yaml:60)")
         _, _, H, W = live_frame.shape
+        rgb, depth = live_frame.rgb_image[0, 0], live_frame.depth_image[0, 0, ..., 0]
+        lists = [l[0] for l in (pointclouds.points_list, pointclouds.colors_list, pointclouds.features_list) if l]
+        with_graph = self.map_gradient and torch.is_grad_enabled() and any(t.requires_grad for t in [depth, rgb] + lists)
         if not pointclouds.has_points:
             # empty map: nothing to associate with -> the frame's valid pixels, still attached to the autograd
             # graph of the depth (the 3-D loss differentiates through this: online_adaption.py:461-469,638-645)
-            out = frame_as_pointcloud(live_frame)
+            out = frame_as_pointcloud(live_frame, alpha_grad=with_graph)
             return out
         fm = self._resident_map(pointclouds, live_frame)      # adopts an externally built cloud once
+        if with_graph:
+            P, Nn, C, cc = fm.step_differentiable(rgb, depth, live_frame.intrinsics[0, 0], live_frame.poses[0, 0],
+                                                  prev=(pointclouds.points_list[0], pointclouds.colors_list[0], pointclouds.features_list[0]))
+            out = Pointclouds([P], [Nn], [C], [cc.reshape(-1, 1)], device=live_frame.device)
+            out._fusion_maps = fm
+            return out
         fm.step(live_frame.rgb_image[0, 0].detach(), live_frame.depth_image[0, 0, ..., 0].detach(),
                 live_frame.intrinsics[0, 0], live_frame.poses[0, 0])
         P, Nn, C, cc = fm.live()

@@ -87,13 +87,18 @@ class RGBDImages:
         return self._poses is not None
 
     # ---- maps --------------------------------------------------------------------------------------
-    def _maps(self):
-        if self._cache is None:
+    def _maps(self, alpha_grad=False):
+        """alpha_grad: the fusion confidence carries a gradient to the depth as well (PointFusion(map_gradient=True)); the same values,
+        computed apart from the cache."""
+        if self._cache is None or alpha_grad:
             B, L, H, W = self.shape
             K = self._K.expand(B, L, 4, 4).reshape(B * L, 4, 4)
             poses = self._poses if self._poses is not None else torch.eye(4, device=self.device).expand(B, L, 4, 4)
-            m = ops.vertex_normal_maps(self._depth.reshape(B * L, H, W), K, poses.reshape(B * L, 4, 4))
-            self._cache = {k: (v.reshape((B, L) + tuple(v.shape[1:])) if v.dim() == 4 else v.reshape(B, L, H, W, 1)) for k, v in m.items()}
+            m = ops.vertex_normal_maps(self._depth.reshape(B * L, H, W), K, poses.reshape(B * L, 4, 4), alpha_grad=alpha_grad)
+            m = {k: (v.reshape((B, L) + tuple(v.shape[1:])) if v.dim() == 4 else v.reshape(B, L, H, W, 1)) for k, v in m.items()}
+            if alpha_grad:
+                return m
+            self._cache = m
         return self._cache
 
     @property

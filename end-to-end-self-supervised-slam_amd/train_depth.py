@@ -62,6 +62,10 @@ class Depth_Estimation:
         # DATA.use_gt_pose: False -- the estimated poses carry the gradient of the loss through the odometry into the predicted depth, as
         # the reference's do (train_depth.py:381-382, :395).  E2E_POSE_GRAD=0 (or pose_gradient = False): the poses are constants.
         self.pose_gradient = os.environ.get("E2E_POSE_GRAD", "1") != "0"
+        # MODEL.slam: PointFusion with LOSS.knn_points / chamfer_distance -- the reference takes the 3-D loss on the reconstruction of the
+        # whole predicted-depth sequence (train_depth.py:378-385), so every frame's depth gets a gradient through the fusion.  E2E_MAP_GRAD=1
+        # (or map_gradient = True) differentiates the map update; default off: only the frame that met the empty map gets one.
+        self.map_gradient = os.environ.get("E2E_MAP_GRAD", "0") == "1"
         self.dataset_init()
         self.model_init()
         self.view_reconstruction_init()
@@ -220,10 +224,12 @@ class Depth_Estimation:
                     # (:682-695); with ground-truth poses the reconstruction has no other consumer, so it is skipped
                     noisy_reconstruction, new_transform = None, transform
                 elif a.DATA.use_gt_pose:
+                    self.models["SLAM"].map_gradient = self.map_gradient
                     noisy_reconstruction, _ = self.models["SLAM"](noisy_rgbd)
                     new_transform = transform
                 else:
                     self.models["SLAM"].pose_gradient = self.pose_gradient
+                    self.models["SLAM"].map_gradient = self.map_gradient
                     noisy_reconstruction, new_poses = self.models["SLAM"](noisy_rgbd)
                     new_transform = torch_poses_to_transforms(new_poses)
                 if noisy_reconstruction is not None:

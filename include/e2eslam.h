@@ -337,6 +337,56 @@ int e2e_frame_append_dev(float* map_points, float* map_normals, float* map_color
                          long long* map_count_dev, int64_t map_capacity, const float* depth, const float* rgb,
                          const float* K, const float* pose, float alpha_den, void* workspace, int H, int W, void* stream);
 
+/* DIFFERENTIABLE MAP STEP (opt-in: gradslam.slam.PointFusion(map_gradient=True), E2E_MAP_GRAD=1 for train_depth.py).  gradslam exists so
+ * that the fused map is differentiable with respect to the frames that built it (train_depth.py:378-385 takes the 3-D loss on the
+ * reconstruction of the predicted depths; gradient_experiments.py:132-161 optimises pixels through slam/custom_slam.py's cloud).
+ *
+ * Differentiation rule.  CONSTANTS: the association (the active / similar / unique tables), the validity mask, the append order, the
+ * pose and the intrinsics.  The normals are not differentiated: their rows come back without a gradient, as for e2e_vertex_maps_bwd.
+ * DIFFERENTIATED: the step's output points, colors and ccounts, with respect to the live frame's depth and rgb and to the previous
+ * map's points, colors and ccounts (which is what carries a gradient through a chain of steps back to earlier frames).
+ * Take a pixel q with a = alpha[q].  It is appended as row r, or fused into its winner row n; c, P, C are the winner's values before the
+ * step, s = c + a, P', C' the fused row (P' = (c P + a Vg[q]) / s: the arithmetic of the forward).  gP, gC, gcc: the gradients of the
+ * step's outputs.
+ *   appended:  g_Vg[q] = gP[r]        g_rgb[q] = gC[r]        g_alpha[q] = gcc[r]
+ *   fused:     g_Vg[q] = (a/s) gP[n]  g_rgb[q] = (a/s) gC[n]  g_alpha[q] = gcc[n] + (gP[n].(Vg[q] - P') + gC[n].(rgb[q] - C')) / s
+ *              g_prevP[n] = (c/s) gP[n]   g_prevC[n] = (c/s) gC[n]   g_prevcc[n] = gcc[n] + (gP[n].(P - P') + gC[n].(C - C')) / s
+ *              (s == 0, where the forward divides by 1: g_alpha[q] = gcc[n] + gP[n].Vg[q] + gC[n].rgb[q], g_prevcc[n] = gcc[n] + gP[n].P +
+ *              gC[n].C, the other four are 0)
+ *   a map row that won no pixel passes its gradient through unchanged -- except that a zero-confidence row in a step where anything
+ *   matched has its point and colour zeroed by the forward and gets 0 for them (its confidence gradient still passes through: c X /
+ *   where(c == 0, 1, c) jumps at c = 0 and has no derivative there);
+ *   invalid pixels and pixels dropped beyond the capacity get 0.
+ * The frame side reaches the depth two ways: g_Vg through e2e_vertex_maps_bwd (Vg = R V + t), g_alpha through e2e_vertex_alpha_bwd.
+ * One pixel owns one row and one row is won by at most one pixel: a gather over pixels, no atomics, bitwise reproducible.
+ * Not differentiated (yet): the pose of the map step (e2e_transform_points_bwd_t would supply it), the normals; single sequence only;
+ * the resident forms (e2e_*_dev) have no tape.
+ *
+ * e2e_pf_fuse_tape runs BETWEEN e2e_pf_associate and e2e_pf_fuse_append on the same workspace and map (the forward fuses in place) and
+ *   records per pixel what the backward needs: the destination row as int64 (winner n, appended row, or -1) and, for a fused pixel, the
+ *   winner's ccount, point and colour before the step.  The appended-row numbering is RECOMPUTED with the same ordered scan as
+ *   e2e_pf_fuse_append's (pixels with depth != 0 and no winner, row-major; rows at or beyond map_capacity are dropped: -1), not read from
+ *   the workspace -- the forward's offsets do not exist yet when the tape is taken.  tape: e2e_pf_fuse_tape_bytes(H, W) bytes, O(H*W)
+ *   whatever the size of the map.
+ * e2e_pf_fuse_bwd: tape, the frame's Vg / rgb (H,W,3) and alpha (H,W), the step's output gradients g_points / g_colors (M_after,3) and
+ *   g_ccounts (M_after) -- each may be NULL = zero -- and the map sizes before and after the step  ->  g_Vg, g_rgb (H,W,3), g_alpha (H,W),
+ *   g_prev_points, g_prev_colors (M_before,3), g_prev_ccounts (M_before).  Every output may be NULL (not wanted), not all of them.
+ *   ccounts_after: the ccounts after the step (at least M_before rows; for a row that won no pixel that is its confidence before the
+ *   step); needed when g_prev_points or g_prev_colors is wanted and M_before > 0.  One streaming pass over the M_before rows (skipped
+ *   when no g_prev_* is wanted), then one pass over the pixels.
+ * e2e_vertex_alpha_bwd: g_depth (+)= g_alpha * d alpha / d depth with alpha = exp(-|V|^2 / alpha_den), V = Kinv [w, h, 1] depth:
+ *   -2 |Kinv [w, h, 1]|^2 depth alpha / alpha_den for a valid pixel, 0 where depth == 0.  alpha: the forward's output.  accumulate = 1
+ *   adds to g_depth (after e2e_vertex_maps_bwd on the same buffer), 0 overwrites it.  depth, alpha, g_alpha, g_depth (B,H,W); K (B,4,4). */
+int64_t e2e_pf_fuse_tape_bytes(int H, int W);
+int e2e_pf_fuse_tape(const float* map_points, const float* map_colors, const float* map_ccounts, int64_t M, int64_t map_capacity,
+                     const float* depth, void* workspace, int H, int W, void* tape, void* stream);
+int e2e_pf_fuse_bwd(const void* tape, const float* Vg, const float* rgb, const float* alpha, const float* g_points,
+                    const float* g_colors, const float* g_ccounts, const float* ccounts_after, int64_t M_before, int64_t M_after,
+                    float* g_Vg, float* g_rgb, float* g_alpha, float* g_prev_points, float* g_prev_colors, float* g_prev_ccounts,
+                    int H, int W, void* stream);
+int e2e_vertex_alpha_bwd(const float* depth, const float* K, const float* alpha, const float* g_alpha, float alpha_den,
+                         float* g_depth, int accumulate, int B, int H, int W, void* stream);
+
 /* ------------------------------------------------------------------------------------------ */
 /* chamferdist.knn_points, K = 1, D = 3 (loss/losses.py:3,57)                                   */
 /* ------------------------------------------------------------------------------------------ */
