@@ -1,6 +1,7 @@
 """The differentiable form of the PointFusion map step (FusionMap.step_differentiable): the kernels of FusionMap.step plus one tape
 launch in the forward, csrc/pointfusion_grad.hip in the backward.  The differentiation rule is stated in include/e2eslam.h: the
-association, the validity mask, the append order, the pose and the intrinsics are constants, the normals carry no gradient.
+association, the validity mask, the append order, the pose (unless pose_gradient) and the intrinsics are constants, the normals carry no
+gradient.
 
 Opt-in (gradslam.slam.PointFusion(map_gradient=True)); FusionMap.step, step_resident and the captured driver do not come here."""
 import torch
@@ -53,17 +54,21 @@ class _FuseStep(torch.autograd.Function):
         return (*out, None, None, None, None, None)
 
 
-def step_differentiable(self, rgb, depth, K, pose, prev=None):
+def step_differentiable(self, rgb, depth, K, pose, prev=None, pose_gradient=False):
     """FusionMap.step_differentiable (self: the FusionMap): step() with a graph.  rgb (H,W,3), depth (H,W), K / pose (4,4);
     prev = (points (M,3), colors (M,3), ccounts (M,) or (M,1)): the tensors that stand for the map before the step in the caller's
     graph (their VALUES are the resident rows; None: the map is a constant).  -> points, normals, colors (M',3), ccounts (M'): tensors of
     their own, copied out of the live rows; forward values and the resident state are those of step(), bit for bit.  points / colors /
-    ccounts carry the gradient to depth, rgb and prev; the normals carry none."""
+    ccounts carry the gradient to depth, rgb and prev; the normals carry none.  pose_gradient (the chain gradient): the points also
+    carry the gradient to a pose that requires grad, through Vg = R V + t; off, such a pose is a constant, as it is for the association
+    either way."""
     M0 = self.M
+    pose_var = pose if pose_gradient else pose.detach()
+    pose = pose.detach()
     if prev is None:
         prev = (self.points[:M0], self.colors[:M0], self.ccounts[:M0])
     prev_points, prev_colors, prev_ccounts = prev
-    maps = vertex_normal_maps(depth.reshape(1, self.H, self.W), K.reshape(1, 4, 4), pose.reshape(1, 4, 4), self.sigma, alpha_grad=True)
+    maps = vertex_normal_maps(depth.reshape(1, self.H, self.W), K.reshape(1, 4, 4), pose_var.reshape(1, 4, 4), self.sigma, alpha_grad=True)
     detached = {k: v.detach() for k, v in maps.items()}
     P, C, cc = _FuseStep.apply(maps["Vg"][0], rgb, maps["alpha"][0], prev_points, prev_colors, prev_ccounts.reshape(-1), self, detached,
                                depth.detach(), K, pose)

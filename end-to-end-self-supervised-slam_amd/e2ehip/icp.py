@@ -118,12 +118,18 @@ def _icp_loop(src, tgt, tgt_n, numiters, damp, dist_thresh, mode, lambda_max, B,
     return T, trace
 
 
-def _icp_backward(src, tgt, tgt_n, recs, Tbar, dist_thresh, mode, lambda_max, B, B2, nu):
-    """The iterations in reverse (the rule of include/e2eslam.h: searches, keep masks and counts fixed; targets constant).  Tbar (4,4)
-    float64: the adjoint of the final transform.  -> d/d src (n,3) fp32."""
+def _icp_backward(src, tgt, tgt_n, recs, Tbar, dist_thresh, mode, lambda_max, B, B2, nu, want_tgt=False, want_tgt_n=False):
+    """The iterations in reverse (the rule of include/e2eslam.h: searches, keep masks and counts fixed).  Tbar (4,4) float64: the
+    adjoint of the final transform.  -> d/d src (n,3) fp32, and d/d tgt, d/d tgt_n (m,3) fp32 where wanted (None otherwise): the
+    targets are not moved by the running transform, so every reduction of every iteration adds into the same pair."""
     dev, n, st = src.device, src.shape[0], L.stream()
     thresh = -1.0 if dist_thresh is None else float(dist_thresh)
     g_src = torch.zeros_like(src)
+    g_tgt = torch.zeros_like(tgt) if want_tgt else None
+    g_tgt_n = torch.zeros_like(tgt_n) if want_tgt_n else None
+    tgt_ws = None
+    if want_tgt or want_tgt_n:
+        tgt_ws = torch.empty(L.query("e2e_icp_normal_equations_bwd_tgt_workspace_bytes", n, tgt.shape[0]), device=dev, dtype=torch.uint8)
     cur, nxt, g_cur, g_nxt, tmp = (torch.empty_like(src) for _ in range(5))
     lambar = 0.0
     Tbar = np.array(Tbar, np.float64)
@@ -132,6 +138,10 @@ def _icp_backward(src, tgt, tgt_n, recs, Tbar, dist_thresh, mode, lambda_max, B,
         adj = torch.from_numpy(adj).to(dev)
         L.call("e2e_icp_normal_equations_bwd", src=L.ptr(pts), tgt=L.ptr(tgt), tgt_normals=L.ptr(tgt_n), n_tgt=tgt.shape[0], idx=L.ptr(idx),
                dists=L.ptr(d), dist_thresh=thresh, adj28=L.ptr(adj), n=n, g_src=L.ptr(g), accumulate=int(accumulate), stream=st)
+        if tgt_ws is not None:
+            L.call("e2e_icp_normal_equations_bwd_tgt", src=L.ptr(pts), tgt=L.ptr(tgt), tgt_normals=L.ptr(tgt_n), n_tgt=tgt.shape[0], idx=L.ptr(idx),
+                   dists=L.ptr(d), dist_thresh=thresh, adj28=L.ptr(adj), n=n, g_tgt=L.ptr(g_tgt), g_tgt_normals=L.ptr(g_tgt_n), accumulate=1,
+                   workspace=L.ptr(tgt_ws), stream=st)
 
     def dT(g, pts):
         full = np.zeros((4, 4))
@@ -183,20 +193,22 @@ def _icp_backward(src, tgt, tgt_n, recs, Tbar, dist_thresh, mode, lambda_max, B,
         Tbar = Tbar + dT(g_cur, src)
         L.call("e2e_transform_points", L.ptr(g_cur), L.ptr(T32), L.ptr(tmp), n, 1, st)
         g_src += tmp
-    return g_src
+    return g_src, g_tgt, g_tgt_n
 
 
 class _DifferentiableICP(torch.autograd.Function):
     """forward: the launch sequence and host arithmetic of _icp_loop (values bit-identical to the plain call), recording each iteration;
-    backward: _icp_backward.  Output: T (4,4) float64, or with prev_pose the pose fl32(T . prev_pose)."""
+    backward: _icp_backward, plus T^T gbar for prev_pose.  Output: T (4,4) float64, or with prev_pose the pose fl32(T . prev_pose).
+    tgt, tgt_n and prev_pose get a gradient only when they require one (point_to_plane_icp detaches them unless target_gradient)."""
 
     @staticmethod
     def forward(ctx, src, tgt, tgt_n, prev_pose, cfg, holder):
-        T, trace = _icp_loop(src, tgt, tgt_n, record=True, **cfg)
+        T, trace = _icp_loop(src, tgt.detach(), tgt_n.detach(), record=True, **cfg)
         holder.append(trace)
         ctx.save_for_backward(src, tgt, tgt_n)
         ctx.recs, ctx.cfg = trace.iterations, cfg
         ctx.prev = None if prev_pose is None else prev_pose.detach().double().cpu().numpy()
+        ctx.T = T
         if prev_pose is None:
             return torch.from_numpy(T).to(src.device)
         return torch.from_numpy(T @ ctx.prev).float().to(src.device)
@@ -206,27 +218,35 @@ class _DifferentiableICP(torch.autograd.Function):
     def backward(ctx, g):
         src, tgt, tgt_n = ctx.saved_tensors
         Tbar = g.double().cpu().numpy()
+        g_prev = None
         if ctx.prev is not None:
+            if ctx.needs_input_grad[3]:
+                g_prev = torch.from_numpy(ctx.T.T @ Tbar).float().to(g.device)
             Tbar = Tbar @ ctx.prev.T
         c = ctx.cfg
-        g_src = _icp_backward(src, tgt, tgt_n, ctx.recs, Tbar, c["dist_thresh"], c["mode"], c["lambda_max"], c["B"], c["B2"], c["nu"])
-        return g_src, None, None, None, None, None
+        g_src, g_tgt, g_tgt_n = _icp_backward(src, tgt, tgt_n, ctx.recs, Tbar, c["dist_thresh"], c["mode"], c["lambda_max"], c["B"], c["B2"], c["nu"],
+                                              want_tgt=ctx.needs_input_grad[1], want_tgt_n=ctx.needs_input_grad[2])
+        return g_src if ctx.needs_input_grad[0] else None, g_tgt, g_tgt_n, g_prev, None, None
 
 
 def point_to_plane_icp(src, tgt, tgt_n, numiters=20, damp=1e-8, dist_thresh=None, mode="icp", lambda_max=2.0, B=1.0, B2=1.0, nu=200.0,
-                       prev_pose=None):
+                       prev_pose=None, target_gradient=False):
     """src (Ns,3), tgt / tgt_n (Nt,3) device tensors -> 4x4 float64 numpy transform aligning src to tgt, plus a trace.
     When src requires grad (and grad mode is on) the transform is a (4,4) float64 DEVICE tensor of the same values that carries the
     gradient to src (the adjoint stated in include/e2eslam.h; targets are constants), and the trace holds the recorded iterations
-    (Trace.iterations).  prev_pose (4,4): return the pose fl32(T . prev_pose) as a float32 device tensor instead of T."""
+    (Trace.iterations).  prev_pose (4,4): return the pose fl32(T . prev_pose) as a float32 device tensor instead of T.
+    target_gradient: tgt, tgt_n and prev_pose are variables too (the chain gradient): the call is differentiable when any of the four
+    requires grad, and the result carries the gradient to each that does.  The values do not depend on the switch."""
     if mode not in ("icp", "gradicp"):
         raise ValueError(f"unknown odometry mode {mode}")
     cfg = dict(numiters=numiters, damp=damp, dist_thresh=dist_thresh, mode=mode, lambda_max=lambda_max, B=B, B2=B2, nu=nu)
-    differentiable = torch.is_grad_enabled() and src.requires_grad
+    if not target_gradient:
+        tgt, tgt_n, prev_pose = tgt.detach(), tgt_n.detach(), None if prev_pose is None else prev_pose.detach()
+    differentiable = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (src, tgt, tgt_n, prev_pose))
     src, tgt, tgt_n = (L.dev(t, n).contiguous() for t, n in ((src, "src"), (tgt, "tgt"), (tgt_n, "tgt_normals")))
     if differentiable:
         holder = []
-        out = _DifferentiableICP.apply(src, tgt.detach(), tgt_n.detach(), prev_pose, cfg, holder)
+        out = _DifferentiableICP.apply(src, tgt, tgt_n, prev_pose, cfg, holder)
         return out, holder[0]
     with torch.no_grad():
         T, trace = _icp_loop(src, tgt, tgt_n, **cfg)
@@ -235,17 +255,28 @@ def point_to_plane_icp(src, tgt, tgt_n, numiters=20, damp=1e-8, dist_thresh=None
     return T, trace
 
 
-def frame_to_model(fmap, depth, K, prev_pose, dsratio=4, **kw):
+def frame_to_model(fmap, depth, K, prev_pose, dsratio=4, map_tensors=None, prev_pose_gradient=False, **kw):
     """PointFusion._localize: pose of the live frame (depth (H,W)) given the resident map `fmap` (e2ehip.FusionMap)
     and the previous frame's pose.  Returns a (4,4) float32 device tensor and the iteration trace.  When depth requires grad (and grad
-    mode is on) the pose carries the gradient to the depth: through the source points only -- the map and prev_pose are constants."""
+    mode is on) the pose carries the gradient to the depth: through the source points only -- by default the map and prev_pose are
+    constants.  The chain gradient: map_tensors = (points, normals), the caller's graph-bearing tensors whose VALUES are the resident
+    rows, make the targets variables; prev_pose_gradient keeps prev_pose attached (it places the source cloud, Vg = prev_pose . V, and
+    it is the right factor of pose = fl32(T . prev_pose)).  Values and trace do not depend on either."""
     H, W = fmap.H, fmap.W
     if fmap.M == 0:
         raise ValueError("frame-to-model odometry needs a non-empty map")
-    differentiable = torch.is_grad_enabled() and depth.requires_grad
-    K, prev_pose = K.detach(), prev_pose.detach()
+    if map_tensors is not None:
+        map_points, map_normals = map_tensors
+        assert map_points.shape == (fmap.M, 3) and map_normals.shape == (fmap.M, 3), "map_tensors must stand for the resident rows"
+    K = K.detach()
+    if not prev_pose_gradient:
+        prev_pose = prev_pose.detach()
+    variables = [depth, prev_pose] + (list(map_tensors) if map_tensors is not None else [])
+    differentiable = torch.is_grad_enabled() and any(t.requires_grad for t in variables)
+    chain = map_tensors is not None or prev_pose_gradient
     with torch.set_grad_enabled(differentiable):
         maps = fmap.frame_maps(depth, K, prev_pose)
+        prev_pose_var, prev_pose = prev_pose, prev_pose.detach()          # the association takes it as a constant
         sub = torch.zeros(H, W, dtype=torch.bool, device=depth.device)
         sub[::dsratio, ::dsratio] = True
         keep = maps["valid"][0] & sub
@@ -254,7 +285,11 @@ def frame_to_model(fmap, depth, K, prev_pose, dsratio=4, **kw):
         sel = fmap.table("active")[::dsratio, 0]
         if sel.numel() < 6 or src.shape[0] < 6:
             raise RuntimeError("too few points for frame-to-model ICP (no overlap between the live frame and the map)")
-        pose, trace = point_to_plane_icp(src, fmap.points[sel].detach(), fmap.normals[sel].detach(), prev_pose=prev_pose, **kw)
+        if map_tensors is not None:
+            tgt, tgt_n = map_points.index_select(0, sel), map_normals.index_select(0, sel)
+        else:
+            tgt, tgt_n = fmap.points[sel].detach(), fmap.normals[sel].detach()
+        pose, trace = point_to_plane_icp(src, tgt, tgt_n, prev_pose=prev_pose_var, target_gradient=chain, **kw)
     return pose, trace
 
 

@@ -282,12 +282,14 @@ class _VertexMaps(torch.autograd.Function):
         L.call("e2e_vertex_normal_maps", depth=L.ptr(d), K=L.ptr(K), pose=L.ptr(pose), alpha_den=float(alpha_den), V=L.ptr(V), Nm=L.ptr(Nm), Vg=L.ptr(Vg),
                Ng=L.ptr(Ng), alpha=L.ptr(alpha), B=B, H=H, W=W, stream=L.stream())
         ctx.alpha_den = float(alpha_den) if alpha_grad else None
+        saved = (d, K, pose, alpha) if alpha_grad else (d, K, pose)
+        if ctx.needs_input_grad[2]:                       # the pose is a variable (the chain gradient): its adjoint needs V
+            saved = saved + (V,)
+        ctx.save_for_backward(*saved)
         if alpha_grad:
-            ctx.save_for_backward(d, K, pose, alpha)
             ctx.mark_non_differentiable(Nm, Ng)
             ctx.set_materialize_grads(False)              # a map step that only moves confidences sends no g_Vg
         else:
-            ctx.save_for_backward(d, K, pose)
             ctx.mark_non_differentiable(Nm, Ng, alpha)
         return V, Nm, Vg, Ng, alpha
 
@@ -301,20 +303,30 @@ class _VertexMaps(torch.autograd.Function):
         if gV is None and gVg is None and ga is None:
             return None, None, None, None, None
         gd = torch.empty_like(d)
+        g_pose = None
         if gV is not None or gVg is not None:
             gV = gV.contiguous() if gV is not None else None
             gVg = gVg.contiguous() if gVg is not None else None
             L.call("e2e_vertex_maps_bwd", L.ptr(d), L.ptr(K), L.ptr(pose), L.ptr(gV), L.ptr(gVg), L.ptr(gd), B, H, W, L.stream())
+        if ctx.needs_input_grad[2]:
+            # Vg = (R V + t) on the valid pixels: g_pose[b][:3] = [sum g_Vg V^T | sum g_Vg]; the normals and alpha do not see the pose
+            g_pose = torch.zeros(B, 4, 4, device=d.device, dtype=torch.float32)
+            if gVg is not None:
+                V = ctx.saved_tensors[-1]
+                gm = (gVg * (d != 0)[..., None]).reshape(B, H * W, 3)
+                for b in range(B):
+                    g_pose[b, :3] = transform_points_bwd_T(gm[b], V[b].reshape(H * W, 3)).float()
         if ga is not None:
             L.call("e2e_vertex_alpha_bwd", depth=L.ptr(d), K=L.ptr(K), alpha=L.ptr(ctx.saved_tensors[3]), g_alpha=L.ptr(ga.contiguous()),
                    alpha_den=ctx.alpha_den, g_depth=L.ptr(gd), accumulate=int(gV is not None or gVg is not None), B=B, H=H, W=W, stream=L.stream())
-        return gd, None, None, None, None
+        return gd, None, g_pose, None, None
 
 
 def vertex_normal_maps(depth, K, pose, sigma=0.6, alpha_grad=False):
     """depth (B,H,W), K/pose (B,4,4) -> dict V, n, Vg, ng (B,H,W,3), alpha (B,H,W), valid (B,H,W) bool.
     gradslam RGBDImages maps; differentiable wrt depth through V and Vg, and -- with alpha_grad=True only --
-    through the fusion confidence alpha (e2e_vertex_alpha_bwd).  The normals are not differentiated."""
+    through the fusion confidence alpha (e2e_vertex_alpha_bwd).  A pose that requires grad gets its gradient through Vg
+    (e2e_transform_points_bwd_t per batch item; bottom row 0).  The normals are not differentiated."""
     if depth.dim() != 3:
         raise ValueError(f"depth: expected (B,H,W), got {tuple(depth.shape)}")
     V, Nm, Vg, Ng, alpha = _VertexMaps.apply(depth, K, pose, fusion_alpha_den(sigma), bool(alpha_grad))

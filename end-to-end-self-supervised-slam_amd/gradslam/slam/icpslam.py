@@ -19,6 +19,7 @@ class ICPSLAM(nn.Module):
         self.damp, self.dist_thresh, self.lambda_max, self.B, self.B2, self.nu = damp, dist_thresh, lambda_max, B, B2, nu
         self.device = torch.device(device) if device is not None else torch.device("cpu")
         self.pose_gradient = True         # False: localise on the detached depth (the pose is a constant of the step)
+        self.chain_gradient = False       # True (PointFusion): the map and the previous pose are variables of the localisation too
 
     # -- odometry ------------------------------------------------------------------------------------
     def _localize(self, pointclouds, live_frame, prev_frame):
@@ -47,10 +48,14 @@ class ICPSLAM(nn.Module):
         if not (self.pose_gradient and torch.is_grad_enabled() and depth.requires_grad):
             depth = depth.detach()
         # with a depth that requires grad the pose carries the gradient back into it (through the ICP / GradICP iterations)
+        chain = {}
+        if self.chain_gradient and self.pose_gradient and torch.is_grad_enabled():
+            # the chain gradient: the pose also carries the gradient to the map it was localised against and to the previous pose
+            chain = dict(map_tensors=(pointclouds.points_list[0], pointclouds.normals_list[0]), prev_pose_gradient=True)
         pose, self.last_trace = icp.frame_to_model(fm, depth, live_frame.intrinsics[0, 0],
                                                    prev_frame.poses[0, 0], dsratio=self.dsratio, numiters=self.numiters, damp=self.damp,
                                                    dist_thresh=self.dist_thresh, mode=self.odom, lambda_max=self.lambda_max, B=self.B,
-                                                   B2=self.B2, nu=self.nu)
+                                                   B2=self.B2, nu=self.nu, **chain)
         return pose.view(1, 1, 4, 4)
 
     def _resident_map(self, pointclouds, live_frame):
@@ -69,6 +74,8 @@ class ICPSLAM(nn.Module):
     # -- map update ------------------------------------------------------------------------------------
     def _map(self, pointclouds, live_frame, inplace=False):
         from .pointfusion import frame_as_pointcloud
+        if self.chain_gradient:
+            raise NotImplementedError("chain_gradient covers the PointFusion map only, not the aggregation map")
         new = frame_as_pointcloud(live_frame)
         target = pointclouds if inplace else pointclouds.clone()
         return target.append_points(new)

@@ -66,6 +66,11 @@ class Depth_Estimation:
         # whole predicted-depth sequence (train_depth.py:378-385), so every frame's depth gets a gradient through the fusion.  E2E_MAP_GRAD=1
         # (or map_gradient = True) differentiates the map update; default off: only the frame that met the empty map gets one.
         self.map_gradient = os.environ.get("E2E_MAP_GRAD", "0") == "1"
+        # DATA.use_gt_pose: False with MODEL.slam: PointFusion -- in the reference the reconstruction and the poses come out of one graph
+        # (train_depth.py:360-397): frame t is localised against the map fused from the predicted depths before it, starting from an
+        # estimated pose.  E2E_CHAIN_GRAD=1 (or chain_gradient = True) makes the map and the previous pose variables of the localisation
+        # and the pose a variable of the map step; default off: they are constants.  Composes with the two switches above.
+        self.chain_gradient = os.environ.get("E2E_CHAIN_GRAD", "0") == "1"
         self.dataset_init()
         self.model_init()
         self.view_reconstruction_init()
@@ -230,6 +235,7 @@ class Depth_Estimation:
                 else:
                     self.models["SLAM"].pose_gradient = self.pose_gradient
                     self.models["SLAM"].map_gradient = self.map_gradient
+                    self.models["SLAM"].chain_gradient = self.chain_gradient
                     noisy_reconstruction, new_poses = self.models["SLAM"](noisy_rgbd)
                     new_transform = torch_poses_to_transforms(new_poses)
                 if noisy_reconstruction is not None:

@@ -359,8 +359,10 @@ int e2e_frame_append_dev(float* map_points, float* map_normals, float* map_color
  *   invalid pixels and pixels dropped beyond the capacity get 0.
  * The frame side reaches the depth two ways: g_Vg through e2e_vertex_maps_bwd (Vg = R V + t), g_alpha through e2e_vertex_alpha_bwd.
  * One pixel owns one row and one row is won by at most one pixel: a gather over pixels, no atomics, bitwise reproducible.
- * Not differentiated (yet): the pose of the map step (e2e_transform_points_bwd_t would supply it), the normals; single sequence only;
- * the resident forms (e2e_*_dev) have no tape.
+ * The pose of the map step is a constant by default; with the chain gradient (FusionMap.step_differentiable(pose_gradient=True)) it is a
+ * variable through Vg = R V + t: g_pose[:3] = [sum g_Vg V^T | sum g_Vg] over the valid pixels (e2e_transform_points_bwd_t), bottom row 0;
+ * the association still sees it as a constant.  Not differentiated: the normals; single sequence only; the resident forms (e2e_*_dev)
+ * have no tape.
  *
  * e2e_pf_fuse_tape runs BETWEEN e2e_pf_associate and e2e_pf_fuse_append on the same workspace and map (the forward fuses in place) and
  *   records per pixel what the backward needs: the destination row as int64 (winner n, appended row, or -1) and, for a fused pixel, the
@@ -793,7 +795,10 @@ int e2e_icp_normal_equations(const float* src, const float* tgt, const float* tg
 
 /* THE ADJOINT OF THE ODOMETRY (differentiable ICP / GradICP; the reference back-propagates the photometric loss through the pose into
  * the live frame's depth, train_depth.py:381-382, :395).  The rule, for the whole iteration sequence:
- *   - it is taken with respect to the SOURCE points only; target points, target normals and prev_pose are constants;
+ *   - by default it is taken with respect to the SOURCE points only: target points, target normals and prev_pose are constants.  The
+ *     chain gradient (opt-in: point_to_plane_icp(target_gradient=True), PointFusion(chain_gradient=True), E2E_CHAIN_GRAD=1) also takes
+ *     it with respect to the target points and normals (e2e_icp_normal_equations_bwd_tgt below) and to prev_pose (pose = T . prev_pose:
+ *     T^T gbar_pose, float64 on the host);
  *   - the nearest-neighbour indices, the dist_thresh keep mask and the inlier counts of every search are held fixed;
  *   - the clipped region of GradICP's gate (|nu delta| >= 60) has zero derivative;
  *   - the fp32 roundings of the running transform and of the pose are passed straight through.
@@ -806,6 +811,25 @@ int e2e_icp_normal_equations(const float* src, const float* tgt, const float* tg
 int e2e_icp_normal_equations_bwd(const float* src, const float* tgt, const float* tgt_normals, int64_t n_tgt,
                                  const long long* idx, const float* dists, float dist_thresh, const double* adj28,
                                  int64_t n, float* g_src, int accumulate, void* stream);
+
+/* The TARGET side of the same reduction's adjoint (the chain gradient: the map is a variable of the localisation).  Same arguments and
+ * notation; for target row j, summed over the kept source rows i with idx[i] == j:
+ *   g_tgt[j]         = sum_i  bbar_i n_j
+ *   g_tgt_normals[j] = sum_i  bbar_i (t_j - s_i) + Abar_i[0:3] + Abar_i[3:6] x s_i            both (n_tgt,3) fp32.
+ * A row the forward skipped contributes nothing; a row whose idx is outside [0, n_tgt) contributes nothing and reads nothing.  A target
+ * that no kept row names gets 0 with accumulate == 0 and keeps its value with accumulate != 0; every other target gets
+ * (float)sum, or (float)((double)old + sum).  g_tgt and g_tgt_normals may each be NULL (not wanted), not both.
+ * Several sources share one target, so this is a scatter with collisions.  It is done without float atomics and without fixed-point
+ * accumulation (adj28 has no bounded scale): the neighbour list is inverted per call (count the kept rows per target, exclusive scan,
+ * fill), and one owner per target adds its segment in ascending source index in float64 and rounds once; a segment of more than 64
+ * rows goes to a wave (lane l adds the rows l, l + 64, ... of the sorted segment, then a fixed shuffle tree).  Bitwise reproducible and
+ * independent of arrival order; memory traffic O(n + n_tgt).  n and n_tgt below 2^31.
+ * workspace: e2e_icp_normal_equations_bwd_tgt_workspace_bytes(n, n_tgt) bytes (0 for sizes out of range). */
+int64_t e2e_icp_normal_equations_bwd_tgt_workspace_bytes(int64_t n, int64_t n_tgt);
+int e2e_icp_normal_equations_bwd_tgt(const float* src, const float* tgt, const float* tgt_normals, int64_t n_tgt,
+                                     const long long* idx, const float* dists, float dist_thresh, const double* adj28,
+                                     int64_t n, float* g_tgt, float* g_tgt_normals, int accumulate,
+                                     void* workspace, void* stream);
 
 /* The rest of an odometry iteration ON THE DEVICE (gradslam odometry providers "icp" / "gradicp" behind PointFusion.step,
  * online_adaption.py:111-122,362; configs/config.yaml:30-35 ships odom: gradicp): solve (A^T A + lambda I) xi = A^T b, the
