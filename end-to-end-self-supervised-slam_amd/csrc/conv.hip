@@ -333,6 +333,50 @@ struct PartIds {
     __device__ __forceinline__ unsigned lin() const { return l; }
 };
 
+// The 1x1 branch of a stage entry (k_conv_fwd_pair) ends in an eval-mode BatchNorm whose gamma / beta train: its epilogue folds the
+// BatchNorm for the block's column (k_bn_fold's expressions, nn_misc.hip, under the same contraction setting), stores the raw GEMM result
+// z -- the backward reads it -- and y = fmaf(z, scale, shift) (k_affine_fwd's expression).  The row tile that holds GEMM row 0 also
+// writes the three per-channel vectors the backward reads.
+struct BnFoldArgs {
+    const float *gamma, *beta, *mean, *var;
+    float eps;
+    float *scale, *shift, *rstd;     // [Ncols] each
+    float* y;                        // [n][Ncols], the affine output; z goes to ConvArgs::out
+};
+
+__device__ __forceinline__ void epilogue_block_bnfold(const ConvArgs& a, const BnFoldArgs& bn, const f16v& acc, int col, int64_t nb, int64_t Ntot, bool writes_vectors) {
+    constexpr unsigned OOB = 0x80000000u;
+    const int64_t out_bytes = Ntot * a.Ncols * 4;
+    const __amdgpu_buffer_rsrc_t rz = __builtin_amdgcn_make_buffer_rsrc((void*)a.out, 0, (int)out_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc((void*)bn.y, 0, (int)out_bytes, 0x00020000);
+    const bool col_ok = col < a.Ncols;
+    float s = 1.f, sh = 0.f;
+    if (col_ok) {
+        const float r = 1.f / sqrtf(bn.var[col] + bn.eps);
+        s = bn.gamma[col] * r;
+        sh = bn.beta[col] - bn.mean[col] * s;
+        if (writes_vectors) {
+            bn.scale[col] = s;
+            bn.shift[col] = sh;
+            bn.rstd[col] = r;
+        }
+    }
+    const unsigned voff0 = (col_ok && nb < Ntot) ? (unsigned)((nb * a.Ncols + col) * 4) : OOB;
+    const int left = (int)((Ntot - nb < 32) ? Ntot - nb : 32);
+    const float one = 1.f, zero = 0.f;
+    float z[16], y[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) z[r] = fmaf(acc[r], one, zero);         // what the plain epilogue gives a convolution without scale / shift
+#pragma unroll
+    for (int r = 0; r < 16; ++r) y[r] = fmaf(z[r], s, sh);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const unsigned vo = ((r & 3) + 8 * (r >> 2) < left) ? voff0 : OOB;
+        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, z[r]), rz, vo, ((r & 3) + 8 * (r >> 2)) * a.Ncols * 4, 0);
+        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, y[r]), ry, vo, ((r & 3) + 8 * (r >> 2)) * a.Ncols * 4, 0);
+    }
+}
+
 // LDS tiles of k_conv_gemm: double-buffered A (k-major, row stride padded for the VEC == 4 loader's transposing stores) and B
 template <int WM, int WN, int TM, int TN, int VEC, int CB>
 struct ConvGemmLds {
@@ -343,9 +387,9 @@ struct ConvGemmLds {
 
 // the body of k_conv_gemm: workgroup `wg` of the launch described by `a`, LDS tiles As / Bs (the kernel's own static arrays, or a
 // share of k_conv_bwd_pair's union)
-template <int WM, int WN, int TM, int TN, int VEC, bool TRANSPOSED, int CB, class Ids>
+template <int WM, int WN, int TM, int TN, int VEC, bool TRANSPOSED, int CB, class Ids, bool BNFOLD = false>
 __device__ __forceinline__ void conv_gemm_body(const ConvArgs& a, const Ids& wg, float (*As)[CB][ConvGemmLds<WM, WN, TM, TN, VEC, CB>::BM + ConvGemmLds<WM, WN, TM, TN, VEC, CB>::APAD],
-                                               float (*Bs)[CB][ConvGemmLds<WM, WN, TM, TN, VEC, CB>::BN]) {
+                                               float (*Bs)[CB][ConvGemmLds<WM, WN, TM, TN, VEC, CB>::BN], const BnFoldArgs* bn = nullptr) {
     constexpr int BM = 32 * WM * TM, BN = 32 * TN * WN, NT = 64 * WM * WN;
     constexpr int KQ = CB / VEC;                           // k-groups (of VEC) per chunk
     constexpr int A_CNT = BM * KQ;                         // (row, k-group) elements of the A tile
@@ -714,6 +758,11 @@ __device__ __forceinline__ void conv_gemm_body(const ConvArgs& a, const Ids& wg,
             }
         return;
     }
+    if constexpr (BNFOLD) {                                   // (forward, unsplit, one accumulator block per wave: k_conv_fwd_pair's second part)
+        static_assert(!TRANSPOSED && TM * TN == 1, "the BatchNorm-folding epilogue serves the forward 1x1 branch");
+        epilogue_block_bnfold(a, *bn, acc[0][0], c0 + wn * 32 + (lane & 31), n0 + wm * 32 + 4 * khalf, Ntot, n0 == 0 && khalf == 0);
+        return;
+    }
     if (!CLS) {
         const EpiRsrc er = make_epi_rsrc<TRANSPOSED>(a);
 #pragma unroll
@@ -756,6 +805,37 @@ __global__ __launch_bounds__(64 * WM * WN) void k_conv_gemm(ConvArgs a) {
     __shared__ float As[2][CB][Lds::BM + Lds::APAD];
     __shared__ float Bs[2][CB][Lds::BN];
     conv_gemm_body<WM, WN, TM, TN, VEC, TRANSPOSED, CB>(a, HwIds{}, As, Bs);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Forward of a stage entry (the first BasicBlock of layer2 / 3 / 4) as ONE launch: the block input goes through conv1 (3x3, stride 2,
+// frozen BatchNorm + ReLU) and, independently, through the downsample branch (1x1, stride 2, then an eval-mode BatchNorm with trainable
+// gamma / beta).  As four launches (GEMM, GEMM, k_bn_fold, k_affine_fwd) three of them sit at the launch floor.  Here a 1-D grid carries
+// both tile sets, as k_conv_bwd_pair does for the backward: conv1's tiles first (rounded up to a multiple of 8, so that the second
+// part's local ids fall on the same XCDs as in a standalone launch), then the 1x1 branch's.  Every workgroup runs the tile it would run
+// in its own launch -- same virtual ids, same K order, same arithmetic; the second part's epilogue does the fold and the affine per
+// element with the expressions of the kernels it replaces -- so every output is bit-identical.  Both parts are the 32 x 128 tile at
+// chunk depth 32 and share one LDS tile set.
+// ---------------------------------------------------------------------------------------------------------------------
+struct FwdPairGrid {
+    unsigned agx, agy, agz;    // conv1's tile set, laid out as in its own launch (agz: its K slices)
+    unsigned bgx, bgy;         // the 1x1 branch's tile set (unsplit)
+    unsigned first;            // workgroups of the first part, a multiple of 8
+};
+
+__global__ __launch_bounds__(256) void k_conv_fwd_pair(ConvArgs a, ConvArgs b, BnFoldArgs bn, FwdPairGrid pg) {
+    using Lds = ConvGemmLds<1, 4, 1, 1, 4, 32>;
+    __shared__ float As[2][32][Lds::BM + Lds::APAD];
+    __shared__ float Bs[2][32][Lds::BN];
+    const unsigned id = blockIdx.x;
+    if (id < pg.first) {
+        if (id >= pg.agx * pg.agy * pg.agz) return;          // the padding of the first part
+        conv_gemm_body<1, 4, 1, 1, 4, false, 32>(a, PartIds{id, pg.agx, pg.agy, pg.agz}, As, Bs);
+    } else {
+        const unsigned l = id - pg.first;
+        if (l >= pg.bgx * pg.bgy) return;
+        conv_gemm_body<1, 4, 1, 1, 4, false, 32, PartIds, true>(b, PartIds{l, pg.bgx, pg.bgy, 1u}, As, Bs, &bn);
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -2570,6 +2650,29 @@ __global__ __launch_bounds__(256) void k_head_fwd(const float* __restrict__ x, c
     }
 }
 
+// dZ summed over the outputs q that read input pixel (h, ww) of one image through tap (kh, kw): padded position q + (kh - 1, kw - 1) must
+// map to the pixel.  Along one axis that is q = p - k + 1 (the direct reader) and, for p one pixel away from a border only, the reader that
+// reaches p through the reflection (p = 1: padded -1, i.e. q = -k, `ra` = 0; p = n - 2: padded n, i.e. q = n - k + 1, `rb` = n + 1; -100:
+// none).  On a 3-pixel axis the middle pixel is next to BOTH borders and has both.  Exactly one reader for interior pixels -- the first
+// version searched a 5 x 5 neighbourhood for every pixel of a border WAVE.  Fixed order: direct, then the reflected columns, rows, corners.
+__device__ __forceinline__ float head_dz_gather(const float* __restrict__ gz, int h, int ww, int kh, int kw, int H, int W, int rya, int ryb, int rxa, int rxb) {
+    const int qy0 = h - kh + 1, qx0 = ww - kw + 1, qya = rya - kh, qyb = ryb - kh, qxa = rxa - kw, qxb = rxb - kw;
+    const bool y0 = qy0 >= 0 && qy0 < H, x0 = qx0 >= 0 && qx0 < W;
+    const bool ya = qya >= 0 && qya < H, yb = qyb >= 0 && qyb < H, xa = qxa >= 0 && qxa < W, xb = qxb >= 0 && qxb < W;
+    float g = (y0 && x0) ? gz[(int64_t)qy0 * W + qx0] : 0.f;
+    if (ya | yb | xa | xb) {                                        // border pixels only (divergence is a handful of lanes per row)
+        if (y0 && xa) g += gz[(int64_t)qy0 * W + qxa];
+        if (y0 && xb) g += gz[(int64_t)qy0 * W + qxb];
+        if (ya && x0) g += gz[(int64_t)qya * W + qx0];
+        if (yb && x0) g += gz[(int64_t)qyb * W + qx0];
+        if (ya && xa) g += gz[(int64_t)qya * W + qxa];
+        if (ya && xb) g += gz[(int64_t)qya * W + qxb];
+        if (yb && xa) g += gz[(int64_t)qyb * W + qxa];
+        if (yb && xb) g += gz[(int64_t)qyb * W + qxb];
+    }
+    return g;
+}
+
 // d/dx: every input pixel gathers the (reflect-aware) outputs that read it:  dx[p,ci] = sum_{q, tap: src(q,tap)=p} dz[q] w[tap,ci]
 __global__ __launch_bounds__(256) void k_head_bwd_data(const float* __restrict__ dz, const float* __restrict__ w, float* __restrict__ dx,
                                                        int B, int H, int W, const float* __restrict__ xin, int dact) {
@@ -2587,26 +2690,16 @@ __global__ __launch_bounds__(256) void k_head_bwd_data(const float* __restrict__
         const int b = (int)(n / ((int64_t)H * W));
         const int r = (int)(n - (int64_t)b * H * W), h = r / W, ww = r - h * W;
         f4v acc = {0.f, 0.f, 0.f, 0.f};
-        // the outputs q that read input pixel p through tap (kh, kw): padded position q + (kh - 1, kw - 1) must map to p.  Along one
-        // axis that is q = p - k + 1 (the direct reader) and, for p one pixel away from a border only, the reader that reaches p through
-        // the reflection (p = 1: padded -1, i.e. q = -k; p = n - 2: padded n, i.e. q = n - k + 1).  At most 2 x 2 readers per tap, and
-        // exactly one for interior pixels -- the first version searched a 5 x 5 neighbourhood for every pixel of a border WAVE.
-        const int ry = (h == 1) ? 0 : ((h == H - 2) ? H + 1 : -100);             // reflected reader: q = ry - kh (invalid when out of range)
-        const int rx = (ww == 1) ? 0 : ((ww == W - 2) ? W + 1 : -100);
+        // the reflected readers of this pixel (head_dz_gather): q = r - k, invalid when out of range
+        const int rya = (h == 1) ? 0 : -100, ryb = (h == H - 2) ? H + 1 : -100;
+        const int rxa = (ww == 1) ? 0 : -100, rxb = (ww == W - 2) ? W + 1 : -100;
         const float* gz = dz + (int64_t)b * H * W;
 #pragma unroll
         for (int kh = 0; kh < 3; ++kh)
 #pragma unroll
             for (int kw = 0; kw < 3; ++kw) {
                 const float* wt = &sw[(kh * 3 + kw) * HC + cq * 4];
-                const int qy0 = h - kh + 1, qx0 = ww - kw + 1, qy1 = ry - kh, qx1 = rx - kw;
-                const bool y0 = qy0 >= 0 && qy0 < H, x0 = qx0 >= 0 && qx0 < W, y1 = qy1 >= 0 && qy1 < H, x1 = qx1 >= 0 && qx1 < W;
-                float g = (y0 && x0) ? gz[(int64_t)qy0 * W + qx0] : 0.f;
-                if (y1 | x1) {                                                  // border pixels only (divergence is a handful of lanes per row)
-                    if (y0 && x1) g += gz[(int64_t)qy0 * W + qx1];
-                    if (y1 && x0) g += gz[(int64_t)qy1 * W + qx0];
-                    if (y1 && x1) g += gz[(int64_t)qy1 * W + qx1];
-                }
+                const float g = head_dz_gather(gz, h, ww, kh, kw, H, W, rya, ryb, rxa, rxb);
 #pragma unroll
                 for (int c = 0; c < 4; ++c) acc[c] = fmaf(g, wt[c], acc[c]);
             }
@@ -2649,6 +2742,87 @@ __global__ __launch_bounds__(256) void k_head_bwd_weight(const float* __restrict
                 for (int c = 0; c < 4; ++c) acc[(kh * 3 + kw) * 4 + c] = fmaf(g, v[c], acc[(kh * 3 + kw) * 4 + c]);
             }
         sb += g;
+    }
+#pragma unroll
+    for (int k = 0; k < 36; ++k) {
+        float v = acc[k];
+#pragma unroll
+        for (int o = 4; o < 64; o <<= 1) v += __shfl_xor(v, o, 64);
+        acc[k] = v;
+    }
+#pragma unroll
+    for (int o = 4; o < 64; o <<= 1) sb += __shfl_xor(sb, o, 64);
+    if (lane < 4) {
+#pragma unroll
+        for (int t = 0; t < 9; ++t)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) red[wave][t * HC + lane * 4 + c] = acc[t * 4 + c];
+        if (lane == 0) red[wave][9 * HC] = sb;
+    }
+    __syncthreads();
+    if (threadIdx.x < 9 * HC + 1)
+        partials[(int64_t)blockIdx.x * (9 * HC + 1) + threadIdx.x] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+}
+
+// d/dx and d/dw, d/dbias in ONE pass over the pixels (e2e_head_bwd_act with both gradients asked for).  The two kernels above stream the same
+// activation x (39 MB at 480 x 640 x 2) and the same dZ: this one walks the pixels with k_head_bwd_weight's partition -- same per-workgroup
+// range, same lane -> (pixel slot, channel quad) mapping, same 36 running sums, same shuffle and LDS combine order, same k_head_wreduce
+// afterwards -- and, for the pixel a lane holds, also evaluates k_head_bwd_data's expressions (the nine dZ gathers with the reflected
+// readers, the same fmaf order, act' from x) and stores dx.  The centre tap of the weight part IS the x quad the data part's act' needs,
+// so x comes from HBM once.  Every sum keeps its order: dx, dw and dbias are bit-identical to the two-kernel form.
+__global__ __launch_bounds__(256) void k_head_bwd_fused(const float* __restrict__ dz, const float* __restrict__ x, const float* __restrict__ w,
+                                                        float* __restrict__ dx, float* __restrict__ partials, int B, int H, int W, int dact) {
+    __shared__ float red[4][9 * HC + 1];
+    __shared__ float sw[9 * HC];
+    for (int i = threadIdx.x; i < 9 * HC; i += 256) {
+        const int ci = i / 9, tap = i - ci * 9;
+        sw[tap * HC + ci] = w[i];
+    }
+    __syncthreads();
+    const int64_t N = (int64_t)B * H * W;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, cq = threadIdx.x & 3, ps = threadIdx.x >> 2;
+    const int64_t per = (N + gridDim.x - 1) / gridDim.x;
+    const int64_t n0 = (int64_t)blockIdx.x * per, n1 = (n0 + per < N) ? n0 + per : N;
+    float acc[36];
+#pragma unroll
+    for (int k = 0; k < 36; ++k) acc[k] = 0.f;
+    float sb = 0.f;
+    for (int64_t n = n0 + ps; n < n1; n += 64) {
+        const float g = dz[n];
+        const int b = (int)(n / ((int64_t)H * W));
+        const int r = (int)(n - (int64_t)b * H * W), h = r / W, ww = r - h * W;
+        f4v xv = {0.f, 0.f, 0.f, 0.f};
+        // ---- the weight part (k_head_bwd_weight) ----
+#pragma unroll
+        for (int kh = 0; kh < 3; ++kh)
+#pragma unroll
+            for (int kw = 0; kw < 3; ++kw) {
+                const int ys = reflect1(h + kh - 1, H), xs = reflect1(ww + kw - 1, W);
+                const f4v v = *(const f4v*)(x + (((int64_t)b * H + ys) * W + xs) * HC + cq * 4);
+                if (kh == 1 && kw == 1) xv = v;                                 // the pixel's own quad: x[n]
+#pragma unroll
+                for (int c = 0; c < 4; ++c) acc[(kh * 3 + kw) * 4 + c] = fmaf(g, v[c], acc[(kh * 3 + kw) * 4 + c]);
+            }
+        sb += g;
+        // ---- the data part (k_head_bwd_data) ----
+        f4v da = {0.f, 0.f, 0.f, 0.f};
+        const int rya = (h == 1) ? 0 : -100, ryb = (h == H - 2) ? H + 1 : -100;
+        const int rxa = (ww == 1) ? 0 : -100, rxb = (ww == W - 2) ? W + 1 : -100;
+        const float* gz = dz + (int64_t)b * H * W;
+#pragma unroll
+        for (int kh = 0; kh < 3; ++kh)
+#pragma unroll
+            for (int kw = 0; kw < 3; ++kw) {
+                const float* wt = &sw[(kh * 3 + kw) * HC + cq * 4];
+                const float gg = head_dz_gather(gz, h, ww, kh, kw, H, W, rya, ryb, rxa, rxb);
+#pragma unroll
+                for (int c = 0; c < 4; ++c) da[c] = fmaf(gg, wt[c], da[c]);
+            }
+        if (dact) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) da[e] *= act_deriv(xv[e], dact);
+        }
+        *(f4v*)(dx + n * HC + cq * 4) = da;
     }
 #pragma unroll
     for (int k = 0; k < 36; ++k) {
@@ -2999,26 +3173,38 @@ struct FwdOps { const float *src0, *src1, *w_fwd; int ld_fwd; const float *scale
 struct BwdDataOps { const float* dz; const float* w_bwd; int ld_bwd; float* dxp; int accumulate; const float* x_in; int in_act; const float* pre_add; };
 struct WgradIn { const float *dz, *src0, *src1; float* workspace; };
 
-static int conv_fwd_impl(const FwdOps& f, const ConvGeom& g, float* workspace, GemmCfg force, void* stream) {
+// A forward call up to its launch: checks the arguments and fills the GEMM's ConvArgs.  Shared by conv_fwd_impl and the stage-entry pair.
+static int fwd_setup(const FwdOps& f, const ConvGeom& g, ConvArgs& a_out, int& vec_out, const char* who) {
     const int B = g.B, Hs = g.Hs, Ws = g.Ws, Cin = g.Cin, Cout = g.Cout, KH = g.KH, KW = g.KW, stride = g.stride, pad = g.pad, pad_mode = g.pad_mode;
     const int C1 = g.C1, up = g.up, ld_fwd = f.ld_fwd;
-    E2E_REQUIRE(f.src0 && f.w_fwd && f.out && B > 0 && Hs > 0 && Ws > 0 && Cin > 0 && Cout > 0, E2E_ERR_ARG, "e2e_conv2d_fwd: bad argument");
-    E2E_REQUIRE(up == 1 || up == 2, E2E_ERR_ARG, "e2e_conv2d_fwd: upsample factor must be 1 or 2");
-    E2E_REQUIRE(C1 > 0 && C1 <= Cin && (C1 == Cin || f.src1), E2E_ERR_ARG, "e2e_conv2d_fwd: bad channel split");
-    E2E_REQUIRE(pad_mode == 0 || (pad_mode == 1 && pad == 1 && Hs >= 2 && Ws >= 2), E2E_ERR_ARG, "e2e_conv2d_fwd: reflection padding needs pad == 1");
-    E2E_REQUIRE(stride == 1 || stride == 2, E2E_ERR_ARG, "e2e_conv2d_fwd: stride must be 1 or 2");
-    E2E_REQUIRE(Hs % up == 0 && Ws % up == 0 && ld_fwd % 4 == 0 && ld_fwd >= Cout, E2E_ERR_ARG, "e2e_conv2d_fwd: bad sizes");
+    E2E_REQUIRE(f.src0 && f.w_fwd && f.out && B > 0 && Hs > 0 && Ws > 0 && Cin > 0 && Cout > 0, E2E_ERR_ARG, "%s: bad argument", who);
+    E2E_REQUIRE(up == 1 || up == 2, E2E_ERR_ARG, "%s: upsample factor must be 1 or 2", who);
+    E2E_REQUIRE(C1 > 0 && C1 <= Cin && (C1 == Cin || f.src1), E2E_ERR_ARG, "%s: bad channel split", who);
+    E2E_REQUIRE(pad_mode == 0 || (pad_mode == 1 && pad == 1 && Hs >= 2 && Ws >= 2), E2E_ERR_ARG, "%s: reflection padding needs pad == 1", who);
+    E2E_REQUIRE(stride == 1 || stride == 2, E2E_ERR_ARG, "%s: stride must be 1 or 2", who);
+    E2E_REQUIRE(Hs % up == 0 && Ws % up == 0 && ld_fwd % 4 == 0 && ld_fwd >= Cout, E2E_ERR_ARG, "%s: bad sizes", who);
     const int vec = (Cin % 16 == 0 && (C1 == Cin || C1 % 16 == 0)) ? 4 : 1;
-    E2E_REQUIRE(vec == 4 || (C1 == Cin && up == 1), E2E_ERR_ARG, "e2e_conv2d_fwd: the scalar path (Cin %% 16 != 0) takes a single full-resolution source");
+    E2E_REQUIRE(vec == 4 || (C1 == Cin && up == 1), E2E_ERR_ARG, "%s: the scalar path (Cin %% 16 != 0) takes a single full-resolution source", who);
     E2E_REQUIRE((int64_t)B * Hs * Ws * Cin * 4 < (1ll << 30) && (int64_t)KH * KW * Cin * ld_fwd * 4 < (1ll << 31), E2E_ERR_ARG,
-                "e2e_conv2d_fwd: activations must stay below 1 GB, weights below 2 GB (32-bit buffer offsets with out-of-range markers)");
-    E2E_REQUIRE(vec != 4 || (KH <= 3 && KW <= 3), E2E_ERR_ARG, "e2e_conv2d_fwd: the channel-quad loader takes kernels up to 3 x 3");
+                "%s: activations must stay below 1 GB, weights below 2 GB (32-bit buffer offsets with out-of-range markers)", who);
+    E2E_REQUIRE(vec != 4 || (KH <= 3 && KW <= 3), E2E_ERR_ARG, "%s: the channel-quad loader takes kernels up to 3 x 3", who);
     ConvArgs a{};
     a.src0 = f.src0; a.src1 = f.src1; a.w = f.w_fwd; a.scale = f.scale; a.shift = f.shift; a.res = f.residual; a.out = f.out;
     a.B = B; a.Hs = Hs; a.Ws = Ws; a.Cin = Cin; a.C1 = C1; a.up = up;
     a.Hd = (Hs + 2 * pad - KH) / stride + 1; a.Wd = (Ws + 2 * pad - KW) / stride + 1;
     a.Ncols = Cout; a.ldw = ld_fwd; a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad; a.pad_mode = pad_mode; a.off = 0; a.act = f.act;
     a.in_sub = g.in_sub; a.in_mul = g.in_mul;
+    a_out = a; vec_out = vec;
+    return E2E_OK;
+}
+
+static int conv_fwd_impl(const FwdOps& f, const ConvGeom& g, float* workspace, GemmCfg force, void* stream) {
+    const int B = g.B, Hs = g.Hs, Ws = g.Ws, Cin = g.Cin, Cout = g.Cout, KH = g.KH, KW = g.KW, stride = g.stride, pad = g.pad, pad_mode = g.pad_mode;
+    const int C1 = g.C1, up = g.up, ld_fwd = f.ld_fwd;
+    ConvArgs a;
+    int vec;
+    const int rc = fwd_setup(f, g, a, vec, "e2e_conv2d_fwd");
+    if (rc != E2E_OK) return rc;
     // the RGB stem: patch kernel
     if (!force.bm && KH == 7 && KW == 7 && stride == 2 && pad == 3 && pad_mode == 0 && Cin == 3 && Cout == 64 && C1 == Cin && up == 1 && !f.residual && ld_fwd >= 64) {
         StemArgs t{f.src0, f.w_fwd, f.scale, f.shift, f.out, B, Hs, Ws, a.Hd, a.Wd, ld_fwd, f.act, g.in_sub, g.in_mul};
@@ -3058,6 +3244,88 @@ int e2e_conv2d_fwd_tuned(const float* src0, const float* src1, int C1, int up, c
     E2E_REQUIRE(tuning_ok(tile_m, tile_n, ksplit), E2E_ERR_ARG, "e2e_conv2d_fwd_tuned: unsupported decomposition %d x %d / %d", tile_m, tile_n, ksplit);
     GEOM_LAYER(g); GEOM_SOURCES(g);
     return conv_fwd_impl(FwdOps{src0, src1, w_fwd, ld_fwd, scale, shift, residual, out, act}, g, workspace, GemmCfg{tile_m, tile_n, ksplit}, stream);
+}
+
+// ---- forward of a stage entry: conv1 and the downsample branch of one block input (k_conv_fwd_pair) -------------------------------------
+struct EntryOps {
+    const float* x;
+    const float *w1_fwd; int ld1; const float *scale1, *shift1; float* out1; int act1; float* workspace1;
+    const float* wd_fwd; int ldd; const float *gamma, *beta, *mean, *var; float eps; float *bn_scale, *bn_shift, *bn_rstd, *z, *y;
+};
+// What an entry call will run: both setups, both plans (each the one its own e2e_conv2d_fwd call takes: conv1 with its workspace, the
+// 1x1 branch without one), and whether the two main launches are ONE k_conv_fwd_pair launch.
+struct EntryPlan { ConvArgs a1, ad; int vec1, vecd; GemmLaunch p1, pd; ConvGeom g1, gd; bool paired; };
+
+static int fwd_entry_plan(const EntryOps& q, const ConvGeom& g, EntryPlan& P, const char* who) {
+    E2E_REQUIRE(q.gamma && q.beta && q.mean && q.var && q.bn_scale && q.bn_shift && q.bn_rstd && q.z && q.y, E2E_ERR_ARG, "%s: bad argument", who);
+    E2E_REQUIRE(g.pad_mode == 0 && g.C1 == g.Cin && g.up == 1, E2E_ERR_ARG, "%s: a stage entry reads one zero-padded full-resolution source", who);
+    P.g1 = g;
+    P.gd = g; P.gd.KH = P.gd.KW = 1; P.gd.pad = 0;
+    int rc = fwd_setup(FwdOps{q.x, nullptr, q.w1_fwd, q.ld1, q.scale1, q.shift1, nullptr, q.out1, q.act1}, P.g1, P.a1, P.vec1, who);
+    if (rc != E2E_OK) return rc;
+    rc = fwd_setup(FwdOps{q.x, nullptr, q.wd_fwd, q.ldd, nullptr, nullptr, nullptr, q.z, ACT_NONE}, P.gd, P.ad, P.vecd, who);
+    if (rc != E2E_OK) return rc;
+    E2E_REQUIRE(P.a1.Hd == P.ad.Hd && P.a1.Wd == P.ad.Wd, E2E_ERR_ARG, "%s: the two branches must produce the same output grid", who);
+    P.paired = false;
+    // (Cout >= 128 keeps both convolutions off e2e_conv2d_fwd's patch kernels, which serve 64 and 16 output channels)
+    if (P.vec1 != 4 || P.vecd != 4 || g.Cout < 128) return E2E_OK;
+    P.p1 = plan_gemm<false>(P.a1, 4, q.workspace1, GemmCfg{0, 0, 0});
+    P.pd = plan_gemm<false>(P.ad, 4, nullptr, GemmCfg{0, 0, 0});
+    auto t14 = [](const GemmLaunch& p) { return p.kind == GK_TILE && p.cb == 32 && p.c.bm == 32 && p.c.bn == 128; };
+    P.paired = t14(P.p1) && t14(P.pd) && P.pd.tail == GT_NONE && P.ad.ksplit == 1 && P.pd.g.z == 1;
+    return E2E_OK;
+}
+
+/* A stage entry's forward.  conv1: out1 = act1(scale1 * conv(x, w1) + shift1), KH x KW with `stride` / `pad`, zero padding (what
+ * e2e_conv2d_fwd computes with these operands and workspace1).  Downsample branch: z = conv(x, wd), 1 x 1 with the same stride and no
+ * padding (e2e_conv2d_fwd without a workspace), the folded BatchNorm vectors (e2e_bn_fold) and y = z * bn_scale + bn_shift
+ * (e2e_affine_fwd).  Where both GEMMs resolve to the tile k_conv_fwd_pair carries they and the fold / affine are ONE launch (followed by
+ * conv1's split-K epilogue, if it is split); every other combination runs the four launch sequences one after the other.  Bit-identical
+ * to the separate calls either way. */
+int e2e_conv2d_fwd_entry_pair(const float* x, const float* w1_fwd, int ld1, const float* scale1, const float* shift1, float* out1, int act1,
+                              float* workspace1, const float* wd_fwd, int ldd, const float* gamma, const float* beta, const float* running_mean,
+                              const float* running_var, float eps, float* bn_scale, float* bn_shift, float* bn_rstd, float* z, float* y, int B, int Hs,
+                              int Ws, int Cin, int Cout, int KH, int KW, int stride, int pad, void* stream) {
+    const int pad_mode = 0, C1 = Cin, up = 1;
+    const float in_sub = 0.f, in_mul = 1.f;
+    GEOM_LAYER(g); GEOM_SOURCES(g);
+    const EntryOps q{x, w1_fwd, ld1, scale1, shift1, out1, act1, workspace1, wd_fwd, ldd, gamma, beta, running_mean, running_var, eps, bn_scale, bn_shift, bn_rstd, z, y};
+    EntryPlan P;
+    int rc = fwd_entry_plan(q, g, P, "e2e_conv2d_fwd_entry_pair");
+    if (rc != E2E_OK) return rc;
+    const hipStream_t st = (hipStream_t)stream;
+    if (!P.paired) {
+        rc = conv_fwd_impl(FwdOps{x, nullptr, w1_fwd, ld1, scale1, shift1, nullptr, out1, act1}, P.g1, workspace1, GemmCfg{0, 0, 0}, stream);
+        if (rc != E2E_OK) return rc;
+        rc = conv_fwd_impl(FwdOps{x, nullptr, wd_fwd, ldd, nullptr, nullptr, nullptr, z, ACT_NONE}, P.gd, nullptr, GemmCfg{0, 0, 0}, stream);
+        if (rc != E2E_OK) return rc;
+        rc = e2e_bn_fold(gamma, beta, running_mean, running_var, eps, bn_scale, bn_shift, bn_rstd, Cout, stream);
+        if (rc != E2E_OK) return rc;
+        return e2e_affine_fwd(z, bn_scale, bn_shift, nullptr, 0, y, (int64_t)B * P.ad.Hd * P.ad.Wd * Cout, Cout, stream);
+    }
+    FwdPairGrid pg;
+    pg.agx = P.p1.g.x; pg.agy = P.p1.g.y; pg.agz = P.p1.g.z;
+    pg.bgx = P.pd.g.x; pg.bgy = P.pd.g.y;
+    pg.first = (pg.agx * pg.agy * pg.agz + 7u) / 8u * 8u;
+    const BnFoldArgs bn{gamma, beta, running_mean, running_var, eps, bn_scale, bn_shift, bn_rstd, y};
+    hipLaunchKernelGGL(k_conv_fwd_pair, dim3(pg.first + pg.bgx * pg.bgy), dim3(256), 0, st, P.a1, P.ad, bn, pg);
+    launch_gemm_tail(P.a1, P.p1, st);
+    E2E_LAUNCH_CHECK("e2e_conv2d_fwd_entry_pair");
+    return E2E_OK;
+}
+
+/* 1 where e2e_conv2d_fwd_entry_pair runs the two GEMMs, the fold and the affine as ONE k_conv_fwd_pair launch, 0 where it falls back to
+ * the separate launches or refuses the arguments.  Host only. */
+int e2e_conv2d_fwd_entry_pair_is_one_launch(int ld1, int ldd, int has_workspace1, int B, int Hs, int Ws, int Cin, int Cout, int KH, int KW, int stride, int pad) {
+    static float nowhere[4];                                 // stands for every operand: the plan looks at which pointers are NULL, never through them
+    float* const p = nowhere;
+    const int pad_mode = 0, C1 = Cin, up = 1;
+    const float in_sub = 0.f, in_mul = 1.f;
+    GEOM_LAYER(g); GEOM_SOURCES(g);
+    const EntryOps q{p, p, ld1, p, p, p, ACT_RELU, has_workspace1 ? p : nullptr, p, ldd, p, p, p, p, 0.f, p, p, p, p, p};
+    EntryPlan P;
+    if (fwd_entry_plan(q, g, P, "e2e_conv2d_fwd_entry_pair_is_one_launch") != E2E_OK) return 0;
+    return P.paired ? 1 : 0;
 }
 
 // backward-data up to its GEMM: checks the arguments, serves the 16 -> 16 reflection-padded layer with its patch kernel (*done = true), or
@@ -3197,6 +3465,14 @@ int e2e_head_bwd_act(const float* dz, const float* x, const float* w, float* dx,
     E2E_REQUIRE(dz && x && w && workspace && B > 0 && H >= 2 && W >= 2 && Cin == HC && in_act >= 0 && in_act <= 2, E2E_ERR_ARG, "e2e_head_bwd: bad argument");
     E2E_REQUIRE((int64_t)B * H * W * HC < (1ll << 31), E2E_ERR_ARG, "e2e_head_bwd: activation too large for 32-bit element offsets");
     hipStream_t st = (hipStream_t)stream;
+    // both gradients: one pass over x and dZ (k_head_bwd_fused, bit-identical); E2E_HEAD_BWD_FUSED=0 runs the two kernels (A/B comparison, bisecting)
+    const char* ev = getenv("E2E_HEAD_BWD_FUSED");
+    if (dx && dw && !(ev && ev[0] == '0')) {
+        hipLaunchKernelGGL(k_head_bwd_fused, dim3(HEAD_PARTS), dim3(256), 0, st, dz, x, w, dx, workspace, B, H, W, in_act);
+        hipLaunchKernelGGL(k_head_wreduce, dim3(9 * HC + 1), dim3(256), 0, st, workspace, HEAD_PARTS, dw, dbias);
+        E2E_LAUNCH_CHECK("e2e_head_bwd");
+        return E2E_OK;
+    }
     if (dx) hipLaunchKernelGGL(k_head_bwd_data, dim3(egrid((int64_t)B * H * W * 4)), dim3(256), 0, st, dz, w, dx, B, H, W, x, in_act);
     if (dw) {
         hipLaunchKernelGGL(k_head_bwd_weight, dim3(HEAD_PARTS), dim3(256), 0, st, dz, x, workspace, B, H, W);

@@ -116,6 +116,9 @@ class _Conv:
         # adds this layer's gradient to the block input (pre_add) -- no separate accumulate pass; `res_aliased`: the residual tensor
         # has no activation and no other consumer (downsample branch), its gradient buffer IS this layer's
         self.res_via, self.res_aliased, self.pre_from = None, False, None
+        # stage entry (NetPlan.__init__): `entry` on conv1 = (the downsample convolution, its BatchNorm); conv1's forward call then runs both
+        # branches (e2e_conv2d_fwd_entry_pair) and the two ops it names, marked `fwd_in`, launch nothing of their own
+        self.entry, self.fwd_in = None, None
         self.reduce_desc = L.WgradReduceDesc()               # filled by every backward-weight launch (identical every time: the plan is static)
 
     def layout_row(self):
@@ -125,6 +128,17 @@ class _Conv:
     def fwd(self, plan, st, slot=None):
         """slot None: the whole batch; an int: that image of the batch alone (B = 1 launch on the slot's part of every buffer)."""
         s = self
+        if s.fwd_in is not None:
+            return
+        if s.entry is not None:
+            ds, bn = s.entry
+            b = bn.bn
+            L.call("e2e_conv2d_fwd_entry_pair", geom=s.geom, B=s.src0.B if slot is None else 1, x=_at(s.src0.t, slot), w1_fwd=L.ptr(s.wf), ld1=s.ldf,
+                   scale1=L.ptr(s.scale), shift1=L.ptr(s.shift), out1=_at(s.out.t, slot), act1=s.act, workspace1=L.ptr(s.ws_f), wd_fwd=L.ptr(ds.wf),
+                   ldd=ds.ldf, gamma=L.ptr(b.weight), beta=L.ptr(b.bias), running_mean=L.ptr(b.running_mean), running_var=L.ptr(b.running_var),
+                   eps=float(b.eps), bn_scale=L.ptr(bn.scale), bn_shift=L.ptr(bn.shift), bn_rstd=L.ptr(bn.rstd), z=_at(ds.out.t, slot),
+                   y=_at(bn.out.t, slot), stream=st)
+            return
         L.call("e2e_conv2d_fwd", geom=s.geom, B=s.src0.B if slot is None else 1, src0=_at(s.src0.t, slot),
                src1=_at(s.src1.t, slot) if s.src1 is not None else None, w_fwd=L.ptr(s.wf), ld_fwd=s.ldf, scale=L.ptr(s.scale),
                shift=L.ptr(s.shift if s.bias is None else s.bias), residual=_at(s.res.t, slot) if s.res is not None else None,
@@ -240,8 +254,11 @@ class _BNAffine:
         self.out = Buf(src.B, src.h, src.w, C, plan.dev)
         self.scale, self.shift, self.rstd = (torch.empty(C, device=plan.dev, dtype=_f32) for _ in range(3))
         self.ws = torch.empty(L.load().e2e_affine_bwd_workspace_floats(C), device=plan.dev, dtype=_f32)
+        self.fwd_in = None                              # the stage entry's conv1, where its forward call does this op's work (_Conv.entry)
 
     def fwd(self, plan, st, slot=None):
+        if self.fwd_in is not None:
+            return
         b, s = self.bn, self.src
         L.call("e2e_bn_fold", L.ptr(b.weight), L.ptr(b.bias), L.ptr(b.running_mean), L.ptr(b.running_var), float(b.eps), L.ptr(self.scale),
                L.ptr(self.shift), L.ptr(self.rstd), s.C, st)
@@ -270,6 +287,9 @@ class NetPlan:
         self.paired = os.environ.get("E2E_PAIRED_BWD", "1") != "0"
         # ... and the paired launches carry the slab reductions of the layers before them (E2E_CARRY_REDUCE=0: one batched launch per half, as before)
         self.carry = self.paired and not overlap and os.environ.get("E2E_CARRY_REDUCE", "1") != "0"
+        # a stage entry's conv1, downsample convolution, BatchNorm fold and affine as one forward call (e2e_conv2d_fwd_entry_pair); E2E_FWD_ENTRY_PAIR=0
+        # issues the four separately (results are bit-identical either way)
+        self.entry_pair = os.environ.get("E2E_FWD_ENTRY_PAIR", "1") != "0"
         self.B, self.H, self.W = B, H, W
         if H % 32 or W % 32:
             raise ValueError(f"launch plan: the encoder halves the image five times and the decoder doubles it back before every skip "
@@ -313,6 +333,13 @@ class NetPlan:
                 elif isinstance(idt_op, _BNAffine) and idt.act == 0:
                     idt.g = c2.out.g                       # identity branch without activation and with ONE consumer: share the gradient buffer
                     c2.res_aliased = True
+                if blk.downsample is not None and isinstance(idt_op, _BNAffine) and self.entry_pair:
+                    ds = self.ops[self.ops.index(idt_op) - 1]
+                    # both branches read the block input at the same stride; the 1x1 one is unpadded and runs unsplit (no workspace)
+                    if (ds.out is idt_op.src and ds.src0 is c1.src0 and (ds.KH, ds.KW, ds.pad, ds.stride) == (1, 1, 0, c1.stride) and ds.ws_f is None
+                            and c1.direct and c1.res is None and (c1.isub, c1.imul) == (0.0, 1.0) and c1.bias is None and (ds.Ho, ds.Wo) == (c1.Ho, c1.Wo)):
+                        c1.entry = (ds, idt_op)
+                        ds.fwd_in = idt_op.fwd_in = c1
             feats.append(x)
         self.features = feats
         x = feats[-1]

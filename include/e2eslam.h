@@ -712,6 +712,23 @@ int e2e_conv2d_bwd_pair_is_one_launch(int ld_bwd, int B, int Hs, int Ws, int Cin
                                       int KH, int KW, int stride, int pad, int pad_mode, int accumulate,
                                       int in_act, int has_pre_add, int has_workspace, int has_src1, int C1,
                                       int up, int has_bias);
+/* Forward of a stage entry (the first BasicBlock of an encoder stage) on ONE block input x: conv1 -- out1 = act1(scale1 * conv(x, w1) +
+ * shift1), KH x KW with `stride` / `pad`, zero padding, exactly e2e_conv2d_fwd with these operands and workspace1 -- and the downsample
+ * branch -- z = conv(x, wd), 1 x 1, same stride, no padding (e2e_conv2d_fwd without a workspace); bn_scale / bn_shift / bn_rstd as
+ * e2e_bn_fold gives them; y = z * bn_scale + bn_shift as e2e_affine_fwd gives it.  Where both GEMMs resolve to the 32 x 128 tile at
+ * chunk depth 32 (e2e_conv2d_fwd_entry_pair_is_one_launch) all of it is ONE launch whose grid carries both tile sets, followed by conv1's
+ * split-K epilogue when conv1 is split; otherwise the four launch sequences run one after the other.  Bit-identical to the separate
+ * calls either way.  z is the tensor the BatchNorm's backward reads (e2e_affine_bwd). */
+int e2e_conv2d_fwd_entry_pair(const float* x, const float* w1_fwd, int ld1, const float* scale1, const float* shift1,
+                              float* out1, int act1, float* workspace1, const float* wd_fwd, int ldd,
+                              const float* gamma, const float* beta, const float* running_mean,
+                              const float* running_var, float eps, float* bn_scale, float* bn_shift, float* bn_rstd,
+                              float* z, float* y, int B, int Hs, int Ws, int Cin, int Cout, int KH, int KW, int stride,
+                              int pad, void* stream);
+/* Host only: 1 where e2e_conv2d_fwd_entry_pair runs as ONE launch (decided by the code the call itself uses), 0 where it falls back to the
+ * separate launches or refuses the arguments.  has_workspace1: conv1's workspace is non-NULL. */
+int e2e_conv2d_fwd_entry_pair_is_one_launch(int ld1, int ldd, int has_workspace1, int B, int Hs, int Ws, int Cin,
+                                            int Cout, int KH, int KW, int stride, int pad);
 long long e2e_wgrad_reduce_batch_prepare(e2e_wgrad_reduce_desc* descs_host, int n);
 int e2e_wgrad_reduce_batched(const e2e_wgrad_reduce_desc* descs_dev, int n, long long total_items, void* stream);
 /* the work items [first_item, first_item + items) of a prepared table: the layers (or parts of layers) in that range and nothing else */
@@ -775,7 +792,9 @@ int e2e_head_bwd(const float* dz, const float* x, const float* w, float* dx, flo
                  float* workspace, int B, int H, int W, int Cin, void* stream);
 
 /* e2e_head_bwd whose dx is multiplied by act'(x) (in_act 1 ReLU / 2 ELU, from the activation's output x): the pre-activation
- * gradient of the layer that produced x (launch plan form, see e2e_conv2d_bwd_data_fused). */
+ * gradient of the layer that produced x (launch plan form, see e2e_conv2d_bwd_data_fused).  With both dx and dw asked for, the two
+ * gradients come out of ONE pass over x and dz (same partition and summation orders: bit-identical); the environment variable
+ * E2E_HEAD_BWD_FUSED=0, read by every call, restores the two kernels. */
 int e2e_head_bwd_act(const float* dz, const float* x, const float* w, float* dx, float* dw, float* dbias,
                      float* workspace, int B, int H, int W, int Cin, int in_act, void* stream);
 
