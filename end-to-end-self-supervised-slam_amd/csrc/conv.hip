@@ -2023,6 +2023,167 @@ __global__ __launch_bounds__(256) void k_wgrad3x3_thin(ThinWgradArgs a) {
             }
 }
 
+// The same kernel with the dZ operand kept out of LDS (the product's form; k_wgrad3x3_thin above stays for E2E_THIN_WGRAD_REGS=0).
+// A wave reads only its own tile row of dZ, and for a fixed k-step its 64 lanes (kq, l16) need dZ[y0 + wave][x0 + 4 ks + kq][16 mt + l16]:
+// 4 pixels x 16 channels, one 256-byte run for 16 output channels, four 64-byte runs per mt for 32.  Every lane loads its 16 MT values of
+// a tile straight into registers in MFMA layout (buffer loads on a resource that covers the wave's ROW: a pixel past the row's end or a
+// row below the image is out of range and reads as the zero the LDS path writes), so LDS holds the input patch only: 25 344 B against
+// 41 728 / 58 112.  Where a workgroup walks more than one tile the next tile's operands are fetched under the current tile's MFMAs: the
+// next patch goes to registers before the sweep and to LDS after its barrier, and each dZ register is refilled with the next tile's value
+// right after the k-step that consumed it (an out-of-range offset when there is no next tile).  The bias column's MFMA (one in ten) is
+// issued only by the workgroups that store it (has_bias && hf == 0, workgroup-uniform).  Every accumulator still receives its MFMAs in
+// the order tiles ascending, k-steps ascending, the waves are summed in the same tree ((w0 + w2) + (w1 + w3)) -- one half (mt) of the
+// accumulators at a time, so that the scratch fits the patch's LDS -- and wgrad_plan's partition is untouched: every slab is bit for bit
+// the slab of the kernel above.
+template <int MT, bool BIAS>                                 // BIAS: this workgroup computes (and stores) the bias column
+__device__ __forceinline__ void wgrad3x3_thin_regs_body(const ThinWgradArgs& a, float* smem) {
+    constexpr int TH = 4, TW = 64, PH = TH + 2, PW = TW + 2, CO = 16 * MT, NA = 10 * MT, PJ = PH + 1;
+    constexpr unsigned OOB = 0x80000000u;
+    static_assert(2 * 10 * 4 * 64 <= PH * PW * 16, "reduction scratch: ten accumulators of two waves");
+    static_assert(TW * 4 == 256 && (PW - TW) * PH * 4 <= 256, "patch loads: one row of 64 pixels per pass, the rest in one");
+    float* patch = smem;                                     // [py][px][ci]
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), l16 = lane & 15, kq = lane >> 4;
+    const int nhalf = a.Cin >> 4, n0 = a.C1 >> 4;
+    const int b = blockIdx.z / nhalf, hf = blockIdx.z % nhalf;
+    const bool first = hf < n0;
+    const int sh = first ? (a.up >> 1) : 0, Cs = first ? a.C1 : a.Cin - a.C1, cs0 = (first ? hf : hf - n0) * 16;
+    const int Hs = a.Hd >> sh, Ws = a.Wd >> sh;
+    const int y0 = blockIdx.y * TH;
+    const float* sb = (first ? a.src0 : a.src1) + (int64_t)b * Hs * Ws * Cs + cs0;
+    const int tx0 = blockIdx.x * a.tiles_x;
+    const int ntl = min(a.tiles_x, (a.Wd + TW - 1) / TW - tx0);                  // tiles this workgroup walks (workgroup-uniform)
+    // this wave's row of dZ as a buffer of its own: Wd x CO floats, none if the row lies below the image
+    const int yr = y0 + wave;
+    const __amdgpu_buffer_rsrc_t rz = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)(a.dz + ((int64_t)b * a.Hd + min(yr, a.Hd - 1)) * a.Wd * CO), 0, yr < a.Hd ? a.Wd * CO * 4 : 0, 0x00020000);
+    const unsigned zl = (unsigned)(kq * CO + l16) * 4u;      // A[m = co][k = pixel]: dZ[row = wave][4 ks + kq][co = 16 mt + l16]
+    float areg[TW / 4][MT];
+    f4v preg[PJ];
+    auto load_dz = [&](unsigned zo) {                        // zo: byte offset of the tile's first pixel in the row + zl, or OOB
+#pragma unroll
+        for (int ks = 0; ks < TW / 4; ++ks)
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt)
+                areg[ks][mt] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rz, zo + (unsigned)(ks * 4 * CO + mt * 16) * 4u, 0, 0));
+    };
+    // patch: 16 channels = 4 quads per pixel, quad-fastest (64-byte runs).  Load j < PH takes quad `tid` of patch row j (pixels 0 .. 63: the
+    // source row is workgroup-uniform, the column the same for all six), load PH the two last pixels of the six rows (threads 0 .. 47)
+    const int pq = tid & 3, ppx = tid >> 2;
+    const int epy = min(tid >> 3, PH - 1), epx = TW + ((tid >> 2) & 1);
+    auto src_row = [&](int py) { return min(max(reflect1(y0 - 1 + py, a.Hd), 0), a.Hd - 1) >> sh; };
+    auto src_col = [&](int X) { return min(max(reflect1(X, a.Wd), 0), a.Wd - 1) >> sh; };
+    const int erow = src_row(epy) * Ws;
+    auto load_patch = [&](int x0) {
+        const int c = src_col(x0 - 1 + ppx) * Cs + pq * 4;
+#pragma unroll
+        for (int j = 0; j < PH; ++j) preg[j] = *(const f4v*)(sb + (int64_t)src_row(j) * Ws * Cs + c);
+        preg[PH] = *(const f4v*)(sb + (int64_t)(erow + src_col(x0 - 1 + epx)) * Cs + pq * 4);
+    };
+    auto store_patch = [&]() {
+#pragma unroll
+        for (int j = 0; j < PH; ++j) *(f4v*)&patch[(j * PW * 4 + tid) * 4] = preg[j];
+        if (tid < PH * 8) *(f4v*)&patch[((epy * PW + epx) * 4 + pq) * 4] = preg[PH];
+    };
+    f4v acc[NA];
+#pragma unroll
+    for (int t = 0; t < NA; ++t) acc[t] = (f4v){0.f, 0.f, 0.f, 0.f};
+    const float one = (l16 == 0) ? 1.f : 0.f;                // B operand of the bias column: n = 0 only
+    const float* bp = patch + (wave * PW + kq) * 16 + l16;   // B[k = pixel][n = ci]: X[row + kh][4 ks + kq + kw][ci = l16]
+    // one tile: per 4 pixels one A register feeds 9 MFMAs (+ 1 for the bias column), then takes the next tile's value
+    auto sweep = [&](unsigned zn) {
+        float bv[9];
+#pragma unroll
+        for (int t = 0; t < 9; ++t) bv[t] = bp[((t / 3) * PW + (t % 3)) * 16];
+#pragma unroll
+        for (int ks = 0; ks < TW / 4; ++ks) {
+            float bn[9];                                     // the next k-step's B values, read under this one's MFMAs
+#pragma unroll
+            for (int t = 0; t < 9; ++t) bn[t] = ks + 1 < TW / 4 ? bp[((t / 3) * PW + (t % 3)) * 16 + (ks + 1) * 64] : 0.f;
+#pragma unroll
+            for (int t = 0; t < 9; ++t)
+#pragma unroll
+                for (int mt = 0; mt < MT; ++mt) acc[mt * 10 + t] = __builtin_amdgcn_mfma_f32_16x16x4f32(areg[ks][mt], bv[t], acc[mt * 10 + t], 0, 0, 0);
+            if constexpr (BIAS) {
+#pragma unroll
+                for (int mt = 0; mt < MT; ++mt) acc[mt * 10 + 9] = __builtin_amdgcn_mfma_f32_16x16x4f32(areg[ks][mt], one, acc[mt * 10 + 9], 0, 0, 0);
+            }
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt)
+                areg[ks][mt] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rz, zn + (unsigned)(ks * 4 * CO + mt * 16) * 4u, 0, 0));
+#pragma unroll
+            for (int t = 0; t < 9; ++t) bv[t] = bn[t];
+            __builtin_amdgcn_sched_barrier(0);               // keeps the unrolled k-steps apart: without it the scheduler hoists the LDS reads of
+        }                                                    // all sixteen and the kernel spills
+    };
+    if (ntl > 0) {
+        load_dz((unsigned)(tx0 * TW * CO) * 4u + zl);
+        load_patch(tx0 * TW);
+        store_patch();
+    }
+    __syncthreads();
+    for (int tx = 0; tx < ntl; ++tx) {
+        const bool more = tx + 1 < ntl;
+        const int xn = (tx0 + tx + 1) * TW;
+        const unsigned zn = more ? (unsigned)(xn * CO) * 4u + zl : OOB;
+        if (more) load_patch(xn);
+        sweep(zn);
+        __syncthreads();                                     // every wave is done with the patch
+        if (more) {
+            store_patch();
+            __syncthreads();
+        }
+    }
+    // ---- cross-wave sum in a fixed tree ((w0 + w2) + (w1 + w3)) through LDS, ten accumulators (one mt) at a time, then the slab --------
+    float* red = smem;                                       // [2 waves][10 x 4][64 lanes]: the patch is dead after the loop's last barrier
+    const int64_t sid = ((int64_t)b * gridDim.y + blockIdx.y) * a.nxg + blockIdx.x;
+    float* slab = a.slabs + sid * CO * a.npad;
+    const int kconv = 9 * a.Cin, cg0 = hf * 16;              // D[m = co][n]: lane (kq, l16) holds co = 16 mt + 4 kq + i, n = l16
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) {
+        if (mt > 0) __syncthreads();                         // wave 0 has read the previous half
+        if (wave >= 2) {
+#pragma unroll
+            for (int t = 0; t < 10; ++t)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) red[((wave - 2) * 40 + t * 4 + i) * 64 + lane] = acc[mt * 10 + t][i];
+        }
+        __syncthreads();
+        if (wave < 2) {
+#pragma unroll
+            for (int t = 0; t < 10; ++t)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) acc[mt * 10 + t][i] += red[(wave * 40 + t * 4 + i) * 64 + lane];
+        }
+        __syncthreads();
+        if (wave == 1) {
+#pragma unroll
+            for (int t = 0; t < 10; ++t)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) red[(t * 4 + i) * 64 + lane] = acc[mt * 10 + t][i];
+        }
+        __syncthreads();
+        if (wave == 0) {
+#pragma unroll
+            for (int t = 0; t < 10; ++t)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const float v = acc[mt * 10 + t][i] + red[(t * 4 + i) * 64 + lane];
+                    const int co = mt * 16 + 4 * kq + i;
+                    if (t < 9) slab[co * a.npad + t * a.Cin + cg0 + l16] = v;
+                    else if (BIAS && l16 == 0) slab[co * a.npad + kconv] = v;
+                }
+        }
+    }
+}
+
+template <int MT>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MT == 1 ? 4 : 2))) void k_wgrad3x3_thin_regs(ThinWgradArgs a) {
+    __shared__ float smem[6 * 66 * 16];
+    // two copies of the body, not a test per k-step: a branch inside the sweep keeps the scheduler from reading LDS ahead across k-steps
+    if (a.has_bias && blockIdx.z % (a.Cin >> 4) == 0) wgrad3x3_thin_regs_body<MT, true>(a, smem);
+    else wgrad3x3_thin_regs_body<MT, false>(a, smem);
+}
+
 // Backward-weight of the RGB stem from the same staged patch: dW[co][k] = sum_p dZ[p][co] * patch(p, k), k = (kh, kw, ci) < 147.
 // Every wave owns 16 output channels (M) and all ten 16-column tiles of k (N, 160 >= 148) -- no cross-wave sum; K = the tile's pixels,
 // 4 per MFMA: one A read (dZ) feeds ten MFMAs.  A workgroup sweeps `tiles_x` tiles and writes one slab [64][148].
@@ -2875,7 +3036,8 @@ struct GemmCfg { int bm, bn, S; };
 // 128-byte line) -- except for the shape with 2 x 2 blocks per wave, which exists at depth 16 only.
 #define CONV_TILE_SHAPES(X)                                                                                      \
     X(64, 64, 2, 2, 1, 1, 32) X(128, 64, 2, 2, 2, 1, 32) X(128, 128, 2, 2, 2, 2, 16) X(128, 32, 4, 1, 1, 1, 32) \
-    X(32, 128, 1, 4, 1, 1, 32) X(32, 64, 1, 2, 1, 1, 32) X(64, 32, 2, 1, 1, 1, 32) X(32, 32, 1, 1, 1, 1, 32)
+    X(32, 128, 1, 4, 1, 1, 32) X(32, 64, 1, 2, 1, 1, 32) X(64, 32, 2, 1, 1, 1, 32) X(32, 32, 1, 1, 1, 1, 32) \
+    X(32, 96, 1, 3, 1, 1, 32) X(64, 96, 2, 3, 1, 1, 32)
 static int tile_max_cb(int bm, int bn) {                   // 0: unsupported shape
 #define X(BM, BN, WM, WN, TM, TN, MAXCB) if (bm == BM && bn == BN) return MAXCB;
     CONV_TILE_SHAPES(X)
@@ -2941,6 +3103,15 @@ static GemmCfg choose_cfg(int64_t rows, int cols, int K, int cb, bool allow_spli
             S = best;
         }
         c.S = S;
+    }
+    // 65 .. 96 columns: ONE column tile of three 32-column wave blocks instead of two 64-column tiles, a quarter of whose waves run
+    // prologue, staging, MFMAs and epilogue on zero padding.  The slice count above stays the one the 64 x 64 tiling gives and the K order
+    // of every sum is unchanged: bit-identical.  Rows (tools/gemm_tune.py, profiles/decoder_tail_gemm_tune.txt, up(1,1) backward-data
+    // 155 848 x 96 x 288): 32 x 96 110.8 us, 64 x 64 121.4, 64 x 96 135.7 at batch 2 (its six waves fall unevenly on the four SIMDs: two of
+    // them carry two); at batch 1 65.7 / 64.9 / 69.3, level.  In the step's trace 123.3 -> 111.7 us.  E2E_TILE96=0 keeps 64 x 64, =64 takes 64 x 96 (A/B comparison, bisecting).
+    if (cols > 64 && cols <= 96) {
+        const char* ev = getenv("E2E_TILE96");
+        if (!(ev && ev[0] == '0')) { c.bm = ev && ev[0] == '6' ? 64 : 32; c.bn = 96; }
     }
     return c;
 }
@@ -3505,7 +3676,8 @@ static WgradPlan wgrad_plan(WgradPath path, const ConvGeom& g, int has_bias, boo
         p.S = (int64_t)B * p.ny * p.nxg; p.Mpad = 64; p.Npad = 148;
     } else if (path == WP_THIN) {    // k_wgrad3x3_thin: workgroups of `tiles_x` consecutive 4 x 64 tiles, ~1200 of them; one slab per workgroup position
         // measured against the implicit-GEMM kernels (tools/gemm_tune.py wgrad): upconv(0,1) 16 -> 16: 94 -> 66 us, upconv(0,0) 32 -> 16: 55 -> 45 us,
-        // upconv(1,1) 96 -> 32: 174 -> 142 us; upconv(1,0) 64 -> 32 is faster as a GEMM (39 vs 46 us) and stays there
+        // upconv(1,1) 96 -> 32: 174 -> 142 us; upconv(1,0) 64 -> 32 is faster as a GEMM (39 vs 46 us) and stays there.  With dZ in registers
+        // (k_wgrad3x3_thin_regs, same partition, same slabs): 49.8 -> 39.5, 34.3 -> 25.2 and 141.1 -> 109.6 us in the step's trace
         if (tuned || !(KH == 3 && KW == 3 && ((Cout == 16 && (Cin == 16 || Cin == 32)) || (Cout == 32 && Cin == 96)))) return p;
         const int txt = (Wo + 63) / 64;
         p.ny = (Ho + 3) / 4;
@@ -3631,7 +3803,13 @@ static int wgrad_setup(const WgradIn& in, const ConvGeom& g, int wg_target, cons
     } else if (p.path == WP_THIN) {
         ThinWgradArgs ta{in.dz, in.src0, in.src1, in.workspace, B, Ho, Wo, Cin, g.C1, g.up, p.Npad, a.has_bias, p.tiles_x, p.nxg};
         const dim3 tg((unsigned)p.nxg, (unsigned)p.ny, (unsigned)(B * (Cin / 16)));
-        if (Cout == 32) hipLaunchKernelGGL((k_wgrad3x3_thin<2>), tg, dim3(256), 0, st, ta);
+        // dZ in registers, the next tile's loads under the MFMAs (k_wgrad3x3_thin_regs, bit-identical slabs); E2E_THIN_WGRAD_REGS=0 runs the
+        // kernel that stages dZ in LDS (A/B comparison, bisecting)
+        const char* ev = getenv("E2E_THIN_WGRAD_REGS");
+        const bool regs = !(ev && ev[0] == '0') && (int64_t)Wo * Cout * 4 < (1ll << 31);
+        if (regs && Cout == 32) hipLaunchKernelGGL((k_wgrad3x3_thin_regs<2>), tg, dim3(256), 0, st, ta);
+        else if (regs) hipLaunchKernelGGL((k_wgrad3x3_thin_regs<1>), tg, dim3(256), 0, st, ta);
+        else if (Cout == 32) hipLaunchKernelGGL((k_wgrad3x3_thin<2>), tg, dim3(256), 0, st, ta);
         else hipLaunchKernelGGL((k_wgrad3x3_thin<1>), tg, dim3(256), 0, st, ta);
     } else if (p.path == WP_TAPS) {
         TapWgradArgs ta{in.dz, in.src0, in.src1, in.workspace, B, Ho, Wo, Cin, g.C1, g.up, Cout, g.pad_mode == 1 ? 1 : 0, a.has_bias,

@@ -576,7 +576,7 @@ int64_t e2e_conv2d_bwd_data_workspace_floats(int B, int Hd, int Wd, int cols, in
 int e2e_conv_workspace_flag_floats(void);
 int e2e_conv_streamk_error_index(void);
 /* Tuned forms (tools/gemm_tune.py, tests/test_gpu_conv.py): the same operators with the GEMM decomposition given PER CALL -- the
- * library keeps no mutable tuning state.  tile_m x tile_n in {64x64, 128x64, 128x128, 128x32, 32x128, 32x64, 64x32, 32x32};
+ * library keeps no mutable tuning state.  tile_m x tile_n in {64x64, 128x64, 128x128, 128x32, 32x128, 32x64, 64x32, 32x32, 32x96, 64x96};
  * ksplit >= 1: K slices (split-K slabs + reduction launch); ksplit < 0: stream-K on -ksplit persistent workgroups (64 x 64 tiles:
  * equal shares of the flattened (tile, K chunk) space, partial tiles combined in-launch in K order); tile_m == 0: the built-in choice.
  * workspace: e2e_conv_tuned_workspace_floats(GEMM rows, GEMM columns) floats, flag region zeroed.

@@ -4,7 +4,10 @@ depth network at the benchmark size (batch 2, 480x640), forward and backward-dat
 rounds), next to the decomposition the built-in cost model picks -- the calibration data of `gemm_cost` in conv.hip.
 
     python tools/gemm_tune.py [fwd|bwd|both] > gpurun_out/gemm_tune.txt        (on an MI355X)"""
+# GEMM_TUNE_LAYERS=a,b restricts the layers, GEMM_TUNE_BATCH=n sets the batch (default 2), GEMM_TUNE_ALL=1 lists every decomposition
+# timed instead of the best six.
 import os
+import re
 import sys
 
 import torch
@@ -23,7 +26,7 @@ LAYERS = [
     ("up(2,1)", 64, 64, 2, 120, 160, 64, 3, 1, 1, 1), ("up(1,0)", 64, 0, 1, 120, 160, 32, 3, 1, 1, 1), ("up(1,1)", 32, 64, 2, 240, 320, 32, 3, 1, 1, 1),
     ("up(0,0)", 32, 0, 1, 240, 320, 16, 3, 1, 1, 1), ("up(0,1)", 16, 0, 2, 480, 640, 16, 3, 1, 1, 1),
 ]
-TILES = [(64, 64), (128, 64), (128, 128), (128, 32), (32, 128), (32, 64), (64, 32), (32, 32)]
+TILES = [(64, 64), (128, 64), (128, 128), (128, 32), (32, 128), (32, 64), (64, 32), (32, 32), (32, 96), (64, 96)]
 
 
 def ld(n):
@@ -44,9 +47,9 @@ def timeit(fn, n=12):
 def main():
     which = sys.argv[1] if len(sys.argv) > 1 else "both"
     lib = L.load()
-    B = 2
+    B = int(os.environ.get("GEMM_TUNE_BATCH", "2"))
     st = L.stream()
-    only = [x for x in os.environ.get("GEMM_TUNE_LAYERS", "").split(",") if x]
+    only = re.findall(r"[^,(]+(?:\([^)]*\))?", os.environ.get("GEMM_TUNE_LAYERS", ""))      # names hold commas: up(1,1),layer2
     product_only = os.environ.get("GEMM_TUNE_PRODUCT_ONLY") == "1"
     for name, Cx, Cs, up, H, W, Cout, k, s, p, pm in LAYERS:
         if only and name not in only:
@@ -126,7 +129,7 @@ def main():
                 print(f"{name} {tag}: STREAM-K TIME-OUT FLAG RAISED", flush=True)
             res.sort()
             best = res[0]
-            line = " ".join((f"sk{-S}:{t:.1f}" if S < 0 else f"{bm}x{bn}/{S}:{t:.1f}") for t, bm, bn, S in res[:6])
+            line = " ".join((f"sk{-S}:{t:.1f}" if S < 0 else f"{bm}x{bn}/{S}:{t:.1f}") for t, bm, bn, S in (res if os.environ.get("GEMM_TUNE_ALL") == "1" else res[:6]))
             line += "  || stream-K: " + " ".join(f"sk{-S}:{t:.1f}" for t, bm, bn, S in sorted(res, key=lambda r: r[3]) if S < 0)
             print(f"{name:10s} {tag} {gf:5.2f} GF  auto {t_auto:7.1f} us ({gf / t_auto * 1e3:5.1f} TF/s)  best {best[0]:7.1f} us ({gf / best[0] * 1e3:5.1f} TF/s)  | {line}", flush=True)
 
