@@ -23,7 +23,8 @@ LIBDIR = os.path.join(os.path.dirname(HERE), "lib")
 LIB = os.path.join(LIBDIR, "libe2eslam_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function", "-Wno-unused-result"]
-EXACT = {"pointfusion.hip", "knn.hip", "icp.hip"}          # bit-exact against the oracle: no implicit FMA
+EXACT = {"pointfusion.hip", "knn.hip", "icp.hip",           # bit-exact against the oracle: no implicit FMA
+         "normal_maps_grad.hip"}                            # a x a must be exactly 0 where the forward's cross product is
 
 
 def flags_for(src):

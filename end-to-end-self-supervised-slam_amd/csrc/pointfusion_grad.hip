@@ -1,7 +1,8 @@
 // pointfusion_grad.hip -- the adjoint of the PointFusion map step (k_pf_fuse + k_pf_append of pointfusion.hip) for gfx950, and of the
 // fusion confidence alpha = exp(-|V|^2 / alpha_den) with respect to the depth.  The differentiation rule is stated in
-// include/e2eslam.h: the association, the validity mask, the append order, the pose and the intrinsics are constants, the normals
-// are not differentiated.
+// include/e2eslam.h: the association, the validity mask, the append order, the pose and the intrinsics are constants.  The normals'
+// side of the step (opt-in) is at the end: its own tape and its own backward, the points' rule with N for P; the adjoint of the normal
+// map itself is in normal_maps_grad.hip.
 //
 // One pixel owns one map row and one map row is won by at most one pixel, so everything here is a gather over pixels (lane = pixel:
 // the per-pixel arrays are read and written coalesced, the 12-byte map rows are gathered) plus one streaming pass over the rows of
@@ -224,6 +225,79 @@ __global__ __launch_bounds__(PF_T) void k_vertex_alpha_bwd(const float* __restri
     }
 }
 
+// The normals' side of the map step.  N' = (c N + a Ng[q]) / s, not renormalised: the points' rule with N for P (D = gN . (Ng - N)).
+// The normals tape holds the winner's normal before the step for every fused pixel; row / c come from the step's own tape.
+__global__ __launch_bounds__(PF_T) void k_pft_record_normals(const long long* __restrict__ t_row, const float* __restrict__ nrm, int64_t M,
+                                                             int64_t N, float* __restrict__ t_N) {
+    for (int64_t q = (int64_t)blockIdx.x * PF_T + threadIdx.x; q < N; q += (int64_t)gridDim.x * PF_T) {
+        const long long row = t_row[q];
+        const bool fused = row >= 0 && row < M;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) t_N[q * 3 + j] = fused ? nrm[row * 3 + j] : 0.f;
+    }
+}
+
+__global__ __launch_bounds__(PF_T) void k_pf_fuse_normals_bwd_rows(const float* __restrict__ gN, const float* __restrict__ cc_after,
+                                                                   const unsigned int* __restrict__ hdr, int64_t M_before,
+                                                                   float* __restrict__ g_prevN, float* __restrict__ g_prevcc) {
+    // as k_pf_fuse_bwd_rows: rows that won no pixel pass gN through (a zero-confidence row in a step where anything matched: 0) and
+    // get nothing for their confidence; the winners are overwritten by the pixel pass.  g_prevcc is NULL here under accumulate.
+    const bool fused_any = hdr[0] != 0u;
+    for (int64_t i = (int64_t)blockIdx.x * PF_T + threadIdx.x; i < M_before * 3; i += (int64_t)gridDim.x * PF_T) {
+        if (g_prevN) g_prevN[i] = (fused_any && cc_after[i / 3] == 0.f) ? 0.f : gN[i];
+        if (g_prevcc && i < M_before) g_prevcc[i] = 0.f;
+    }
+}
+
+__global__ __launch_bounds__(PF_T) void k_pf_fuse_normals_bwd_pixels(const long long* __restrict__ t_row, const float* __restrict__ t_c,
+                                                                     const float* __restrict__ t_N, const float* __restrict__ Ng,
+                                                                     const float* __restrict__ alpha, const float* __restrict__ gN,
+                                                                     int64_t M_before, int64_t M_after, int64_t N, int accumulate,
+                                                                     float* __restrict__ g_Ng, float* __restrict__ g_alpha,
+                                                                     float* __restrict__ g_prevN, float* __restrict__ g_prevcc) {
+    for (int64_t q = (int64_t)blockIdx.x * PF_T + threadIdx.x; q < N; q += (int64_t)gridDim.x * PF_T) {
+        const long long row = t_row[q];
+        float gn[3] = {0.f, 0.f, 0.f}, ga = 0.f;
+        if (row >= 0 && row < M_after) {
+            const float u[3] = {gN[row * 3], gN[row * 3 + 1], gN[row * 3 + 2]};
+            if (row >= M_before) {                          // appended: the row is the pixel
+#pragma unroll
+                for (int j = 0; j < 3; ++j) gn[j] = u[j];
+            } else {                                        // fused into its winner
+                const float a = alpha[q], c = t_c[q], s = c + a;
+                float D = 0.f, Df = 0.f, Dm = 0.f;
+#pragma unroll
+                for (int j = 0; j < 3; ++j) {
+                    const float v = Ng[q * 3 + j], p = t_N[q * 3 + j];
+                    D += u[j] * (v - p);
+                    Df += u[j] * v;
+                    Dm += u[j] * p;
+                }
+                float wf, wm, gprev_cc;
+                if (s == 0.f) {
+                    wf = 0.f; wm = 0.f;
+                    ga = Df;
+                    gprev_cc = Dm;
+                } else {
+                    wf = a / s; wm = c / s;
+                    ga = wm * (D / s);
+                    gprev_cc = -wf * (D / s);
+                }
+#pragma unroll
+                for (int j = 0; j < 3; ++j) {
+                    gn[j] = wf * u[j];
+                    if (g_prevN) g_prevN[row * 3 + j] = wm * u[j];
+                }
+                if (g_prevcc) g_prevcc[row] = accumulate ? g_prevcc[row] + gprev_cc : gprev_cc;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+            if (g_Ng) g_Ng[q * 3 + j] = gn[j];
+        if (g_alpha) g_alpha[q] = accumulate ? g_alpha[q] + ga : ga;
+    }
+}
+
 static inline int pfg_grid(int64_t n, int cap = 2048) {
     int64_t g = (n + PF_T - 1) / PF_T;
     return (int)(g < 1 ? 1 : (g > cap ? cap : g));
@@ -286,6 +360,46 @@ int e2e_vertex_alpha_bwd(const float* depth, const float* K, const float* alpha,
     hipLaunchKernelGGL(k_vertex_alpha_bwd, dim3(pfg_grid((int64_t)H * W), B), dim3(PF_T), 0, (hipStream_t)stream, depth, K, alpha, g_alpha,
                        alpha_den, g_depth, accumulate, H, W);
     E2E_LAUNCH_CHECK("e2e_vertex_alpha_bwd");
+    return E2E_OK;
+}
+
+int64_t e2e_pf_fuse_normals_tape_bytes(int H, int W) {
+    if (H <= 0 || W <= 0) return 0;
+    return (12 * (int64_t)H * W + 255) & ~255ll;
+}
+
+int e2e_pf_fuse_normals_tape(const void* tape, const float* map_normals, int64_t M, void* ntape, int H, int W, void* stream) {
+    E2E_REQUIRE(M >= 0 && H > 0 && W > 0 && (int64_t)H * W < (1ll << 31), E2E_ERR_ARG, "e2e_pf_fuse_normals_tape: bad sizes M=%lld",
+                (long long)M);
+    E2E_REQUIRE(tape && ntape && (M == 0 || map_normals), E2E_ERR_ARG, "e2e_pf_fuse_normals_tape: null pointer");
+    const int64_t N = (int64_t)H * W;
+    const PfTape t = pf_tape((void*)tape, N);
+    hipLaunchKernelGGL(k_pft_record_normals, dim3(pfg_grid(N)), dim3(PF_T), 0, (hipStream_t)stream, (const long long*)t.row, map_normals, M, N,
+                       (float*)ntape);
+    E2E_LAUNCH_CHECK("e2e_pf_fuse_normals_tape");
+    return E2E_OK;
+}
+
+int e2e_pf_fuse_normals_bwd(const void* tape, const void* ntape, const float* Ng, const float* alpha, const float* g_normals,
+                            const float* ccounts_after, int64_t M_before, int64_t M_after, float* g_Ng, float* g_prev_normals,
+                            float* g_alpha, float* g_prev_ccounts, int accumulate, int H, int W, void* stream) {
+    E2E_REQUIRE(M_before >= 0 && M_after >= M_before && H > 0 && W > 0 && (int64_t)H * W < (1ll << 31), E2E_ERR_ARG,
+                "e2e_pf_fuse_normals_bwd: bad sizes M_before=%lld M_after=%lld", (long long)M_before, (long long)M_after);
+    E2E_REQUIRE(tape && ntape && Ng && alpha && (g_normals || M_after == 0), E2E_ERR_ARG, "e2e_pf_fuse_normals_bwd: null pointer");
+    E2E_REQUIRE(g_Ng || g_prev_normals || g_alpha || g_prev_ccounts, E2E_ERR_ARG, "e2e_pf_fuse_normals_bwd: no output");
+    E2E_REQUIRE(ccounts_after || M_before == 0 || !g_prev_normals, E2E_ERR_ARG,
+                "e2e_pf_fuse_normals_bwd: ccounts_after is needed for the previous map's normal gradient");
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t N = (int64_t)H * W;
+    const PfTape t = pf_tape((void*)tape, N);
+    float* rows_cc = accumulate ? nullptr : g_prev_ccounts;         // under accumulate the rows that won no pixel keep what they hold
+    if (M_before > 0 && (g_prev_normals || rows_cc))
+        hipLaunchKernelGGL(k_pf_fuse_normals_bwd_rows, dim3(pfg_grid(M_before * 3, 8192)), dim3(PF_T), 0, st, g_normals, ccounts_after,
+                           (const unsigned int*)t.hdr, M_before, g_prev_normals, rows_cc);
+    hipLaunchKernelGGL(k_pf_fuse_normals_bwd_pixels, dim3(pfg_grid(N)), dim3(PF_T), 0, st, (const long long*)t.row, (const float*)t.c,
+                       (const float*)ntape, Ng, alpha, g_normals, M_before, M_after, N, accumulate != 0, g_Ng, g_alpha, g_prev_normals,
+                       g_prev_ccounts);
+    E2E_LAUNCH_CHECK("e2e_pf_fuse_normals_bwd");
     return E2E_OK;
 }
 

@@ -127,12 +127,13 @@ class FusionMap:
             self.fuse_append(maps, rgb, depth)
         return maps
 
-    def step_differentiable(self, rgb, depth, K, pose, prev=None, pose_gradient=False):
+    def step_differentiable(self, rgb, depth, K, pose, prev=None, pose_gradient=False, normal_gradient=False):
         """step() as an autograd Function (e2ehip/fusion_grad.py): -> points, normals, colors, ccounts after the step as tensors of their
         own; points / colors / ccounts carry the gradient to depth, rgb and `prev` (the previous map's tensors in the caller's graph) and,
-        with pose_gradient, to a pose that requires grad (otherwise the pose is a constant)."""
+        with pose_gradient, to a pose that requires grad (otherwise the pose is a constant).  normal_gradient: `prev` takes the previous
+        normals as a fourth tensor and the returned normals carry the gradient too (off: they have no graph)."""
         from .fusion_grad import step_differentiable
-        return step_differentiable(self, rgb, depth, K, pose, prev, pose_gradient)
+        return step_differentiable(self, rgb, depth, K, pose, prev, pose_gradient, normal_gradient)
 
     def step_resident(self, rgb, depth, K, pose):
         """The same map step without any host read or allocation: frame maps into preallocated buffers, association / fusion /

@@ -272,7 +272,7 @@ def fusion_alpha_den(sigma, eps=1e-7):
 
 class _VertexMaps(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, depth, K, pose, alpha_den, alpha_grad=False):
+    def forward(ctx, depth, K, pose, alpha_den, alpha_grad=False, normal_grad=False):
         B, H, W = depth.shape
         d = L.dev(depth, "depth").contiguous()
         K, pose = _mat(K, "intrinsics", B), _mat(pose, "poses", B)
@@ -282,15 +282,20 @@ class _VertexMaps(torch.autograd.Function):
         L.call("e2e_vertex_normal_maps", depth=L.ptr(d), K=L.ptr(K), pose=L.ptr(pose), alpha_den=float(alpha_den), V=L.ptr(V), Nm=L.ptr(Nm), Vg=L.ptr(Vg),
                Ng=L.ptr(Ng), alpha=L.ptr(alpha), B=B, H=H, W=W, stream=L.stream())
         ctx.alpha_den = float(alpha_den) if alpha_grad else None
+        ctx.normal_grad = bool(normal_grad)
         saved = (d, K, pose, alpha) if alpha_grad else (d, K, pose)
         if ctx.needs_input_grad[2]:                       # the pose is a variable (the chain gradient): its adjoint needs V
             saved = saved + (V,)
+            if normal_grad:                               # ... and Ng = R n needs n
+                saved = saved + (Nm,)
         ctx.save_for_backward(*saved)
+        fixed = () if normal_grad else (Nm, Ng)
         if alpha_grad:
-            ctx.mark_non_differentiable(Nm, Ng)
-            ctx.set_materialize_grads(False)              # a map step that only moves confidences sends no g_Vg
+            ctx.mark_non_differentiable(*fixed)
         else:
-            ctx.mark_non_differentiable(Nm, Ng, alpha)
+            ctx.mark_non_differentiable(*fixed, alpha)
+        if alpha_grad or normal_grad:
+            ctx.set_materialize_grads(False)              # a map step that only moves confidences sends no g_Vg
         return V, Nm, Vg, Ng, alpha
 
     @staticmethod
@@ -300,36 +305,53 @@ class _VertexMaps(torch.autograd.Function):
         B, H, W = d.shape
         if ctx.alpha_den is None:
             ga = None
-        if gV is None and gVg is None and ga is None:
-            return None, None, None, None, None
+        if not ctx.normal_grad:
+            gN = gNg = None
+        if gV is None and gVg is None and ga is None and gN is None and gNg is None:
+            return None, None, None, None, None, None
         gd = torch.empty_like(d)
         g_pose = None
-        if gV is not None or gVg is not None:
+        written = gV is not None or gVg is not None
+        if written:
             gV = gV.contiguous() if gV is not None else None
             gVg = gVg.contiguous() if gVg is not None else None
             L.call("e2e_vertex_maps_bwd", L.ptr(d), L.ptr(K), L.ptr(pose), L.ptr(gV), L.ptr(gVg), L.ptr(gd), B, H, W, L.stream())
+        if gN is not None or gNg is not None:
+            gN = gN.contiguous() if gN is not None else None
+            gNg = gNg.contiguous() if gNg is not None else None
         if ctx.needs_input_grad[2]:
-            # Vg = (R V + t) on the valid pixels: g_pose[b][:3] = [sum g_Vg V^T | sum g_Vg]; the normals and alpha do not see the pose
+            # Vg = (R V + t) on the valid pixels: g_pose[b][:3] = [sum g_Vg V^T | sum g_Vg]; alpha does not see the pose
             g_pose = torch.zeros(B, 4, 4, device=d.device, dtype=torch.float32)
             if gVg is not None:
-                V = ctx.saved_tensors[-1]
+                V = ctx.saved_tensors[-2 if ctx.normal_grad else -1]
                 gm = (gVg * (d != 0)[..., None]).reshape(B, H * W, 3)
                 for b in range(B):
                     g_pose[b, :3] = transform_points_bwd_T(gm[b], V[b].reshape(H * W, 3)).float()
+            if gNg is not None:
+                # Ng = R n: g_pose[b][:3,:3] += sum g_Ng n^T (n is 0 on the invalid pixels); the fourth column of that call is no gradient
+                Nm = ctx.saved_tensors[-1]
+                for b in range(B):
+                    g_pose[b, :3, :3] += transform_points_bwd_T(gNg[b].reshape(H * W, 3), Nm[b].reshape(H * W, 3))[:, :3].float()
         if ga is not None:
             L.call("e2e_vertex_alpha_bwd", depth=L.ptr(d), K=L.ptr(K), alpha=L.ptr(ctx.saved_tensors[3]), g_alpha=L.ptr(ga.contiguous()),
-                   alpha_den=ctx.alpha_den, g_depth=L.ptr(gd), accumulate=int(gV is not None or gVg is not None), B=B, H=H, W=W, stream=L.stream())
-        return gd, None, g_pose, None, None
+                   alpha_den=ctx.alpha_den, g_depth=L.ptr(gd), accumulate=int(written), B=B, H=H, W=W, stream=L.stream())
+            written = True
+        if gN is not None or gNg is not None:
+            L.call("e2e_normal_maps_bwd", depth=L.ptr(d), K=L.ptr(K), pose=L.ptr(pose), g_Nm=L.ptr(gN), g_Ng=L.ptr(gNg), g_depth=L.ptr(gd),
+                   accumulate=int(written), B=B, H=H, W=W, stream=L.stream())
+        return gd, None, g_pose, None, None, None
 
 
-def vertex_normal_maps(depth, K, pose, sigma=0.6, alpha_grad=False):
+def vertex_normal_maps(depth, K, pose, sigma=0.6, alpha_grad=False, normal_grad=False):
     """depth (B,H,W), K/pose (B,4,4) -> dict V, n, Vg, ng (B,H,W,3), alpha (B,H,W), valid (B,H,W) bool.
     gradslam RGBDImages maps; differentiable wrt depth through V and Vg, and -- with alpha_grad=True only --
     through the fusion confidence alpha (e2e_vertex_alpha_bwd).  A pose that requires grad gets its gradient through Vg
-    (e2e_transform_points_bwd_t per batch item; bottom row 0).  The normals are not differentiated."""
+    (e2e_transform_points_bwd_t per batch item; bottom row 0).  The normals are differentiated with normal_grad=True only: n and ng
+    then carry the gradient to the depth (e2e_normal_maps_bwd, into the same g_depth) and ng to the rotation of such a pose; off,
+    they are constants and the values are the same bits."""
     if depth.dim() != 3:
         raise ValueError(f"depth: expected (B,H,W), got {tuple(depth.shape)}")
-    V, Nm, Vg, Ng, alpha = _VertexMaps.apply(depth, K, pose, fusion_alpha_den(sigma), bool(alpha_grad))
+    V, Nm, Vg, Ng, alpha = _VertexMaps.apply(depth, K, pose, fusion_alpha_den(sigma), bool(alpha_grad), bool(normal_grad))
     return {"V": V, "n": Nm, "Vg": Vg, "ng": Ng, "alpha": alpha, "valid": depth.detach() != 0}
 
 

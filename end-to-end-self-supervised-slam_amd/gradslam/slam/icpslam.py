@@ -20,6 +20,7 @@ class ICPSLAM(nn.Module):
         self.device = torch.device(device) if device is not None else torch.device("cpu")
         self.pose_gradient = True         # False: localise on the detached depth (the pose is a constant of the step)
         self.chain_gradient = False       # True (PointFusion): the map and the previous pose are variables of the localisation too
+        self.normal_gradient = False      # True (PointFusion): the map's normals carry a gradient to the depths that built them
 
     # -- odometry ------------------------------------------------------------------------------------
     def _localize(self, pointclouds, live_frame, prev_frame):

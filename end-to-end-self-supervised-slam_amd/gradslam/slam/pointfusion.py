@@ -4,15 +4,18 @@ from ..structures import Pointclouds
 from .icpslam import ICPSLAM
 
 
-def frame_as_pointcloud(frame, alpha_grad=False, pose_grad=False):
+def frame_as_pointcloud(frame, alpha_grad=False, pose_grad=False, normal_grad=False):
     """All valid-depth pixels of a 1-frame RGBDImages as a Pointclouds (row-major order), differentiable wrt
     depth through the global vertex map (alpha_grad: and through the confidences in features_list; pose_grad: and wrt a pose that
-    requires grad).  This is what PointFusion.step returns for an EMPTY map (online_adaption.py:461-469) and what ICPSLAM's
+    requires grad; normal_grad: the normals are attached too).  This is what PointFusion.step returns for an EMPTY map (online_adaption.py:461-469) and what ICPSLAM's
     aggregation appends."""
     B, L, H, W = frame.shape
     if L != 1:
         raise ValueError(f"Expected a frame with sequence length 1. Got {L}.")
-    m = frame._maps(alpha_grad=alpha_grad, pose_grad=pose_grad) if alpha_grad or pose_grad else frame._maps()
+    if alpha_grad or pose_grad or normal_grad:
+        m = frame._maps(alpha_grad=alpha_grad, pose_grad=pose_grad, normal_grad=normal_grad)
+    else:
+        m = frame._maps()
     pts, nrm, col, feat = [], [], [], []
     for b in range(B):
         keep = m["valid"][b, 0, ..., 0] if m["valid"].dim() == 5 else m["valid"][b, 0]
@@ -39,10 +42,17 @@ class PointFusion(ICPSLAM):
     chain_gradient (default False): the two halves are one graph, as in the reference (train_depth.py:360-397).  The localisation takes
     the map (the incoming cloud's points and normals lists) and the previous frame's pose as variables, and the map step takes the live
     pose as one (the association still sees a constant), so a pose carries the gradient to the depth of every earlier frame through
-    whatever graph map_gradient gave the map, and the fused cloud moves with the estimated poses.  Values do not change."""
+    whatever graph map_gradient gave the map, and the fused cloud moves with the estimated poses.  Values do not change.
+
+    normal_gradient (default False): the normals of the returned cloud carry a gradient as well: to the live depth through the
+    finite-difference normal map (e2e_normal_maps_bwd) and, in a differentiable map step, through the confidence-weighted fusion to the
+    incoming cloud's normals and confidences (e2e_pf_fuse_normals_bwd).  Something has to read that graph: with chain_gradient the
+    point-to-plane residual of every later localisation does; with map_gradient as well it reaches the fused rows, otherwise only the
+    rows of the first frame.  Values do not change."""
 
     def __init__(self, *, odom="gradicp", dist_th=0.05, angle_th=20, sigma=0.6, dsratio=4, numiters=20, damp=1e-8, dist_thresh=None,
-                 lambda_max=2.0, B=1.0, B2=1.0, nu=200.0, device=None, map_capacity=None, map_gradient=False, chain_gradient=False):
+                 lambda_max=2.0, B=1.0, B2=1.0, nu=200.0, device=None, map_capacity=None, map_gradient=False, chain_gradient=False,
+                 normal_gradient=False):
         super().__init__(odom=odom, dsratio=dsratio, numiters=numiters, damp=damp, dist_thresh=dist_thresh, lambda_max=lambda_max,
                          B=B, B2=B2, nu=nu, device=device)
         self.chain_gradient = bool(chain_gradient)
@@ -57,25 +67,30 @@ class PointFusion(ICPSLAM):
         self.dist_th, self.angle_th, self.sigma = dist_th, angle_th, sigma
         self.map_capacity = map_capacity
         self.map_gradient = bool(map_gradient)
+        self.normal_gradient = bool(normal_gradient)
 
     def _map(self, pointclouds, live_frame, inplace=False):
         if len(pointclouds) > 1 or live_frame.shape[0] != 1:
             raise NotImplementedError("batch size 1 only (OPTIMIZATION.batch_size, configs/config.yaml:60)")
         _, _, H, W = live_frame.shape
         rgb, depth = live_frame.rgb_image[0, 0], live_frame.depth_image[0, 0, ..., 0]
-        lists = [l[0] for l in (pointclouds.points_list, pointclouds.colors_list, pointclouds.features_list) if l]
+        normals = self.normal_gradient and torch.is_grad_enabled()
+        lists = [l[0] for l in (pointclouds.points_list, pointclouds.colors_list, pointclouds.features_list) +
+                 ((pointclouds.normals_list,) if normals else ()) if l]
         chain = self.chain_gradient and torch.is_grad_enabled() and live_frame.poses.requires_grad       # the live pose is a variable
         with_graph = self.map_gradient and torch.is_grad_enabled() and (chain or any(t.requires_grad for t in [depth, rgb] + lists))
         if not pointclouds.has_points:
             # empty map: nothing to associate with -> the frame's valid pixels, still attached to the autograd
             # graph of the depth (the 3-D loss differentiates through this: online_adaption.py:461-469,638-645)
-            out = frame_as_pointcloud(live_frame, alpha_grad=with_graph, pose_grad=chain)
+            attach = {"normal_grad": True} if normals and (chain or depth.requires_grad) else {}
+            out = frame_as_pointcloud(live_frame, alpha_grad=with_graph, pose_grad=chain, **attach)
             return out
         fm = self._resident_map(pointclouds, live_frame)      # adopts an externally built cloud once
         if with_graph:
             P, Nn, C, cc = fm.step_differentiable(rgb, depth, live_frame.intrinsics[0, 0], live_frame.poses[0, 0],
-                                                  prev=(pointclouds.points_list[0], pointclouds.colors_list[0], pointclouds.features_list[0]),
-                                                  pose_gradient=chain)
+                                                  prev=(pointclouds.points_list[0], pointclouds.colors_list[0], pointclouds.features_list[0]) +
+                                                       ((pointclouds.normals_list[0],) if normals else ()),
+                                                  pose_gradient=chain, **({"normal_gradient": True} if normals else {}))
             out = Pointclouds([P], [Nn], [C], [cc.reshape(-1, 1)], device=live_frame.device)
             out._fusion_maps = fm
             return out

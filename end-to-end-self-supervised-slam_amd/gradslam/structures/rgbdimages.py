@@ -87,19 +87,21 @@ class RGBDImages:
         return self._poses is not None
 
     # ---- maps --------------------------------------------------------------------------------------
-    def _maps(self, alpha_grad=False, pose_grad=False):
+    def _maps(self, alpha_grad=False, pose_grad=False, normal_grad=False):
         """alpha_grad: the fusion confidence carries a gradient to the depth as well (PointFusion(map_gradient=True)); pose_grad: the
         global vertex map carries a gradient to poses that require one (PointFusion(chain_gradient=True); otherwise the poses are
-        constants).  Either way the same values, computed apart from the cache."""
-        if self._cache is None or alpha_grad or pose_grad:
+        constants); normal_grad: the normal maps carry a gradient to the depth, and the global one to such poses
+        (PointFusion(normal_gradient=True)).  Either way the same values, computed apart from the cache."""
+        if self._cache is None or alpha_grad or pose_grad or normal_grad:
             B, L, H, W = self.shape
             K = self._K.expand(B, L, 4, 4).reshape(B * L, 4, 4)
             poses = self._poses if self._poses is not None else torch.eye(4, device=self.device).expand(B, L, 4, 4)
             if not pose_grad:
                 poses = poses.detach()
-            m = ops.vertex_normal_maps(self._depth.reshape(B * L, H, W), K, poses.reshape(B * L, 4, 4), alpha_grad=alpha_grad)
+            m = ops.vertex_normal_maps(self._depth.reshape(B * L, H, W), K, poses.reshape(B * L, 4, 4), alpha_grad=alpha_grad,
+                                       normal_grad=normal_grad)
             m = {k: (v.reshape((B, L) + tuple(v.shape[1:])) if v.dim() == 4 else v.reshape(B, L, H, W, 1)) for k, v in m.items()}
-            if alpha_grad or pose_grad:
+            if alpha_grad or pose_grad or normal_grad:
                 return m
             self._cache = m
         return self._cache

@@ -71,6 +71,11 @@ class Depth_Estimation:
         # estimated pose.  E2E_CHAIN_GRAD=1 (or chain_gradient = True) makes the map and the previous pose variables of the localisation
         # and the pose a variable of the map step; default off: they are constants.  Composes with the two switches above.
         self.chain_gradient = os.environ.get("E2E_CHAIN_GRAD", "0") == "1"
+        # In that one graph every map normal is a function of three depths, is fused with the confidences and is read by the point-to-plane
+        # residual of every later localisation.  E2E_NORMAL_GRAD=1 (or normal_gradient = True) lets the normals carry that gradient to the
+        # depth; default off: they are constants.  It has an effect where something reads the normals' graph, which is the chain gradient
+        # (with E2E_MAP_GRAD=1 as well it reaches the fused rows too).
+        self.normal_gradient = os.environ.get("E2E_NORMAL_GRAD", "0") == "1"
         self.dataset_init()
         self.model_init()
         self.view_reconstruction_init()
@@ -236,6 +241,7 @@ class Depth_Estimation:
                     self.models["SLAM"].pose_gradient = self.pose_gradient
                     self.models["SLAM"].map_gradient = self.map_gradient
                     self.models["SLAM"].chain_gradient = self.chain_gradient
+                    self.models["SLAM"].normal_gradient = self.normal_gradient
                     noisy_reconstruction, new_poses = self.models["SLAM"](noisy_rgbd)
                     new_transform = torch_poses_to_transforms(new_poses)
                 if noisy_reconstruction is not None:

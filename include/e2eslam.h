@@ -389,6 +389,55 @@ int e2e_pf_fuse_bwd(const void* tape, const float* Vg, const float* rgb, const f
 int e2e_vertex_alpha_bwd(const float* depth, const float* K, const float* alpha, const float* g_alpha, float alpha_den,
                          float* g_depth, int accumulate, int B, int H, int W, void* stream);
 
+/* THE NORMALS' GRADIENT (opt-in: gradslam.slam.PointFusion(normal_gradient=True), E2E_NORMAL_GRAD=1 for train_depth.py).  In the
+ * reference's single graph every normal is a finite-difference function of three depths, is fused with the confidence weights and is
+ * read by the point-to-plane residual of every later localisation (e2e_icp_normal_equations_bwd_tgt returns g_tgt_normals).  The three
+ * entry points below carry that gradient to the depth; the blocks above keep their rule ("the normals are not differentiated") for the
+ * entry points they declare.
+ *
+ * e2e_normal_maps_bwd: d/d(depth) of sum(g_Nm . Nm) + sum(g_Ng . Ng), the adjoint of e2e_vertex_normal_maps's own normal expressions.
+ *   depth (B,H,W); K, pose (B,4,4); g_Nm, g_Ng (B,H,W,3) channels-last, either may be NULL, both NULL is refused; g_depth (B,H,W).
+ *   accumulate = 1 adds to g_depth (after e2e_vertex_maps_bwd or e2e_vertex_alpha_bwd on the same buffer), 0 overwrites it.
+ *   Rule.  CONSTANTS: the validity mask vf = (depth != 0), the pose, the intrinsics.  Per pixel p = (h,w): r_p = (kx w + kxc, ky h + kyc, 1),
+ *   V_p = r_p d_p vf_p; dh_p = V_{h,w+1} - V_p (the constant 0 in the last column), dv_p = V_{h+1,w} - V_p (the constant 0 in the last
+ *   row); c = dh x dv, nrm = |c|, n = (c / where(nrm == 0, 1, nrm)) vf_p, Ng = R n.  Adjoint:
+ *     gn = (g_Nm[p] + R^T g_Ng[p]) vf_p
+ *     gc = (gn - nh (nh . gn)) / nrm with nh = c / nrm where nrm != 0;  gc = gn where nrm == 0: the forward's divisor is the constant 1
+ *          there (the where is taken on the norm, nothing is divided by 0), so the result is finite, never NaN
+ *     g_dh = dv x gc,  g_dv = gc x dh
+ *     p sends -(g_dh + g_dv) to V_p, g_dh to V_{h,w+1} when w+1 < W, g_dv to V_{h+1,w} when h+1 < H (a difference held at the constant
+ *     0 sends nothing);  g_depth[j] = vf_j r_j . gV_j.
+ *   A gather: the thread of pixel j collects its three contributors (j itself, (h,w-1) as a right neighbour, (h-1,w) as a lower
+ *   neighbour) and recomputes their cross-product adjoints from seven depths and three gn.  No atomics; the result does not depend on
+ *   the grid; bitwise reproducible.  Invalid pixels get exactly 0 (accumulate: keep their prior value).  The per-pixel arithmetic is
+ *   float64, rounded once on the store (1 / nrm and V_{p+1} - V_p cancel digits in float32); the inverse intrinsics are the float32
+ *   ones of the forward, widened.
+ *   With a pose that requires grad, Ng = R n also gives g_pose[:3,:3] += sum_p g_Ng[p] n_p^T: e2e_transform_points_bwd_t(g = g_Ng,
+ *   points = Nm), left 3x3 block only (the fourth column of that call is no gradient of anything here and is discarded).
+ *
+ * The normals' side of the map step.  The forward is N' = (c N + a Ng[q]) / s, s = c + a, NOT renormalised; constants as for the
+ * DIFFERENTIABLE MAP STEP above.  The adjoint is the points' rule with N for P (gN: the gradient of the step's output normals):
+ *   appended:  g_Ng[q] = gN[r]
+ *   fused:     g_Ng[q] = (a/s) gN[n]     g_alpha[q] += gN[n].(Ng[q] - N') / s     g_prevN[n] = (c/s) gN[n]     g_prevcc[n] += gN[n].(N - N') / s
+ *              (s == 0, where the forward divides by 1: g_alpha[q] += gN[n].Ng[q], g_prevcc[n] += gN[n].N, the other two are 0)
+ *   a map row that won no pixel passes gN through and gets nothing for its confidence, except that a zero-confidence row in a step where
+ *   anything matched gets 0, as for the points;  invalid pixels and rows dropped beyond the capacity get 0.
+ * e2e_pf_fuse_normals_tape runs AFTER e2e_pf_fuse_tape and BEFORE e2e_pf_fuse_append: for every fused pixel (the winner's row number is
+ *   already in `tape`) it records the winner's normal before the step, 0 for every other pixel.  ntape:
+ *   e2e_pf_fuse_normals_tape_bytes(H, W) bytes, O(H*W) whatever the size of the map.  M: the live rows before the step.
+ * e2e_pf_fuse_normals_bwd: both tapes, the frame's Ng (H,W,3) and alpha (H,W), g_normals (M_after,3), ccounts_after (as for
+ *   e2e_pf_fuse_bwd; needed when g_prev_normals is wanted and M_before > 0)  ->  g_Ng (H,W,3), g_prev_normals (M_before,3), and the
+ *   normals' contributions to g_alpha (H,W) and g_prev_ccounts (M_before).  One accumulate flag covers those two: 1 adds to what
+ *   e2e_pf_fuse_bwd wrote into them, 0 overwrites.  Every output may be NULL (not wanted), not all of them.  One streaming pass over
+ *   the M_before rows (skipped when it has nothing to write), then one pass over the pixels.  No atomics. */
+int e2e_normal_maps_bwd(const float* depth, const float* K, const float* pose, const float* g_Nm, const float* g_Ng,
+                        float* g_depth, int accumulate, int B, int H, int W, void* stream);
+int64_t e2e_pf_fuse_normals_tape_bytes(int H, int W);
+int e2e_pf_fuse_normals_tape(const void* tape, const float* map_normals, int64_t M, void* ntape, int H, int W, void* stream);
+int e2e_pf_fuse_normals_bwd(const void* tape, const void* ntape, const float* Ng, const float* alpha, const float* g_normals,
+                            const float* ccounts_after, int64_t M_before, int64_t M_after, float* g_Ng, float* g_prev_normals,
+                            float* g_alpha, float* g_prev_ccounts, int accumulate, int H, int W, void* stream);
+
 /* ------------------------------------------------------------------------------------------ */
 /* chamferdist.knn_points, K = 1, D = 3 (loss/losses.py:3,57)                                   */
 /* ------------------------------------------------------------------------------------------ */

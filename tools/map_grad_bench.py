@@ -2,7 +2,11 @@
 """Time of one PointFusion map step at camera resolution against a large map: FusionMap.step, FusionMap.step_differentiable (forward:
 the same kernels + the tape + the copy-out of the live rows) and its backward (e2e_pf_fuse_bwd + the vertex / alpha backward).
 
-    python tools/map_grad_bench.py [--height 480 --width 640 --frames 5 --reps 20 --warmup 5]
+    python tools/map_grad_bench.py [--height 480 --width 640 --frames 5 --reps 20 --warmup 5] [--normals]
+
+--normals adds a leg with the normals' gradient (step_differentiable(normal_gradient=True): the normals tape in the forward,
+e2e_pf_fuse_normals_bwd and e2e_normal_maps_bwd in the backward, an upstream gradient on the normals as well) and times
+e2e_normal_maps_bwd alone.
 
 The map: `frames - 1` views of the synthetic scene from cameras turned so that no two overlap (every pixel appended: about
 (frames - 1) x H x W rows), plus the first view again from the front; the timed step then fuses a slightly moved front view into it.
@@ -36,6 +40,7 @@ def main():
     ap.add_argument("--frames", type=int, default=5)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--normals", action="store_true", help="also time the step with the normals' gradient, and e2e_normal_maps_bwd alone")
     a = ap.parse_args()
     from e2ehip.fusionmap import FusionMap
     from e2ehip.synthetic import make_sequence
@@ -82,7 +87,34 @@ def main():
         assert d.grad is not None and c.grad is not None and all(t.grad is not None for t in prev)
         return fm.M
 
+    def differentiable_normals(ev):
+        d = d1.clone().requires_grad_(True)
+        c = rgb1.clone().requires_grad_(True)
+        prev = tuple(t.clone().requires_grad_(True) for t in (base[0], base[2], base[3], base[1]))
+        ev[0].record()
+        P, N, C, cc = fm.step_differentiable(c, d, K, p1, prev=prev, normal_gradient=True)
+        ev[1].record()
+        if "N" not in up:
+            up.update(N=torch.randn_like(N))
+        torch.autograd.backward([P, C, cc, N], [up["P"], up["C"], up["cc"], up["N"]])
+        ev[2].record()
+        assert d.grad is not None and c.grad is not None and all(t.grad is not None for t in prev)
+        return fm.M
+
+    def normal_maps_bwd_alone(ev):
+        from e2ehip import _lib as L
+        if "gd" not in up:
+            up.update(gd=torch.empty(H, W, device=dev), gn=torch.randn(H, W, 3, device=dev), gg=torch.randn(H, W, 3, device=dev),
+                      K1=K.contiguous(), P1=p1.contiguous())
+        ev[0].record()
+        L.call("e2e_normal_maps_bwd", depth=L.ptr(d1), K=L.ptr(up["K1"]), pose=L.ptr(up["P1"]), g_Nm=L.ptr(up["gn"]), g_Ng=L.ptr(up["gg"]),
+               g_depth=L.ptr(up["gd"]), accumulate=0, B=1, H=H, W=W, stream=L.stream())
+        ev[1].record()
+        ev[2].record()
+
     res = {"plain": [], "diff_fwd": [], "diff_bwd": []}
+    if a.normals:
+        res.update(normals_fwd=[], normals_bwd=[], normal_maps_bwd=[])
     for i in range(a.warmup + a.reps):
         restore()
         t_plain, _, m_plain = timed(plain)
@@ -90,6 +122,15 @@ def main():
         restore()
         t_fwd, t_bwd, m_diff = timed(differentiable)
         assert m_plain == m_diff
+        if a.normals:
+            restore()
+            t_nf, t_nb, m_n = timed(differentiable_normals)
+            assert m_n == m_plain
+            t_k, _, _ = timed(normal_maps_bwd_alone)
+            if i >= a.warmup:
+                res["normals_fwd"].append(t_nf)
+                res["normals_bwd"].append(t_nb)
+                res["normal_maps_bwd"].append(t_k)
         if i >= a.warmup:
             res["plain"].append(t_plain)
             res["diff_fwd"].append(t_fwd)
