@@ -51,6 +51,9 @@ const char* e2e_last_error(void);
 /* ------------------------------------------------------------------------------------------ */
 /* View synthesis -- depth_estimation/view_synthesis.py                                         */
 /* ------------------------------------------------------------------------------------------ */
+/* Every entry point of this section, of the photometric loss and of the fused refinement step that takes an image size as (B,H,W) needs
+ * H >= 2 and W >= 2 (the grid is normalised by dividing by W-1 and H-1, and the 1-pixel reflection pad needs a second pixel): an axis of
+ * length 1 is refused with E2E_ERR_ARG.  e2e_grid_sample_* take (Hi,Wi) and (Ho,Wo) instead and accept any positive sizes. */
 
 /* BackprojectDepth.forward (view_synthesis.py:34-40): depth (B,H*W), inv_K (B,4,4)
  * -> cam_points (B,4,H*W) rows x,y,z,1. */

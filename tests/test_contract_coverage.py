@@ -1,6 +1,6 @@
 """Host-only: every entry point that include/e2eslam.h declares and csrc/depth_ops.hip, aux_losses.hip or nn_misc.hip implements is
 called by one of the two contract modules (tests/test_gpu_depth_aux_contracts.py, tests/test_gpu_nn_misc_contracts.py); the same for
-csrc/icp.hip and tests/test_gpu_icp_contracts.py."""
+csrc/icp.hip and tests/test_gpu_icp_contracts.py, and for csrc/warp_photo.hip and tests/test_gpu_warp_photo_contracts.py."""
 import os
 import re
 
@@ -36,4 +36,16 @@ def test_every_entry_point_of_the_icp_file_has_a_contract_case():
     assert implemented <= declared, sorted(implemented - declared)
     assert "e2e_pf_active_subsample_dev" in declared
     called = set(re.findall(r"[\"'.](e2e_\w+)[\"'(]", _read(ROOT, "tests", "test_gpu_icp_contracts.py")))
+    assert not names - called, f"no contract case calls {sorted(names - called)}"
+
+
+def test_every_entry_point_of_the_warp_photo_file_has_a_contract_case():
+    """csrc/warp_photo.hip's entry points (view synthesis, photometric loss, the fused pair and its workspace query) are all called by
+    tests/test_gpu_warp_photo_contracts.py."""
+    declared = set(re.findall(r"^(?:int|int64_t|long long)\s+(e2e_\w+)\s*\(", _read(ROOT, "include", "e2eslam.h"), re.M))
+    implemented = set(re.findall(r"^(?:int|int64_t|long long)\s+(e2e_\w+)\s*\(", _read(CSRC, "warp_photo.hip"), re.M))
+    names = declared & implemented
+    assert len(names) >= 12, sorted(names)                                # 12 at the time of writing: the greps still find them
+    assert implemented <= declared, sorted(implemented - declared)
+    called = set(re.findall(r"[\"'.](e2e_\w+)[\"'(]", _read(ROOT, "tests", "test_gpu_warp_photo_contracts.py")))
     assert not names - called, f"no contract case calls {sorted(names - called)}"
