@@ -47,7 +47,7 @@ class direct_weight_grads:
     slices of the optimiser's flat gradient bucket and autograd gets no gradient for them (one AccumulateGrad add kernel less per
     parameter and step: 48 at 5 us).  The switch is a field of THAT optimiser's FlatParams -- another model's backward running
     meanwhile is not affected -- and it is off outside the block: torch.autograd.grad() callers get their gradients returned.
-    An optimiser without a flat bucket (torch's own, or FusedAdam before its first step): a no-op.
+    An optimiser without a flat bucket (torch's own, or a fused one before its first step): a no-op.
     overlap=True additionally moves every backward-weight chain (GEMM + slab folds + reduce) to the FlatParams' side stream: it
     depends only on dZ, like the backward-data GEMM next to it.  The exit joins the streams."""
 
@@ -197,7 +197,7 @@ def supports(weight):
 
 
 def _grad_out(param, shape):
-    """(buffer, accumulate): the parameter's slice of FusedAdam's flat gradient buffer inside direct_weight_grads(),
+    """(buffer, accumulate): the parameter's slice of the fused optimiser's flat gradient buffer inside direct_weight_grads(),
     else a fresh tensor that is returned to autograd."""
     s = _sink(param, shape)
     return (s, 1) if s is not None else (torch.empty(shape, device=param.device, dtype=torch.float32), 0)

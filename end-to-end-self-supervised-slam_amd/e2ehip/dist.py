@@ -1,7 +1,7 @@
 """One process per GPU over torch.distributed (backend "nccl" = RCCL over xGMI on ROCm; "gloo" in the CPU tests).
 
 The path shards by SEQUENCE: every rank refines its own keyframe pairs against its own global map; the only
-exchange per refinement step is the depth network's gradient, which FusedAdam keeps as ONE contiguous fp32
+exchange per refinement step is the depth network's gradient, which the fused optimiser (e2ehip.optim) keeps as ONE contiguous fp32
 bucket (14 319 409 trainable elements = 57.3 MB, plus a tail element that counts the participating ranks), so the step
 is ONE logical all-reduce with no flatten copies -- issued in two segments (exchange_gradients_late_ / _early_) so that 80 % of
 it overlaps the second half of the backward pass.
@@ -65,10 +65,10 @@ def broadcast_parameters_(flat, src=0):
 
 def exchange_gradients_(flat, participating=True):
     """The ONE collective of a refinement step (between loss.backward() and optimizer.step(), online_adaption.py:539-540):
-    all-reduce(SUM) of FusedAdam's flat gradient bucket.  Keyframe decisions are data dependent (online_adaption.py:234), so a
+    all-reduce(SUM) of the fused optimiser's flat gradient bucket.  Keyframe decisions are data dependent (online_adaption.py:234), so a
     rank without a keyframe joins with a zero bucket; the number of contributing ranks rides in the bucket's tail element
-    (`flat.grad_ext` = gradients + one 16-byte tail), so it is summed by the SAME all-reduce, and FusedAdam divides by it
-    inside the Adam kernel (e2e_adam_step_mean) -- no second collective, no separate division pass.
+    (`flat.grad_ext` = gradients + one 16-byte tail), so it is summed by the SAME all-reduce, and the optimiser divides by it
+    inside its kernel (e2e_*_step_resident) -- no second collective, no separate division pass.
     `flat`: e2ehip.optim.FlatParams.  world size 1: nothing to do (participants stays 1)."""
     if not participating:
         flat.grad_ext.zero_()

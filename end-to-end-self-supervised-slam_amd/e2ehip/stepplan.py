@@ -224,6 +224,9 @@ class RefineStepPlan:
         (the caller's promise: SLAM.refinement keeps track) -- see _forward_new_target.  both_forwards_are_current: both slots do
         (update_map(prefetch=True) ran the new target next to the map step) -- see _scale_only."""
         use_3d = knn_index is not None
+        # learning rate (and, for Adam, betas) as the optimiser's group holds them NOW, written to the device scalars the captured
+        # optimiser launch reads: a scheduler stepped since the capture takes effect in the replay (no recapture; a no-op without a change)
+        self.opt.sync_hyperparameters()
         if both_forwards_are_current:
             self._run("scale_only", self._scale_only)
         elif source_forward_is_current:
@@ -266,6 +269,7 @@ class RefineStepPlan:
 
     def idle_step(self):
         """A step of a rank without a keyframe in this round (data-parallel runs): zero bucket in, averaged update out."""
+        self.opt.sync_hyperparameters()
         if self._split is None:
             self._split = self.net.split_offset(self.opt.flat)
         handle = edist.exchange_gradients_late_(self.opt.flat, self._split, False)      # the same two collectives as a participating rank

@@ -7,8 +7,8 @@ MI355X way:
   * warp + mask + SSIM/L1 + depth regulariser, forward AND backward, are ONE launch (e2e_warp_photo_lossgrad)
     whose d(loss)/d(depth) is injected into the network's backward -- synth / valid / loss map never reach HBM;
   * the 3-D loss is unproject -> rigid transform -> exact nearest neighbour (HIP kernels) on the resident map;
-  * Adam is one fused launch over one flat parameter bucket, which is also the single RCCL all-reduce bucket when
-    several GPUs refine several sequences (one sequence per rank);
+  * the optimiser (OPTIMIZATION.optimizer: Adam, SGD, RMSprop or Adagrad) is one fused launch over one flat parameter bucket,
+    which is also the single RCCL all-reduce bucket when several GPUs refine several sequences (one sequence per rank);
   * a whole refinement step is a static launch plan over resident buffers, replayed from captured hipGraphs
     (e2ehip.stepplan / e2ehip.netplan): no autograd graph, no allocator traffic, no host synchronisation in a step;
     `refinement_autograd` keeps the torch.autograd form of the same step (same kernels) for the off-by-default loss
@@ -323,7 +323,7 @@ class SLAM:
             self._before_plan_step(sp)
             sp.step(refine_step == 0, index, source_forward_is_current=held == (None, prev), both_forwards_are_current=held == (prev, cur))
             self._after_plan_step(sp)
-            self._forward_holds = None              # Adam stepped
+            self._forward_holds = None              # the optimiser stepped
             self.refinement_steps_done += 1
             if a.DEBUG.print_metrics:
                 lp, lr, l3 = sp.losses()
@@ -414,7 +414,7 @@ class SLAM:
                 l3 = self.compute_3d_loss(d_tgt, K, poses[:, 1], T)
                 roots.append(l3 * a.LOSS.three3d_loss_weight)
                 grads.append(None)
-            with e2e_conv.direct_weight_grads(self.optimizer, overlap=self.overlap_wgrad_autograd):     # weight gradients accumulate straight into FusedAdam's flat bucket
+            with e2e_conv.direct_weight_grads(self.optimizer, overlap=self.overlap_wgrad_autograd):     # weight gradients accumulate straight into the fused optimiser's flat bucket
                 torch.autograd.backward(roots, grads)
             self._exchange_gradients()
             self.optimizer.step()

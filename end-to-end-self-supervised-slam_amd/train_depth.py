@@ -151,7 +151,7 @@ class Depth_Estimation:
 
     def load_optimizer(self):
         """Resume the optimiser from `<MODEL.load_depth_path>/<OPTIMIZATION.optimizer>.pth` when that file exists (train_depth.py:849-863;
-        torch.optim.Adam's state-dict format, which e2ehip.optim.FusedAdam reads and writes)."""
+        the state-dict format of torch's optimiser of that name, which the fused optimisers of e2ehip.optim read and write)."""
         path = os.path.join(os.path.expanduser(str(self.args.MODEL.load_depth_path)), "{}.pth".format(self.args.OPTIMIZATION.optimizer))
         if os.path.isfile(path):
             print("Loading Optimizer Weights")

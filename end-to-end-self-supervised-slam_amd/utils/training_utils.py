@@ -1,24 +1,29 @@
 """Drop-in for utils/training_utils.py (reference: utils/training_utils.py:11-216): optimiser / scheduler
 factories and the 4x4 pose helpers.  The 4x4 algebra stays in torch on whatever device the poses live on
-(host-side 4x4 math); the Adam option returns the fused multi-tensor HIP optimiser when the
-parameters live on the GPU."""
+(host-side 4x4 math); Adam, SGD, RMSprop and Adagrad return the fused multi-tensor HIP optimiser
+of that name (e2ehip.optim) when the parameters live on the GPU."""
 import torch
 
 
 def define_optim(args, parameters):
+    """The reference's five names with the reference's settings.  GPU parameters: the fused optimiser over one flat bucket, which is what
+    the online driver's step plan, its captured graphs and the data-parallel exchange run on; CPU parameters: torch's own.  SparseAdam
+    is torch's on either device: torch itself rejects it on the dense gradients every parameter here receives."""
     name, lr = args.OPTIMIZATION.optimizer, args.OPTIMIZATION.learning_rate
     parameters = list(parameters)
+    fused = bool(parameters) and parameters[0].is_cuda
+    if fused:
+        from e2ehip.optim import FusedAdagrad, FusedAdam, FusedRMSprop, FusedSGD
     if name == "Adam":
-        from e2ehip.optim import FusedAdam
-        opt = FusedAdam(parameters, lr=lr) if parameters and parameters[0].is_cuda else torch.optim.Adam(parameters, lr=lr)
+        opt = FusedAdam(parameters, lr=lr) if fused else torch.optim.Adam(parameters, lr=lr)
     elif name == "SparseAdam":
         opt = torch.optim.SparseAdam(parameters, lr=lr)
     elif name == "SGD":
-        opt = torch.optim.SGD(parameters, lr=lr, momentum=0.9, weight_decay=1e-3)
+        opt = (FusedSGD if fused else torch.optim.SGD)(parameters, lr=lr, momentum=0.9, weight_decay=1e-3)
     elif name == "RMSprop":
-        opt = torch.optim.RMSprop(parameters, lr=lr)
+        opt = (FusedRMSprop if fused else torch.optim.RMSprop)(parameters, lr=lr)
     elif name == "Adagrad":
-        opt = torch.optim.Adagrad(parameters, lr=lr)
+        opt = (FusedAdagrad if fused else torch.optim.Adagrad)(parameters, lr=lr)
     else:
         raise ValueError("Define an optimizer")
     print("{} Optimizer Defined with initial LR = {}".format(name, lr))

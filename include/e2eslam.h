@@ -583,6 +583,25 @@ int e2e_adam_step_resident(float* params, const float* grad_sums, const float* p
                            float* exp_avg_sq, int64_t n, float beta1, float beta2, float eps,
                            const float* schedule, int schedule_len, int* step_counter, void* stream);
 
+/* The other optimisers of define_optim (training_utils.py:26-47) over the same flat bucket, hipGraph-safe like the resident Adam
+ * form: one flat, 16-byte-aligned fp32 buffer per array, g = grad_sums / max(participants[0], 1) (participants: device scalar or
+ * NULL = 1), the learning rate READ FROM DEVICE MEMORY (`lr`, one float: a replayed launch sees a rate rewritten in place), and a
+ * device step counter that a second one-thread kernel advances by exactly 1 behind the update (the update does not read it).  The
+ * other hyper-parameters are doubles, rounded to fp32 once on the host as torch rounds the python scalars of its own updates.  No
+ * atomics: equal inputs give equal bits.  g == 0 on a zero state leaves the parameter as it is (the padding between bucket slices).
+ *   SGD (dampening 0, no nesterov):       d = g + weight_decay * p;  buf = momentum * buf + d;  p -= lr * buf
+ *                                         (a zero buffer makes the first step buf = d, as torch's first step does)
+ *   RMSprop (no momentum, not centred):   v = alpha * v + (1 - alpha) * g * g;  p -= lr * g / (sqrt(v) + eps)
+ *   Adagrad (lr_decay 0):                 s += g * g;  p -= lr * g / (sqrt(s) + eps)
+ * momentum, weight_decay >= 0; 0 <= alpha <= 1; eps > 0. */
+int e2e_sgd_step_resident(float* params, const float* grad_sums, const float* participants, float* momentum_buffer,
+                          int64_t n, const float* lr, double momentum, double weight_decay, int* step_counter,
+                          void* stream);
+int e2e_rmsprop_step_resident(float* params, const float* grad_sums, const float* participants, float* square_avg,
+                              int64_t n, const float* lr, double alpha, double eps, int* step_counter, void* stream);
+int e2e_adagrad_step_resident(float* params, const float* grad_sums, const float* participants, float* sum, int64_t n,
+                              const float* lr, double eps, int* step_counter, void* stream);
+
 /* ------------------------------------------------------------------------------------------ */
 /* Depth network convolutions -- depth_estimation/networks.py:44-57,157-189,277-292             */
 /* fp32 implicit GEMM on v_mfma_f32_32x32x2_f32, NHWC activations.                               */
