@@ -3348,12 +3348,13 @@ struct WgradIn { const float *dz, *src0, *src1; float* workspace; };
 static int fwd_setup(const FwdOps& f, const ConvGeom& g, ConvArgs& a_out, int& vec_out, const char* who) {
     const int B = g.B, Hs = g.Hs, Ws = g.Ws, Cin = g.Cin, Cout = g.Cout, KH = g.KH, KW = g.KW, stride = g.stride, pad = g.pad, pad_mode = g.pad_mode;
     const int C1 = g.C1, up = g.up, ld_fwd = f.ld_fwd;
-    E2E_REQUIRE(f.src0 && f.w_fwd && f.out && B > 0 && Hs > 0 && Ws > 0 && Cin > 0 && Cout > 0, E2E_ERR_ARG, "%s: bad argument", who);
+    E2E_REQUIRE(f.src0 && f.w_fwd && f.out && B > 0 && Hs > 0 && Ws > 0 && Cin > 0 && Cout > 0 && KH > 0 && KW > 0, E2E_ERR_ARG, "%s: bad argument", who);
     E2E_REQUIRE(up == 1 || up == 2, E2E_ERR_ARG, "%s: upsample factor must be 1 or 2", who);
     E2E_REQUIRE(C1 > 0 && C1 <= Cin && (C1 == Cin || f.src1), E2E_ERR_ARG, "%s: bad channel split", who);
     E2E_REQUIRE(pad_mode == 0 || (pad_mode == 1 && pad == 1 && Hs >= 2 && Ws >= 2), E2E_ERR_ARG, "%s: reflection padding needs pad == 1", who);
     E2E_REQUIRE(stride == 1 || stride == 2, E2E_ERR_ARG, "%s: stride must be 1 or 2", who);
     E2E_REQUIRE(Hs % up == 0 && Ws % up == 0 && ld_fwd % 4 == 0 && ld_fwd >= Cout, E2E_ERR_ARG, "%s: bad sizes", who);
+    E2E_REQUIRE(pad >= 0 && Hs + 2 * pad >= KH && Ws + 2 * pad >= KW, E2E_ERR_ARG, "%s: the kernel must fit the padded input (pad >= 0)", who);
     const int vec = (Cin % 16 == 0 && (C1 == Cin || C1 % 16 == 0)) ? 4 : 1;
     E2E_REQUIRE(vec == 4 || (C1 == Cin && up == 1), E2E_ERR_ARG, "%s: the scalar path (Cin %% 16 != 0) takes a single full-resolution source", who);
     E2E_REQUIRE((int64_t)B * Hs * Ws * Cin * 4 < (1ll << 30) && (int64_t)KH * KW * Cin * ld_fwd * 4 < (1ll << 31), E2E_ERR_ARG,

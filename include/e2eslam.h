@@ -627,7 +627,12 @@ int e2e_conv_weight_layouts_batched(const long long* desc, int nlayers, void* st
  * (pad_mode 0 zeros, 1 reflection) -- upsample, concat and padding are gather arithmetic, never
  * materialised (networks.py:283-287, :186-188).  scale/shift: folded eval-mode BatchNorm and/or
  * bias (either may be NULL).  Cin % 16 != 0 (the RGB stem) takes a scalar-gather path that also
- * applies (v - in_sub) * in_mul to the image (networks.py:50). */
+ * applies (v - in_sub) * in_mul to the image (networks.py:50).
+ * Any Cout > 0 with ld_fwd >= Cout, ld_fwd % 4 == 0; any of the four activations behind any operand combination.  Refused with
+ * E2E_ERR_ARG: a NULL src0 / w_fwd / out; a non-positive B, Hs, Ws, Cin, Cout, KH or KW; up other than 1 or 2 (Hs, Ws multiples of
+ * it); C1 outside 1 .. Cin, or C1 < Cin without src1; a stride other than 1 or 2; pad < 0 or a kernel larger than the padded input
+ * (Hs + 2 pad < KH, Ws + 2 pad < KW); reflection with pad != 1 or Hs, Ws < 2; on the channel-quad path (Cin and a split C1 multiples of
+ * 16) a kernel beyond 3 x 3; on the scalar path an upsample or a second source.  tests/test_gpu_conv_fwd_contracts.py holds all of it. */
 int e2e_conv2d_fwd(const float* src0, const float* src1, int C1, int up, const float* w_fwd,
                    int ld_fwd, const float* scale, const float* shift, const float* residual,
                    float* out, int B, int Hs, int Ws, int Cin, int Cout, int KH, int KW, int stride,

@@ -1,6 +1,7 @@
 """Host-only: every entry point that include/e2eslam.h declares and csrc/depth_ops.hip, aux_losses.hip or nn_misc.hip implements is
 called by one of the two contract modules (tests/test_gpu_depth_aux_contracts.py, tests/test_gpu_nn_misc_contracts.py); the same for
-csrc/icp.hip and tests/test_gpu_icp_contracts.py, and for csrc/warp_photo.hip and tests/test_gpu_warp_photo_contracts.py."""
+csrc/icp.hip and tests/test_gpu_icp_contracts.py, for csrc/warp_photo.hip and tests/test_gpu_warp_photo_contracts.py, and for the forward
+entry points of csrc/conv.hip and tests/test_gpu_conv_fwd_contracts.py."""
 import os
 import re
 
@@ -49,3 +50,22 @@ def test_every_entry_point_of_the_warp_photo_file_has_a_contract_case():
     assert implemented <= declared, sorted(implemented - declared)
     called = set(re.findall(r"[\"'.](e2e_\w+)[\"'(]", _read(ROOT, "tests", "test_gpu_warp_photo_contracts.py")))
     assert not names - called, f"no contract case calls {sorted(names - called)}"
+
+
+CONV_FWD_ENTRY_POINTS = {
+    "e2e_conv2d_fwd", "e2e_conv2d_fwd_tuned", "e2e_head_fwd", "e2e_conv_weight_layouts", "e2e_conv_weight_layouts_batched",
+    "e2e_conv2d_splitk_workspace_floats", "e2e_conv_tuned_workspace_floats", "e2e_conv_gemm_choice", "e2e_conv_workspace_flag_floats",
+    "e2e_conv_streamk_error_index",
+}
+
+
+def test_every_forward_entry_point_of_the_conv_file_has_a_contract_case():
+    """The forward side of csrc/conv.hip (the backward side has tests/test_gpu_conv_bwd_contracts.py, e2e_conv2d_fwd_entry_pair its own
+    module): declared, implemented and called by tests/test_gpu_conv_fwd_contracts.py."""
+    declared = set(re.findall(r"^(?:int|int64_t|long long)\s+(e2e_\w+)\s*\(", _read(ROOT, "include", "e2eslam.h"), re.M))
+    implemented = set(re.findall(r"^(?:int|int64_t|long long)\s+(e2e_\w+)\s*\(", _read(CSRC, "conv.hip"), re.M))
+    assert len(CONV_FWD_ENTRY_POINTS) == 10
+    assert CONV_FWD_ENTRY_POINTS <= declared, sorted(CONV_FWD_ENTRY_POINTS - declared)
+    assert CONV_FWD_ENTRY_POINTS <= implemented, sorted(CONV_FWD_ENTRY_POINTS - implemented)
+    called = set(re.findall(r"[\"'.](e2e_\w+)[\"'(]", _read(ROOT, "tests", "test_gpu_conv_fwd_contracts.py")))
+    assert not CONV_FWD_ENTRY_POINTS - called, f"no contract case calls {sorted(CONV_FWD_ENTRY_POINTS - called)}"
