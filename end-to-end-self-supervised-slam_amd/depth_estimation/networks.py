@@ -7,7 +7,8 @@ Conv3x3 / Conv1x1), :206-221 (ScaleLayer, upsample), :224-292 (DispResNet_Indoor
 torchvision is not required: the ResNet body is defined here (BasicBlock, [2,2,2,2] / [3,4,6,3]).
 
 Every convolution goes through e2ehip.nn_ops.conv2d, which fuses eval-mode BatchNorm and the activation into
-the convolution's epilogue and keeps activations in channels-last memory.
+the convolution's epilogue and keeps activations in channels-last memory.  The 1-channel disparity heads (16 / 32 /
+64 / 128 -> 1, with 10*sigmoid+0.01 or the plain sigmoid) are kernels of their own with the activation fused.
 """
 from collections import OrderedDict
 
@@ -253,13 +254,14 @@ class _DecoderBase(nn.Module):
 
 
 class DepthDecoder(_DecoderBase):
-    """monodepth2 decoder: sigmoid disparities at every requested scale (reference: networks.py:107-154)."""
+    """monodepth2 decoder: sigmoid disparities at every requested scale (reference: networks.py:107-154).  The heads are the
+    16 / 32 / 64 / 128 -> 1 kernels of csrc/disp_heads.hip with the sigmoid fused; `self.sigmoid` stays as an attribute only."""
 
     def forward(self, input_features, index):
         self.outputs = {}
         for i, x in self._trunk(input_features):
             if i in self.scales:
-                self.outputs[("disp", index, i)] = self.sigmoid(self.convs[("dispconv", i)](x))
+                self.outputs[("disp", index, i)] = self.convs[("dispconv", i)](x, act="sigmoid")
         return self.outputs
 
 

@@ -8,8 +8,9 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib as L
 
-ACT = {None: 0, "relu": 1, "elu": 2, "disp": 3}
+ACT = {None: 0, "relu": 1, "elu": 2, "disp": 3, "sigmoid": 4}
 CL = torch.channels_last
+HEAD_SHAPES = tuple((1, c, 3, 3) for c in (16, 32, 64, 128))     # the disparity heads: num_ch_dec[0..3] -> 1 (networks.py:134-135)
 
 # ---- state -------------------------------------------------------------------------------------------------------------------
 # This module keeps NO process-wide state.  Everything that outlives a call hangs on the objects it describes:
@@ -191,9 +192,9 @@ def available():
 
 
 def supports(weight):
-    """Layer shapes the native kernels cover: Cout a multiple of 16 (MFMA path), the 16 -> 1 3x3 disparity head and the
-    1 -> 1 1x1 scale layer (Conv1x1(1, 1) of the scale-learning experiments)."""
-    return weight.shape[0] % 16 == 0 or tuple(weight.shape) in ((1, 16, 3, 3), (1, 1, 1, 1))
+    """Layer shapes the native kernels cover: Cout a multiple of 16 (MFMA path), the C -> 1 3x3 disparity heads of the decoder's four
+    scales (C = 16, 32, 64, 128) and the 1 -> 1 1x1 scale layer (Conv1x1(1, 1) of the scale-learning experiments)."""
+    return weight.shape[0] % 16 == 0 or tuple(weight.shape) in (HEAD_SHAPES + ((1, 1, 1, 1),))
 
 
 def _grad_out(param, shape):
@@ -374,6 +375,46 @@ class _Head(torch.autograd.Function):
         return dx, dw, db, None
 
 
+class _DispHead(torch.autograd.Function):
+    """Conv3x3(reflect) C -> 1 + activation for C = 16, 32, 64, 128 (csrc/disp_heads.hip): the heads of the monodepth2 decoder's four
+    scales.  The backward takes the gradient of the ACTIVATED output: act' is applied inside the kernels."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, act):
+        x = _cl(L.dev(x, "input"))
+        B, C, H, W = x.shape
+        w = L.dev(weight, "weight").contiguous()
+        y = torch.empty(B, 1, H, W, device=x.device, dtype=torch.float32)
+        L.call("e2e_disp_head_fwd", x=L.ptr(x), w=L.ptr(w), bias=L.ptr(bias), y=L.ptr(y), B=B, H=H, W=W, Cin=C, act=act, stream=L.stream())
+        ctx.save_for_backward(x, w, y)
+        ctx.cfg = (act, bias is not None)
+        ctx.params = (weight, bias)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        x, w, y = ctx.saved_tensors
+        act, has_bias = ctx.cfg
+        B, C, H, W = x.shape
+        g = g.contiguous()
+        dx = torch.empty(B, C, H, W, device=g.device, dtype=torch.float32, memory_format=CL) if ctx.needs_input_grad[0] else None
+        dw = torch.empty_like(w) if ctx.needs_input_grad[1] else None
+        db = torch.empty(1, device=g.device, dtype=torch.float32) if (has_bias and ctx.needs_input_grad[2]) else None
+        ws = torch.empty(L.query("e2e_disp_head_workspace_floats", B=B, H=H, W=W, Cin=C), device=g.device, dtype=torch.float32)
+        L.call("e2e_disp_head_bwd", dy=L.ptr(g), y=L.ptr(y), x=L.ptr(x), w=L.ptr(w), dx=L.ptr(dx), dw=L.ptr(dw), dbias=L.ptr(db),
+               workspace=L.ptr(ws), B=B, H=H, W=W, Cin=C, act=act, stream=L.stream())
+        sw = _sink(ctx.params[0], w.shape) if dw is not None else None
+        sb = _sink(ctx.params[1], (1,)) if db is not None else None
+        if sw is not None:                          # tiny tensors (at most 1153 numbers): add in place, return nothing
+            sw.add_(dw)
+            dw = None
+        if sb is not None:
+            sb.add_(db)
+            db = None
+        return dx, dw, db, None
+
+
 def _cl(t):
     return t if t.is_contiguous(memory_format=CL) else t.contiguous(memory_format=CL)
 
@@ -531,10 +572,12 @@ def conv2d(x, weight, bias=None, stride=1, padding=0, pad_mode="zeros", act=None
             raise NotImplementedError("the 1 -> 1 convolution is the plain scale layer (Conv1x1(1, 1))")
         return _Affine.apply(x, weight, bias, None, None, 0.0, None, False)
     if weight.shape[0] == 1:
-        if tuple(weight.shape) != (1, 16, 3, 3) or pad_mode != "reflect" or padding != 1 or stride != 1 or skip is not None \
+        if tuple(weight.shape) not in HEAD_SHAPES or pad_mode != "reflect" or padding != 1 or stride != 1 or skip is not None \
                 or upsample != 1 or residual is not None or bn_scale_shift is not None:
-            raise NotImplementedError("single-output-channel convolution other than the 16->1 reflect 3x3 disparity head")
-        return _Head.apply(x, weight, bias, ACT[act])
+            raise NotImplementedError("single-output-channel convolution other than the reflect 3x3 disparity heads (16, 32, 64 or 128 -> 1)")
+        if weight.shape[1] == 16 and act in (None, "disp"):
+            return _Head.apply(x, weight, bias, ACT[act])                       # the indoor network's head (csrc/conv.hip)
+        return _DispHead.apply(x, weight, bias, ACT[act])                       # every other head (csrc/disp_heads.hip)
     scale, shift = bn_scale_shift if bn_scale_shift is not None else (None, None)
     if bias is not None and bn_scale_shift is not None:
         raise ValueError("a bias together with a folded BatchNorm is not used by the network")

@@ -42,8 +42,8 @@ def conv2d(x, weight, bias=None, stride=1, padding=0, pad_mode="zeros", act=None
     in_norm: (sub, mul) applied to x before the convolution (the stem's (x - 0.45) / 0.225)."""
     _require_device(x)
     if not conv.supports(weight):
-        raise NotImplementedError(f"convolution weight {tuple(weight.shape)}: the native kernels cover Cout % 16 == 0, the 16 -> 1 3x3 "
-                                  "reflect disparity head and the 1 -> 1 1x1 scale layer; there is no library fallback")
+        raise NotImplementedError(f"convolution weight {tuple(weight.shape)}: the native kernels cover Cout % 16 == 0, the 3x3 reflect "
+                                  "disparity heads (16, 32, 64 or 128 -> 1) and the 1 -> 1 1x1 scale layer; there is no library fallback")
     if bn is not None and (bn[0].requires_grad or bn[1].requires_grad):
         if bias is not None or act not in (None, "relu") or skip is not None or upsample != 1:
             raise NotImplementedError("a trainable eval-mode BatchNorm follows a plain convolution (ResNet body) only")

@@ -592,6 +592,32 @@ def depth_from_disp_fixed_scale(disp, scale=1.0):
     return _FixedScale.apply(disp, scale)
 
 
+class _RangeDepth(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, disp, min_depth, max_depth, scale):
+        d = L.dev(disp, "disp").contiguous()
+        depth = torch.empty_like(d)
+        ctx.cfg = (float(min_depth), float(max_depth), float(scale))
+        L.call("e2e_disp_range_depth_fwd", L.ptr(d), *ctx.cfg, L.ptr(depth), d.numel(), L.stream())
+        ctx.save_for_backward(d)
+        return depth
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        (d,) = ctx.saved_tensors
+        gd = torch.empty_like(d)
+        L.call("e2e_disp_range_depth_bwd", L.ptr(g.contiguous()), L.ptr(d), *ctx.cfg, L.ptr(gd), d.numel(), L.stream())
+        return gd, None, None, None
+
+
+def depth_from_disp_range(disp, min_depth, max_depth, scale=1.0):
+    """depth = scale / (1 / max_depth + (1 / min_depth - 1 / max_depth) * disp): convert_disp_to_depth of the monodepth2 branch
+    (training_utils.py:106-118, train_depth.py:297-299) on a sigmoid disparity in [0, 1], times the constant depth scale of
+    train_depth.py:302-312 (scale 1.0: the plain conversion); one kernel each way."""
+    return _RangeDepth.apply(disp, min_depth, max_depth, scale)
+
+
 class _MeanDiff(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, b, kind):

@@ -16,6 +16,10 @@ loss/losses.py, PointFusion / RGBDImages, knn_points / ChamferDistance, the dept
 default flags (configs/config.yaml:37-58: masked photometric loss only) the image-space part of a step is the fused
 e2e_warp_photo_* pair instead of the operator-by-operator composition -- `fused_losses=False` keeps the latter.
 
+`MODEL.depth_network` selects the depth network as in the reference (train_depth.py:124-179): `indoor` is DispResNet_Indoor, `monodepth2`
+is ResnetEncoder + DepthDecoder with a sigmoid disparity at every scale of `DATA.scales`, turned into depth by convert_disp_to_depth
+(DATA.min_depth / max_depth) and loaded by load_model() from `<name>.pth` files.
+
     python train_depth.py --config_path configs/config_train_depth.yaml
 """
 import os
@@ -29,7 +33,7 @@ if _HERE not in sys.path:
     sys.path.insert(0, _HERE)
 
 from chamferdist import ChamferDistance  # noqa: E402
-from depth_estimation.networks import DispResNet_Indoor  # noqa: E402
+from depth_estimation.networks import DepthDecoder, DispResNet_Indoor, ResnetEncoder  # noqa: E402
 from depth_estimation.view_synthesis import BackprojectDepth, Project3D  # noqa: E402
 from e2ehip import ops  # noqa: E402
 from e2ehip.synthetic import make_sequence  # noqa: E402
@@ -130,19 +134,49 @@ class Depth_Estimation:
         else:
             raise ValueError("MODEL.slam must be ICPSLAM or PointFusion")
         print("Using the {} for SLAM".format(a.MODEL.slam))
-        if a.MODEL.depth_network != "indoor":
-            # the reference keeps a monodepth2 branch "in case we decide to do outdoor" (train_depth.py:299); its refinement code indexes
-            # self.models["depth"], i.e. the indoor network -- that is the network on the path
-            raise NotImplementedError("MODEL.depth_network: only the indoor network is on the refinement path")
-        self.models["depth"] = DispResNet_Indoor(num_layers=a.MODEL.num_layers, pretrained=a.MODEL.weights_init_encoder == "imagenet")
-        if self._state_dict is not None:
-            self.models["depth"].load_state_dict(self._state_dict)
-        elif a.MODEL.use_pretrained_models:
-            self.load_model_indoor()
-        self.models["depth"].to(self.device)
-        self.train_params = list(self.models["depth"].parameters())
+        self.train_params = []
+        if a.MODEL.depth_network == "monodepth2":
+            # the reference's outdoor branch (train_depth.py:124-136): ResnetEncoder + DepthDecoder with a sigmoid head at every scale of
+            # DATA.scales, as two entries of self.models with two parameter lists
+            self.models["depth_encoder"] = ResnetEncoder(a.MODEL.num_layers, a.MODEL.weights_init_encoder == "imagenet")
+            self.models["depth_decoder"] = DepthDecoder(self.models["depth_encoder"].num_ch_enc, a.DATA.scales)
+            names = ("depth_encoder", "depth_decoder")
+            print("Loaded ResNet{} based depth network".format(a.MODEL.num_layers))
+            if self._state_dict is not None:
+                for n in names:
+                    self.models[n].load_state_dict(self._state_dict[n])
+            elif a.MODEL.use_pretrained_models:
+                self.load_model()
+        elif a.MODEL.depth_network == "indoor":
+            self.models["depth"] = DispResNet_Indoor(num_layers=a.MODEL.num_layers, pretrained=a.MODEL.weights_init_encoder == "imagenet")
+            names = ("depth",)
+            if self._state_dict is not None:
+                self.models["depth"].load_state_dict(self._state_dict)
+            elif a.MODEL.use_pretrained_models:
+                self.load_model_indoor()
+        else:
+            raise ValueError("Given {} is not a valid depth network option".format(a.MODEL.depth_network))       # train_depth.py:174
+        for n in names:
+            self.models[n].to(self.device)
+            self.train_params += list(self.models[n].parameters())
         self.optimizer = define_optim(a, self.train_params)
         self.schedular = define_schedular(a, self.optimizer)
+
+    def load_model(self):
+        """train_depth.py:798-822: for every name of MODEL.pretrained_models_list, `<MODEL.load_depth_path>/<name>.pth` is a state dict of
+        which the keys the module has are taken (monodepth2's encoder.pth also carries `height` / `width`), the rest of the module's
+        own state stays."""
+        a = self.args
+        a.MODEL.load_depth_path = os.path.expanduser(str(a.MODEL.load_depth_path))
+        assert os.path.isdir(a.MODEL.load_depth_path), "Cannot find folder {}".format(a.MODEL.load_depth_path)
+        print("loading model from folder {}".format(a.MODEL.load_depth_path))
+        for n in a.MODEL.pretrained_models_list:
+            print("Loading {} weights...".format(n))
+            path = os.path.join(a.MODEL.load_depth_path, "{}.pth".format(n))
+            model_dict = self.models[n].state_dict()
+            pretrained_dict = torch.load(path, map_location="cpu")
+            model_dict.update({k: v for k, v in pretrained_dict.items() if k in model_dict})
+            self.models[n].load_state_dict(model_dict)
 
     def load_model_indoor(self):
         path = os.path.join(os.path.expanduser(self.args.MODEL.load_depth_path), "depth.pth.tar")
@@ -207,7 +241,11 @@ class Depth_Estimation:
                 depth_tensor = []
                 for index in range(self.sequence_length):
                     frame = colors[:, index]
-                    if a.ABLATION.dual_disparity:
+                    monodepth2 = a.MODEL.depth_network == "monodepth2"
+                    if monodepth2:
+                        # train_depth.py:291-294: sigmoid disparities at every scale of DATA.scales; the flip trick is not applied here
+                        inputs.update(self.models["depth_decoder"](self.models["depth_encoder"](frame), index))
+                    elif a.ABLATION.dual_disparity:
                         inputs.update(self.models["depth"](torch.cat([frame, torch.flip(frame, [2])], 0), index))
                         inputs.update(self.process_disparity(inputs, index))
                     else:
@@ -217,7 +255,12 @@ class Depth_Estimation:
                         k *= float(intrinsics[0, 0, 0, 0]) / a.ABLATION.focal_pretrain                  # scale_by_f (training_utils.py:142-152)
                     if a.ABLATION.scaled_depth:
                         k *= a.ABLATION.scaling_depth                                                    # fixed "median" scale (:343-345)
-                    inputs[("depth", index, scale)] = ops.depth_from_disp_fixed_scale(inputs[("disp", index, scale)], k)
+                    if monodepth2:                                                                       # convert_disp_to_depth * k (:297-312)
+                        inputs[("depth", index, scale)] = ops.depth_from_disp_range(inputs[("disp", index, scale)], a.DATA.min_depth, a.DATA.max_depth, k)
+                    else:
+                        inputs[("depth", index, scale)] = ops.depth_from_disp_fixed_scale(inputs[("disp", index, scale)], k)
+                    # the reference's monodepth2 branch stores this with `.copy()` on a tensor (:315), an AttributeError; both branches here
+                    # keep the indoor branch's `.clone().detach()` (:349)
                     if a.OPTIMIZATION.refinement == "PFT" and a.LOSS.depth_regularizer and refine_step == 0:
                         self.initial_depths[("initial_depth", index, scale)] = inputs[("depth", index, scale)].clone().detach()
                     depth_tensor.append(inputs[("depth", index, scale)].unsqueeze(1))
@@ -440,6 +483,7 @@ def default_config(height=256, width=320, frames=(0, -1), refinement_steps=3):
         DATA=dict(name="synthetic", height=height, width=width, frames=list(frames), scales=[0], seed=1234, dilation=2, stride=2, start=418,
                   use_gt_pose=True, normalize_intrinsics=False, min_depth=0.1, max_depth=80.0),
         MODEL=dict(depth_network="indoor", num_layers=18, weights_init_encoder=False, use_pretrained_models=False, load_depth_path="",
+                   pretrained_models_list=["depth_encoder", "depth_decoder"],
                    slam="PointFusion", odom="gt", dist_th=0.05, angle_th=20, sigma=0.6, numiters=20, padding_mode="border", refinement_mode=True),
         LOSS=dict(chamfer_distance=False, chamfer_weight=0.25, knn_points=False, knn_points_weight=0.25, auto_masking=False, min_reprojection=False,
                   photometric_mask=True, geometric=False, geometric_weight=0.5, smoothness=False, smoothness_weight=1e-3, depth_regularizer=False,

@@ -874,6 +874,40 @@ int e2e_head_bwd(const float* dz, const float* x, const float* w, float* dx, flo
 int e2e_head_bwd_act(const float* dz, const float* x, const float* w, float* dx, float* dw, float* dbias,
                      float* workspace, int B, int H, int W, int Cin, int in_act, void* stream);
 
+/* The multi-scale disparity heads of the monodepth2 decoder (csrc/disp_heads.hip): Conv3x3(reflect) Cin -> 1 + activation at every
+ * scale of DATA.scales, networks.py:134-135,151-152 (num_ch_dec[0..3] = 16, 32, 64, 128 input channels).
+ *
+ * e2e_disp_head_fwd: x (B,H,W,Cin) NHWC, w (1,Cin,3,3) as torch lays it out, bias (1) or NULL (no bias), y (B,H,W):
+ *     y[b,h,w] = act( bias + sum_{ci,kh,kw} w[0,ci,kh,kw] * x[b, r(h+kh-1,H), r(w+kw-1,W), ci] ),
+ * r the index map of ReflectionPad2d(1) (-1 -> 1, n -> n-2).  act: 0 none, 3 disp = 10*sigmoid(.)+0.01, 4 sigmoid.
+ * Refused with E2E_ERR_ARG, nothing written: a NULL x, w or y; B < 1; H < 2 or W < 2 (the pad needs a second pixel); Cin other than
+ * 16, 32, 64, 128; any other act (1 ReLU and 2 ELU of the other convolutions included).
+ *
+ * e2e_disp_head_bwd: dy (B,H,W) is the gradient of the ACTIVATED output and y (B,H,W) the forward's output; the kernels form
+ *     dz = dy * act'(y):   act 0: dy;   act 4: dy * y (1 - y);   act 3: dy * 10 s (1 - s) with s = (y - 0.01) / 10
+ * themselves (no activation-backward launch) and write, each only when its pointer is not NULL (a NULL one is neither computed nor
+ * written):
+ *     dx (B,H,W,Cin): dx[b,p,ci]     = sum over the (q, kh, kw) whose reflected tap position is p of dz[b,q] * w[0,ci,kh,kw]
+ *     dw (1,Cin,3,3): dw[0,ci,kh,kw] = sum_{b,h,w} dz[b,h,w] * x[b, r(h+kh-1,H), r(w+kw-1,W), ci]
+ *     dbias (1):      dbias[0]       = sum_{b,h,w} dz[b,h,w]
+ * dw and dbias are per-workgroup partial sums (in workspace) added by a second kernel in a fixed order; no atomics anywhere: two calls
+ * on the same inputs give the same bits.  workspace: exactly e2e_disp_head_workspace_floats(B, H, W, Cin) floats are used (a number of
+ * partial rows capped by a constant and by the pixel count, times 9 Cin + 1; 0 for sizes the heads refuse); it is required even when
+ * only dx is asked for.  All pixel and element offsets are 64-bit.  Refused with E2E_ERR_ARG, nothing written: a NULL dy, y, x, w or
+ * workspace, and the forward's conditions on B, H, W, Cin and act. */
+int e2e_disp_head_fwd(const float* x, const float* w, const float* bias, float* y, int B, int H, int W, int Cin, int act, void* stream);
+int64_t e2e_disp_head_workspace_floats(int B, int H, int W, int Cin);
+int e2e_disp_head_bwd(const float* dy, const float* y, const float* x, const float* w, float* dx, float* dw, float* dbias,
+                      float* workspace, int B, int H, int W, int Cin, int act, void* stream);
+
+/* convert_disp_to_depth (utils/training_utils.py:106-118) times the fixed depth scale of train_depth.py:302-312, one launch each way:
+ *     depth[i] = scale / (lo + (hi - lo) * disp[i]),   lo = 1 / max_depth, hi = 1 / min_depth,   i < n;
+ *     g_disp[i] = -g_depth[i] * scale * (hi - lo) / (lo + (hi - lo) * disp[i])^2.
+ * Refused with E2E_ERR_ARG, nothing written: a NULL pointer, n < 1, or not 0 < min_depth < max_depth. */
+int e2e_disp_range_depth_fwd(const float* disp, float min_depth, float max_depth, float scale, float* depth, int64_t n, void* stream);
+int e2e_disp_range_depth_bwd(const float* g_depth, const float* disp, float min_depth, float max_depth, float scale, float* g_disp,
+                             int64_t n, void* stream);
+
 /* ------------------------------------------------------------------------------------------ */
 /* Frame-to-model ICP odometry (gradslam odometry providers; MODEL.odom: icp | gradicp)          */
 /* ------------------------------------------------------------------------------------------ */
