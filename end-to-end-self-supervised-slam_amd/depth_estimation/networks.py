@@ -36,12 +36,15 @@ class _ConvBN(nn.Module):
 
         Train-mode BatchNorm (batch statistics + running-average update): the reference only switches to eval() when
         MODEL.refinement_mode is set (online_adaption.py:175-184, train_depth.py:246-247); with the flag off the network stays in train
-        mode.  That configuration is NOT the benchmarked path and has no native kernel: the convolution runs on the HIP kernel
-        and the normalisation itself goes through the nn.BatchNorm2d module (running statistics, num_batches_tracked and the
-        momentum=None cumulative average exactly as in the reference's modules) -- the one place where an ATen operator computes
-        on behalf of the network ("train-mode BatchNorm")."""
+        mode.  The convolution writes its raw output and e2ehip's train-mode BatchNorm kernels (csrc/bn_train.hip) follow it: batch
+        statistics, the running buffers, num_batches_tracked and the momentum=None cumulative average exactly as nn.BatchNorm2d
+        keeps them, all on the device, with the residual add and the ReLU in the normalising pass ("train-mode
+        BatchNorm").  A module the kernels do not cover (track_running_stats=False, affine=False, channels no multiple of 4), and
+        every module under E2E_BN_NATIVE=0, is normalised by the nn.BatchNorm2d module itself."""
         if bn.training:
             y = nn_ops.conv2d(x, conv.weight, None, conv.stride[0], conv.padding[0], "zeros", None, None, in_norm=in_norm)
+            if nn_ops.bn_train_native(bn):
+                return nn_ops.batch_norm_train(y, bn, relu, residual)
             y = bn(y)       # the MODULE, not F.batch_norm: num_batches_tracked advances and momentum=None means the cumulative average
             if residual is not None:
                 y = y + residual

@@ -274,6 +274,95 @@ def conv2d_bn_affine(x, weight, bn, stride, padding, pad_mode, residual=None, re
     return _Affine.apply(z, w, b, rm, rv, eps, residual, bool(relu))
 
 
+class _BNTrain(torch.autograd.Function):
+    """y = relu?( BatchNorm_train(z) + residual ) on NHWC memory (csrc/bn_train.hip): batch statistics over the B*H*W pixels, the
+    running buffers and num_batches_tracked updated IN PLACE on the device by the same call (`stats` = (running_mean, running_var,
+    num_batches_tracked) of the module; their version counters advance so that nn_ops._fold_bn sees the new statistics after
+    eval()).  momentum < 0 is nn.BatchNorm2d(momentum=None): the cumulative average over the device-side count.  Nothing is read on
+    the host.  gamma / beta get their gradients the way _Affine's do: into the flat bucket under direct_weight_grads()."""
+
+    @staticmethod
+    def forward(ctx, z, gamma, beta, stats, momentum, eps, residual, relu):
+        z = L.dev(z, "input")
+        if z.dim() != 4:
+            raise ValueError(f"expected a (B,C,H,W) tensor, got {tuple(z.shape)}")
+        C = z.shape[1]
+        P = z.numel() // C
+        if P < 2:
+            raise ValueError(f"Expected more than 1 value per channel when training, got input size {z.size()}")
+        rm, rv, nbt = stats
+        for t, n in ((gamma, "weight"), (beta, "bias"), (rm, "running_mean"), (rv, "running_var")):
+            if L.dev(t, n).shape != (C,) or not t.is_contiguous():
+                raise ValueError(f"{n}: expected a contiguous ({C},) tensor, got {tuple(t.shape)}")
+        if L.dev(nbt, "num_batches_tracked", torch.int64).numel() != 1:
+            raise ValueError("num_batches_tracked: expected one int64 element")
+        z = _cl(z)
+        dev, st = z.device, L.stream()
+        if residual is not None:
+            residual = _cl(L.dev(residual, "residual"))
+            if residual.shape != z.shape:
+                raise ValueError(f"residual {tuple(residual.shape)} does not match the input {tuple(z.shape)}")
+        y = torch.empty_like(z)
+        # one allocation: the workspace (a multiple of 4 floats), then save_mean and save_rstd; the backward reuses the workspace part
+        nws = L.query("e2e_bn_train_workspace_floats", P, C)
+        stat = torch.empty(nws + 2 * C, device=dev, dtype=torch.float32)
+        base = stat.data_ptr()
+        L.call("e2e_bn_train_fwd", z=L.ptr(z), gamma=L.ptr(gamma), beta=L.ptr(beta), residual=L.ptr(residual), relu=int(bool(relu)), eps=float(eps),
+               momentum=float(momentum), running_mean=L.ptr(rm), running_var=L.ptr(rv), num_batches_tracked=L.ptr(nbt), y=L.ptr(y),
+               save_mean=ctypes.c_void_p(base + 4 * nws), save_rstd=ctypes.c_void_p(base + 4 * (nws + C)), P=P, C=C, workspace=ctypes.c_void_p(base),
+               stream=st)
+        torch.autograd.graph.increment_version((rm, rv, nbt))       # written behind torch's back
+        ctx.save_for_backward(z, gamma, stat, y if relu else None)
+        ctx.params = (gamma, beta)
+        ctx.has_res = residual is not None
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        z, gamma, stat, y = ctx.saved_tensors
+        p_gamma, p_beta = ctx.params
+        C = z.shape[1]
+        P = z.numel() // C
+        nws, base = stat.numel() - 2 * C, stat.data_ptr()
+        g = _cl(g)
+        want_z, want_g, want_b, want_r = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2], ctx.has_res and ctx.needs_input_grad[6]
+        if not (want_z or want_g or want_b or want_r):
+            return None, None, None, None, None, None, None, None
+        sg = _sink(p_gamma, p_gamma.shape) if want_g else None
+        sb = _sink(p_beta, p_beta.shape) if want_b else None
+        direct = (want_g or want_b) and (sg is not None or not want_g) and (sb is not None or not want_b)
+        gg = (sg if direct else torch.empty(C, device=g.device, dtype=torch.float32)) if want_g else None
+        gb = (sb if direct else torch.empty(C, device=g.device, dtype=torch.float32)) if want_b else None
+        dz = torch.empty_like(g) if want_z else None
+        masked = torch.empty_like(g) if (want_r and y is not None) else None           # dy * [y > 0]; without a ReLU the residual's gradient IS g
+        dres = (masked if y is not None else g) if want_r else None
+        if want_z or want_g or want_b or masked is not None:
+            L.call("e2e_bn_train_bwd", dy=L.ptr(g), y=L.ptr(y), z=L.ptr(z), gamma=L.ptr(gamma), save_mean=ctypes.c_void_p(base + 4 * nws),
+                   save_rstd=ctypes.c_void_p(base + 4 * (nws + C)), P=P, C=C, dz=L.ptr(dz), dresidual=L.ptr(masked), dgamma=L.ptr(gg), dbeta=L.ptr(gb),
+                   accumulate=1 if direct else 0, workspace=ctypes.c_void_p(base), stream=L.stream())
+        if direct:
+            gg = gb = None
+        return dz, gg, gb, None, None, None, dres, None
+
+
+def conv2d_bn_train(x, weight, bn_module, stride, padding, pad_mode, residual=None, relu=False, in_norm=None):
+    """relu?( BN_train(conv(x)) + residual ): the convolution writes its raw output, the train-mode BatchNorm of `bn_module` (an
+    nn.BatchNorm2d with affine parameters and running statistics) is three launches behind it.  momentum, eps and the buffers are taken
+    from the module on the host; the count of batches lives and advances on the device."""
+    z = conv2d(x, weight, None, stride, padding, pad_mode, in_norm=in_norm)
+    return bn_train(z, bn_module, residual, relu)
+
+
+def bn_train(z, bn_module, residual=None, relu=False):
+    """relu?( BN_train(z) + residual ) with the hyper-parameters and buffers of `bn_module` (momentum=None -> -1.0: cumulative average)."""
+    m = bn_module
+    if not (m.affine and m.track_running_stats):
+        raise NotImplementedError("the native train-mode BatchNorm takes a module with affine parameters and running statistics")
+    return _BNTrain.apply(z, m.weight, m.bias, (m.running_mean, m.running_var, m.num_batches_tracked),
+                          -1.0 if m.momentum is None else float(m.momentum), float(m.eps), residual, bool(relu))
+
+
 class _MaxPool(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):

@@ -1,10 +1,12 @@
 """Convolution-level operators of the depth network: thin argument plumbing over the native kernels (csrc/conv.hip,
-csrc/nn_misc.hip).  There is ONE backend -- the hand-written HIP kernels; a layer shape they do not cover raises
+csrc/nn_misc.hip, csrc/bn_train.hip).  There is ONE backend -- the hand-written HIP kernels; a layer shape they do not cover raises
 (no torch / MIOpen path: the A/B scaffold that round 1 kept here now lives in tools/conv_bench.py, outside the product).
 
 Activations are NCHW-shaped tensors in channels_last memory (NHWC), the layout the implicit-GEMM kernels want
 (K = Cin contiguous) and the layout the reference's frames already have (online_adaption.py:215-220).
 """
+import os
+
 import torch
 
 from . import conv
@@ -50,6 +52,28 @@ def conv2d(x, weight, bias=None, stride=1, padding=0, pad_mode="zeros", act=None
         return conv.conv2d_bn_affine(x, weight, bn, stride, padding, pad_mode, residual, act == "relu", in_norm)
     return conv.conv2d(x, weight, bias, stride, padding, pad_mode, act, _fold_bn(bn) if bn is not None else None, residual, skip,
                        upsample, in_norm)
+
+
+def bn_train_native(bn_module):
+    """Whether a train-mode nn.BatchNorm2d runs on the native kernels (csrc/bn_train.hip): it has affine parameters and running
+    statistics, and its channel count is a multiple of 4.  E2E_BN_NATIVE=0, read at every call, answers no for every module -- the
+    nn.BatchNorm2d module then normalises, as before the kernels existed (the comparison arm of tools/bn_train_bench.py)."""
+    if os.environ.get("E2E_BN_NATIVE", "1") == "0":
+        return False
+    return bool(bn_module.affine and bn_module.track_running_stats and bn_module.num_features % 4 == 0)
+
+
+def batch_norm_train(z, bn_module, relu=False, residual=None):
+    """relu?( nn.BatchNorm2d in train mode (z) + residual ): batch statistics over (B, H, W), the module's running_mean / running_var /
+    num_batches_tracked updated in place on the device (momentum=None: cumulative average), gradients for z, the residual and the
+    module's weight / bias.  Three launches forward, three backward; no host read.  A module that bn_train_native() turns down
+    (track_running_stats=False, affine=False, channels no multiple of 4) raises here: its caller keeps it on the module."""
+    _require_device(z)
+    if not bn_module.affine or not bn_module.track_running_stats or bn_module.num_features % 4 != 0:
+        raise NotImplementedError("the native train-mode BatchNorm covers affine modules with running statistics and channels % 4 == 0")
+    if z.dim() != 4 or z.shape[1] != bn_module.num_features:
+        raise ValueError(f"expected a (B,{bn_module.num_features},H,W) tensor, got {tuple(z.shape)}")
+    return conv.bn_train(z, bn_module, residual, relu)
 
 
 def max_pool_3x3_s2(x):

@@ -852,6 +852,39 @@ int64_t e2e_affine_bwd_workspace_floats(int C);
 int e2e_affine_bwd(const float* dy, const float* z, const float* mean, const float* rstd, int64_t P,
                    int C, float* dgamma, float* dbeta, int accumulate, float* workspace, void* stream);
 
+/* Train-mode BatchNorm2d behind a convolution (csrc/bn_train.hip; networks.py's ResNet body when MODEL.refinement_mode is off and the
+ * network stays in train mode, train_depth.py:246-247).  z, y, residual, dy, dz, dresidual are (P, C): P = B*H*W pixels of an NHWC
+ * tensor, fp32, 16-byte aligned; C a multiple of 4; P >= 2 (batch statistics need a second value per channel).  Per-channel vectors
+ * (C floats) carry no alignment requirement.  workspace: exactly e2e_bn_train_workspace_floats(P, C) floats, the same for both
+ * directions (a number of partial-sum rows that depends on (P, C) only, times 2 C, plus 2 C; 0 for sizes that are refused).
+ *
+ * Forward, three launches (partial statistics about the channel's first pixel -- never raw moments --, a fixed-order float64 merge,
+ * the normalisation); backward, three launches (partial sums, fixed-order merge, the elementwise pass; the merge pair is skipped
+ * when only dresidual is asked for, the elementwise pass when neither dz nor dresidual is).  No atomics and no host read: two calls on
+ * the same inputs give the same bits.  All element offsets are 64-bit.
+ * Refused with E2E_ERR_ARG before any launch: a NULL z, y (forward), dy (backward), save_mean, save_rstd or workspace; P < 2; C <= 0 or
+ * C % 4 != 0; eps <= 0; only some of running_mean / running_var / num_batches_tracked given; a backward whose dz, dresidual, dgamma and
+ * dbeta are all NULL; a misaligned (P, C) tensor or workspace. */
+int64_t e2e_bn_train_workspace_floats(int64_t P, int C);
+
+/* y = relu?( (z - mean_B) * rstd_B * gamma + beta + residual? ); batch mean / BIASED variance over the P pixels;
+ * running_mean = (1-f) running_mean + f mean_B, running_var likewise with the UNBIASED variance (P / (P-1));
+ * *num_batches_tracked += 1 (int64, device); f = momentum, or 1 / (the incremented count) when momentum < 0
+ * (nn.BatchNorm2d(momentum=None)).  running_* / num_batches_tracked may all be NULL (no update).
+ * save_mean / save_rstd (C floats each) are what the backward needs.  gamma / beta NULL: 1 / 0. */
+int e2e_bn_train_fwd(const float* z, const float* gamma, const float* beta, const float* residual, int relu,
+                     float eps, float momentum, float* running_mean, float* running_var,
+                     int64_t* num_batches_tracked, float* y, float* save_mean, float* save_rstd,
+                     int64_t P, int C, float* workspace, void* stream);
+
+/* g = dy * [y > 0] (y NULL: g = dy);  dbeta = sum_p g;  dgamma = sum_p g * xhat;
+ * dz = gamma * rstd * (g - dbeta / P - xhat * dgamma / P);  dresidual = g (NULL: not wanted).
+ * dz, dgamma, dbeta may each be NULL; accumulate != 0 adds to dgamma / dbeta (flat gradient bucket). */
+int e2e_bn_train_bwd(const float* dy, const float* y, const float* z, const float* gamma,
+                     const float* save_mean, const float* save_rstd, int64_t P, int C,
+                     float* dz, float* dresidual, float* dgamma, float* dbeta, int accumulate,
+                     float* workspace, void* stream);
+
 /* upsample() of networks.py:218-221 [+ torch.cat with the skip tensor, :283-286]: x (B,h,w,C1), skip (B,2h,2w,C2) or
  * NULL -> y (B,2h,2w,C1+C2), all NHWC.  (Inside the decoder this is fused into the next convolution's gather.) */
 int e2e_upsample2_concat(const float* x, const float* skip, float* y, int B, int h, int w, int C1,
