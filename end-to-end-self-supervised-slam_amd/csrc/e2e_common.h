@@ -62,6 +62,11 @@ __device__ __forceinline__ int reflect1(int i, int n) {
     return i >= n ? 2 * n - 2 - i : i;
 }
 
+// multiplicity with which output pixel q's reflect-padded 3-window sees input pixel p (|p-q| <= 1)
+__device__ __forceinline__ float refl_mult(int p, int q, int n) {
+    return ((q == 0 && p == 1) || (q == n - 1 && p == n - 2)) ? 2.f : 1.f;
+}
+
 // Per-batch projection geometry: cam = Ki * [x,y,1];  c = P[:, :3] * (d * cam) + P[:, 3]
 // reference: depth_estimation/view_synthesis.py:36-39 (Kinv3 @ pix, * depth) and :57-59 (P = (K@T)[:3]).
 struct Geom {

@@ -8,25 +8,19 @@
 //                                   -> k_reduce_terms (fixed-order sums -> the five loss values)
 //   e2e_smoothness_norm_lossgrad    k_sm_sum -> k_sm_grad -> k_sm_apply (mean, normalise, loss + gradient ACCUMULATED into d/d disp)
 //
-// k_warp_photo_terms keeps the tile scheme of warp_photo_fused.hip (256 threads = 32x16 pixels, two rows per thread, 36x20 warped
-// positions in LDS, SSIM statistics on 34x18, 3x3 fold-back of (G1,G2,G3)) with three operands per position instead of two:
-// {synth*m, src*m, tgt*m}.  The identity map photometric(src*m, tgt*m) of auto-masking needs no gradient (m is piecewise constant);
-// its VALUE at every q of the 34x18 region decides whether the reprojection map's gradient at q survives the per-pixel minimum.
+// k_warp_photo_terms runs the tile scheme of k_warp_photo_lossgrad (warp_photo_fused.hip; constants in lossgrad_tile.h: 256 threads =
+// 32x16 pixels, two rows per thread, 36x20 warped positions in LDS, SSIM statistics on 34x18, 3x3 fold-back of (G1,G2,G3)) with three
+// operands per position instead of two: {synth*m, src*m, tgt*m}.  The identity map photometric(src*m, tgt*m) of auto-masking needs no
+// gradient (m is piecewise constant); its VALUE at every q of the 34x18 region decides whether the reprojection map's gradient at q
+// survives the per-pixel minimum.
 // The default configuration never comes here: warp_photo_fused.hip is untouched.
 // LDS: 9 x 720 + 10 x 612 floats = 50.4 KB per workgroup (3 workgroups per CU by LDS).
 // fp contraction is ON (FMA), as in warp_photo_fused.hip: tolerance for this path is 1e-4 relative.
 #include "e2e_common.h"
 #pragma clang fp contract(fast)
+#include "lossgrad_tile.h"
 
-#define TT_W 32
-#define TT_H 16
-#define TX_W (TT_W + 4)
-#define TX_H (TT_H + 4)
-#define TG_W (TT_W + 2)
-#define TG_H (TT_H + 2)
-#define TNT 256
-#define T_NPOS (TX_W * TX_H)
-#define T_NQ (TG_W * TG_H)
+#define TNT 256            // block size of the pre-pass, the reduction and the smoothness kernels (their sums add exactly four waves)
 
 // c = d * (M [x,y,1]) + p4 : rows of M (9) then p4 (3), from the device matrices (same arithmetic as warp_photo_fused.hip phase 0)
 __device__ __forceinline__ void terms_geometry(const float* __restrict__ K, const float* __restrict__ invK, const float* __restrict__ T, int b, int tid,
@@ -138,23 +132,22 @@ __global__ __launch_bounds__(TNT) void k_terms_prepare(const float* __restrict__
 __global__ void k_terms_clear_count(int* count) { *count = 0; }
 
 template <int PAD>
-__global__ __launch_bounds__(TNT) void k_warp_photo_terms(
+__global__ __launch_bounds__(TILE_NT) void k_warp_photo_terms(
     const float* __restrict__ depth, const float* __restrict__ d_s, const float* __restrict__ src, e2e_strides ss,
     const float* __restrict__ tgt, e2e_strides ts, const float* __restrict__ K, const float* __restrict__ invK,
     const float* __restrict__ T, int use_mask, int reg_kind, const float* __restrict__ ri_t, const float* __restrict__ ri_s,
     int terms, const float* __restrict__ noise, float w_photo, float w_reg, float w_geo, const int* __restrict__ valid_count,
     float* __restrict__ g_dt, float* g_ds, float* __restrict__ partials, int B, int H, int W) {
-    constexpr int PPT = 2, NE = PPT + 1;
-    constexpr int N_HALO = T_NPOS - TT_W * TT_H;            // 208
-    __shared__ float sx[3][3][T_NPOS];                       // [channel][synth*m | src*m | tgt*m]
-    __shared__ float sg[9][T_NQ];
-    __shared__ float sgate[T_NQ];
+    constexpr int PPT = TILE_PPT, NE = TILE_NE;
+    __shared__ float sx[3][3][TILE_NPOS];                       // [channel][synth*m | src*m | tgt*m]
+    __shared__ float sg[9][TILE_NQ];
+    __shared__ float sgate[TILE_NQ];
     __shared__ float sgeo[12];
     __shared__ double sgeo_d[12];                            // the same 12 numbers from the same inputs in double (geometric term only)
-    __shared__ float red[TNT / 64];
+    __shared__ float red[TILE_NT / 64];
     const bool geo_on = (terms & E2E_TERM_GEOMETRIC) != 0, auto_on = (terms & E2E_TERM_AUTO_MASKING) != 0;
-    const int b = blockIdx.z, tx0 = blockIdx.x * TT_W, ty0 = blockIdx.y * TT_H;
-    const int tid = threadIdx.y * TT_W + threadIdx.x;
+    const int b = blockIdx.z, tx0 = blockIdx.x * TILE_W, ty0 = blockIdx.y * TILE_H;
+    const int tid = threadIdx.y * TILE_W + threadIdx.x;
     const int64_t N = (int64_t)H * W;
     const float* dep = depth + b * N;
     const float* sb = src + b * ss.sb;
@@ -189,15 +182,15 @@ __global__ __launch_bounds__(TNT) void k_warp_photo_terms(
             ly = threadIdx.y * PPT + e + 2;
             lx = threadIdx.x + 2;
         } else {
-            const int h = (tid < N_HALO) ? tid : 0;
-            if (h < 2 * TX_W) { ly = h / TX_W; lx = h % TX_W; }
-            else if (h < 4 * TX_W) { ly = TX_H - 2 + (h - 2 * TX_W) / TX_W; lx = (h - 2 * TX_W) % TX_W; }
-            else { const int k4 = h - 4 * TX_W; ly = 2 + (k4 >> 2); const int k = k4 & 3; lx = (k < 2) ? k : TX_W - 4 + k; }
+            const int h = (tid < TILE_NHALO) ? tid : 0;
+            if (h < 2 * TILE_XW) { ly = h / TILE_XW; lx = h % TILE_XW; }
+            else if (h < 4 * TILE_XW) { ly = TILE_XH - 2 + (h - 2 * TILE_XW) / TILE_XW; lx = (h - 2 * TILE_XW) % TILE_XW; }
+            else { const int k4 = h - 4 * TILE_XW; ly = 2 + (k4 >> 2); const int k = k4 & 3; lx = (k < 2) ? k : TILE_XW - 4 + k; }
         }
         const int gy = ty0 + ly - 2, gx = tx0 + lx - 2;
         const bool dom = gx >= -1 && gx <= W && gy >= -1 && gy <= H;
         // reflect, then clamp so that even unused slots address valid memory (their result is zeroed)
-        const int qx = min(max(reflect1(gx, W), 0), W - 1), qy = min(max(reflect1(gy, H), 0), H - 1);
+        const int qx = tile_clamped(gx, W), qy = tile_clamped(gy, H);
         const float d = dep[qy * W + qx];
         float tv[3], iv[3];
 #pragma unroll
@@ -224,8 +217,8 @@ __global__ __launch_bounds__(TNT) void k_warp_photo_terms(
         }
         const float w00 = (1.f - s.tx) * (1.f - s.ty), w01 = s.tx * (1.f - s.ty), w10 = (1.f - s.tx) * s.ty, w11 = s.tx * s.ty;
         const float mm = dom ? m : 0.f;               // outside the reflect domain: zeros
-        if (e < PPT || tid < N_HALO) {
-            const int lpos = ly * TX_W + lx;
+        if (e < PPT || tid < TILE_NHALO) {
+            const int lpos = ly * TILE_XW + lx;
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
                 const float sv = fmaf(nw[c], w00, fmaf(ne[c], w01, fmaf(sw[c], w10, se[c] * w11)));
@@ -250,11 +243,11 @@ __global__ __launch_bounds__(TNT) void k_warp_photo_terms(
     const float gup = w_photo * kmean * (0.85f / 3.f);      // upstream gradient on every ssim_c(q) that survives the minimum
     float lsum = 0.f;
 #pragma unroll 1
-    for (int i = tid; i < T_NQ; i += TNT) {
-        const int ly = i / TG_W, lx = i - ly * TG_W;
+    for (int i = tid; i < TILE_NQ; i += TILE_NT) {
+        const int ly = i / TILE_GW, lx = i - ly * TILE_GW;
         const int qx = tx0 + lx - 1, qy = ty0 + ly - 1;
         const bool in = qx >= 0 && qx < W && qy >= 0 && qy < H;
-        const bool own = lx >= 1 && lx <= TT_W && ly >= 1 && ly <= TT_H;
+        const bool own = lx >= 1 && lx <= TILE_W && ly >= 1 && ly <= TILE_H;
         float Rq = 0.f, Aq = 0.f, G[9];
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
@@ -263,7 +256,7 @@ __global__ __launch_bounds__(TNT) void k_warp_photo_terms(
             for (int r = 0; r < 3; ++r)
 #pragma unroll
                 for (int k = 0; k < 3; ++k) {
-                    const int j = (ly + r) * TX_W + lx + k;
+                    const int j = (ly + r) * TILE_XW + lx + k;
                     const float x = sx[c][0][j], y = sx[c][2][j];
                     s_x += x; s_y += y;
                     s_xx = fmaf(x, x, s_xx); s_yy = fmaf(y, y, s_yy); s_xy = fmaf(x, y, s_xy);
@@ -272,7 +265,7 @@ __global__ __launch_bounds__(TNT) void k_warp_photo_terms(
                         s_a += a; s_aa = fmaf(a, a, s_aa); s_ay = fmaf(a, y, s_ay);
                     }
                 }
-            const int jc = (ly + 1) * TX_W + lx + 1;
+            const int jc = (ly + 1) * TILE_XW + lx + 1;
             const float k9 = 1.f / 9.f, C1 = 1e-4f, C2 = 9e-4f;
             const float MY = s_y * k9, EYY = s_yy * k9, MYY = MY * MY, SIGY = EYY - MYY;
             {
@@ -322,7 +315,7 @@ __global__ __launch_bounds__(TNT) void k_warp_photo_terms(
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             const int qx = px + k - 1;
-            wx[k] = (qx < 0 || qx >= W) ? 0.f : (((qx == 0 && px == 1) || (qx == W - 1 && px == W - 2)) ? 2.f : 1.f);
+            wx[k] = (qx < 0 || qx >= W) ? 0.f : refl_mult(px, qx, W);
         }
         float gsy[PPT][3];     // d loss / d synth per own pixel and channel
 #pragma unroll
@@ -332,7 +325,7 @@ __global__ __launch_bounds__(TNT) void k_warp_photo_terms(
             for (int j = 0; j < 3; ++j)
 #pragma unroll
                 for (int r = 0; r < PPT + 2; ++r) {
-                    const float* row = &sg[c * 3 + j][(ly0 + r) * TG_W + lxc];
+                    const float* row = &sg[c * 3 + j][(ly0 + r) * TILE_GW + lxc];
                     rs[j][r] = fmaf(row[0], wx[0], fmaf(row[1], wx[1], row[2] * wx[2]));
                 }
 #pragma unroll
@@ -342,17 +335,17 @@ __global__ __launch_bounds__(TNT) void k_warp_photo_terms(
 #pragma unroll
                 for (int k = 0; k < 3; ++k) {
                     const int qy = py + k - 1;
-                    const float wy = (qy < 0 || qy >= H) ? 0.f : (((qy == 0 && py == 1) || (qy == H - 1 && py == H - 2)) ? 2.f : 1.f);
+                    const float wy = (qy < 0 || qy >= H) ? 0.f : refl_mult(py, qy, H);
                     a1 = fmaf(rs[0][e + k], wy, a1);
                     a2 = fmaf(rs[1][e + k], wy, a2);
                     a3 = fmaf(rs[2][e + k], wy, a3);
                 }
-                const int jc = (ly0 + e + 2) * TX_W + lxc + 2;
+                const int jc = (ly0 + e + 2) * TILE_XW + lxc + 2;
                 const float cx = sx[c][0][jc], cy = sx[c][2][jc];
                 float g = (a1 + 2.f * cx * a2 + cy * a3) * (1.f / 9.f);
                 const float df = cy - cx;
-                const float sgn = (df > 0.f) ? 1.f : ((df < 0.f) ? -1.f : 0.f);
-                const float own_gate = sgate[(ly0 + e + 1) * TG_W + lxc + 1];
+                const float sgn = tile_sign(df);
+                const float own_gate = sgate[(ly0 + e + 1) * TILE_GW + lxc + 1];
                 g = fmaf(-w_photo * kmean * (0.15f / 3.f) * own_gate, sgn, g);
                 gsy[e][c] = g * kp[e].m;                             // d/d synth = d/dx * mask
             }
@@ -394,7 +387,7 @@ __global__ __launch_bounds__(TNT) void k_warp_photo_terms(
                 const bool valid = kq.p.inb != 0.f;
                 if (valid) gsum += fminf(fmaxf(r, 0.f), 1.f);
                 if (valid && geo_live && r >= 0.f && r <= 1.f) {
-                    const float sg1 = (dif > 0.f) ? 1.f : ((dif < 0.f) ? -1.f : 0.f);
+                    const float sg1 = tile_sign(dif);
                     const float is = 1.f / sum;
                     const float g_wd = ggeo * (sg1 - r) * is, g_id = ggeo * (-sg1 - r) * is;
                     if (C2 >= 1e-3) gd_direct = g_wd * kq.p.r2;
@@ -498,8 +491,6 @@ __device__ __forceinline__ float sm_edge(const float* __restrict__ img, e2e_stri
     return expf(-s * (1.f / 3.f));
 }
 
-__device__ __forceinline__ float sm_sign(float e) { return (e > 0.f) ? 1.f : ((e < 0.f) ? -1.f : 0.f); }
-
 // gn = d loss / d (normalised disparity) per pixel; partial sums of the loss and of sum_p gn[p] * disp[p] (the mean's own term)
 __global__ __launch_bounds__(TNT) void k_sm_grad(const float* __restrict__ disp, const float* __restrict__ img, e2e_strides is, int H, int W,
                                                   const float* __restrict__ part_m, float* __restrict__ gn, float* __restrict__ part_ls) {
@@ -516,15 +507,15 @@ __global__ __launch_bounds__(TNT) void k_sm_grad(const float* __restrict__ disp,
         if (x < W - 1) {
             const float e = n0 - disp[i + 1] * inv, w = sm_edge(img, is, y, x, y, x + 1) * kx;
             ls = fmaf(fabsf(e), w, ls);
-            g = fmaf(sm_sign(e), w, g);
+            g = fmaf(tile_sign(e), w, g);
         }
-        if (x > 0) g = fmaf(-sm_sign(disp[i - 1] * inv - n0), sm_edge(img, is, y, x - 1, y, x) * kx, g);
+        if (x > 0) g = fmaf(-tile_sign(disp[i - 1] * inv - n0), sm_edge(img, is, y, x - 1, y, x) * kx, g);
         if (y < H - 1) {
             const float e = n0 - disp[i + W] * inv, w = sm_edge(img, is, y, x, y + 1, x) * ky;
             ls = fmaf(fabsf(e), w, ls);
-            g = fmaf(sm_sign(e), w, g);
+            g = fmaf(tile_sign(e), w, g);
         }
-        if (y > 0) g = fmaf(-sm_sign(disp[i - W] * inv - n0), sm_edge(img, is, y - 1, x, y, x) * ky, g);
+        if (y > 0) g = fmaf(-tile_sign(disp[i - W] * inv - n0), sm_edge(img, is, y - 1, x, y, x) * ky, g);
         gn[i] = g;
         ss = fmaf(g, d0, ss);
     }
@@ -552,7 +543,7 @@ __global__ __launch_bounds__(TNT) void k_sm_apply(const float* __restrict__ gn, 
 
 extern "C" {
 
-static int terms_nblk(int B, int H, int W) { return e2e_ceil_div(W, TT_W) * e2e_ceil_div(H, TT_H) * B; }
+static int terms_nblk(int B, int H, int W) { return e2e_ceil_div(W, TILE_W) * e2e_ceil_div(H, TILE_H) * B; }
 
 int64_t e2e_warp_photo_terms_lossgrad_workspace_floats(int B, int H, int W) {
     if (B <= 0 || H <= 0 || W <= 0) return 0;
@@ -564,15 +555,10 @@ int e2e_warp_photo_terms_lossgrad(const float* depth_tgt, const float* depth_src
                                   int reg_kind, const float* reg_init_tgt, const float* reg_init_src, int terms, const float* tie_noise,
                                   float w_photo, float w_reg, float w_geometric, float* loss_out, float* g_depth_tgt, float* g_depth_src,
                                   float* workspace, int B, int H, int W, void* stream) {
-    E2E_REQUIRE(B > 0 && H > 1 && W > 1 && (int64_t)B * H * W * 3 < (1ll << 31), E2E_ERR_ARG,
-                "e2e_warp_photo_terms_lossgrad: bad dims B=%d H=%d W=%d", B, H, W);
-    E2E_REQUIRE(depth_tgt && src && tgt && K && inv_K && T && g_depth_tgt && workspace && loss_out, E2E_ERR_ARG,
-                "e2e_warp_photo_terms_lossgrad: null pointer");
-    E2E_REQUIRE(padding_mode == E2E_PADDING_BORDER || padding_mode == E2E_PADDING_ZEROS, E2E_ERR_ARG,
-                "e2e_warp_photo_terms_lossgrad: padding_mode %d not supported (zeros|border)", padding_mode);
-    E2E_REQUIRE(reg_kind >= 0 && reg_kind <= 2, E2E_ERR_ARG, "e2e_warp_photo_terms_lossgrad: reg_kind %d (0 none, 1 l1, 2 l2)", reg_kind);
-    E2E_REQUIRE(!reg_kind || (reg_init_tgt && reg_init_src && depth_src && g_depth_src), E2E_ERR_ARG,
-                "e2e_warp_photo_terms_lossgrad: regulariser buffers missing");
+    if (const int rc = lossgrad_check_args("e2e_warp_photo_terms_lossgrad", B, H, W,
+                                           depth_tgt && src && tgt && K && inv_K && T && g_depth_tgt && workspace && loss_out, padding_mode,
+                                           reg_kind, reg_init_tgt && reg_init_src && depth_src && g_depth_src))
+        return rc;
     const int known = E2E_TERM_GEOMETRIC | E2E_TERM_AUTO_MASKING | E2E_TERM_MIN_REPROJECTION;
     E2E_REQUIRE((terms & ~known) == 0, E2E_ERR_ARG, "e2e_warp_photo_terms_lossgrad: unknown term bits 0x%x", terms);
     const int geo_on = (terms & E2E_TERM_GEOMETRIC) ? 1 : 0;
@@ -581,7 +567,7 @@ int e2e_warp_photo_terms_lossgrad(const float* depth_tgt, const float* depth_src
     const bool noisy = (terms & E2E_TERM_AUTO_MASKING) && (terms & E2E_TERM_MIN_REPROJECTION);
     const float* noise = noisy ? tie_noise : nullptr;
     hipStream_t st = (hipStream_t)stream;
-    const dim3 g(e2e_ceil_div(W, TT_W), e2e_ceil_div(H, TT_H), B);
+    const dim3 g(e2e_ceil_div(W, TILE_W), e2e_ceil_div(H, TILE_H), B);
     const int nblk = g.x * g.y * g.z;
     int* count = (int*)(workspace + 3ll * nblk);
     if (geo_on) {
@@ -591,8 +577,8 @@ int e2e_warp_photo_terms_lossgrad(const float* depth_tgt, const float* depth_src
     }
 #define TL_ARGS depth_tgt, depth_src, src, ss, tgt, ts, K, inv_K, T, use_mask, reg_kind, reg_init_tgt, reg_init_src, terms, noise, w_photo, w_reg, \
                 w_geometric, count, g_depth_tgt, g_depth_src, workspace, B, H, W
-    if (padding_mode == E2E_PADDING_BORDER) hipLaunchKernelGGL((k_warp_photo_terms<E2E_PAD_BORDER>), g, dim3(TT_W, 8), 0, st, TL_ARGS);
-    else hipLaunchKernelGGL((k_warp_photo_terms<E2E_PAD_ZEROS>), g, dim3(TT_W, 8), 0, st, TL_ARGS);
+    if (padding_mode == E2E_PADDING_BORDER) hipLaunchKernelGGL((k_warp_photo_terms<E2E_PAD_BORDER>), g, dim3(TILE_W, 8), 0, st, TL_ARGS);
+    else hipLaunchKernelGGL((k_warp_photo_terms<E2E_PAD_ZEROS>), g, dim3(TILE_W, 8), 0, st, TL_ARGS);
 #undef TL_ARGS
     E2E_LAUNCH_CHECK("e2e_warp_photo_terms_lossgrad");
     hipLaunchKernelGGL(k_reduce_terms, dim3(1), dim3(TNT), 0, st, workspace, nblk, count, geo_on, 1.0 / ((double)B * H * W), loss_out);

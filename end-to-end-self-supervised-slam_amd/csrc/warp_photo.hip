@@ -253,11 +253,6 @@ __device__ __forceinline__ void ssim_partials(const Stats& s, float g, float& G1
     G3 = gS * (2.f * A1 * inv);
 }
 
-// multiplicity with which output pixel q's reflect-padded 3-window sees input pixel p (|p-q| <= 1)
-__device__ __forceinline__ float refl_mult(int p, int q, int n) {
-    return ((q == 0 && p == 1) || (q == n - 1 && p == n - 2)) ? 2.f : 1.f;
-}
-
 // ---------------------------------------------------------------------------------------------
 // modular photometric forward / backward: C channels, one LDS plane pair per channel pass
 // SSIM.forward losses.py:23-37, photometric_loss losses.py:97-117

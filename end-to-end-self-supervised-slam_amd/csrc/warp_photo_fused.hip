@@ -7,7 +7,7 @@
 // frame: synth / valid / the loss map never touch HBM.  Algorithmic traffic per pixel: depth 4 B +
 // src 12 B (gather) + tgt 12 B in, d/d(depth) 4 B out (+ regulariser: 12 B in, 4 B out).
 //
-// Workgroup = 256 threads = 32x16 pixel tile, two pixels per thread.
+// Workgroup = 256 threads = 32x16 pixel tile, two pixels per thread (constants, shared with loss_terms.hip: lossgrad_tile.h).
 //   phase 1  warp every position of the tile + 2-px halo (36x20): {x,y} = {synth*m, tgt*m} -> LDS as
 //            float2 (one ds_read_b64 serves both SSIM operands; window sums run on v_pk_*_f32);
 //            the thread keeps its own two pixels' taps / projection in registers for the adjoint.
@@ -22,15 +22,9 @@
 // (one kernel per step).
 // fp contraction is ON here (FMA): tolerance for this path is 1e-4 relative (BASELINE.json); the
 // bit-exact index kernels live in other files with contraction off.
-#include <stdlib.h>
-
 #include "e2e_common.h"
 #pragma clang fp contract(fast)
-
-#define LT_W 32
-#define LX_W (LT_W + 4)
-#define LG_W (LT_W + 2)
-#define LNT 256
+#include "lossgrad_tile.h"
 
 typedef float f2 __attribute__((ext_vector_type(2)));
 
@@ -83,24 +77,21 @@ struct Taps {          // what the adjoint needs about one of the thread's own p
     float m;                // validity mask (1 when use_mask == 0)
 };
 
-// PPT = image rows per thread (1 or 2).  Tile = 32 x (8*PPT) pixels, 256 threads.
-template <int PAD, bool NHWC, int PPT>
-__global__ __launch_bounds__(LNT) void k_warp_photo_lossgrad(
+template <int PAD, bool NHWC>
+__global__ __launch_bounds__(TILE_NT) void k_warp_photo_lossgrad(
     const float* __restrict__ depth, const float* __restrict__ src, e2e_strides ss,
     const float* __restrict__ tgt, e2e_strides ts, const float* __restrict__ K,
     const float* __restrict__ invK, const float* __restrict__ T, int use_mask, int reg_kind,
     const float* __restrict__ ri_t, const float* __restrict__ ri_s, const float* __restrict__ d_s,
     float w_photo, float w_reg, float* __restrict__ g_dt, float* __restrict__ g_ds,
     float* __restrict__ partials, int B, int H, int W, HostGeo hg, Chain chain) {
-    constexpr int LT_H = 8 * PPT, LX_H = LT_H + 4, LG_H = LT_H + 2;
-    constexpr int N_HALO = LX_W * LX_H - LT_W * LT_H;      // 176 (PPT 1) / 208 (PPT 2)
-    constexpr int NE = PPT + 1;                            // warp evaluations per thread
-    __shared__ f2 sxy[3][LX_H * LX_W];
-    __shared__ float sg[9][LG_H * LG_W];
+    constexpr int PPT = TILE_PPT, NE = TILE_NE;
+    __shared__ f2 sxy[3][TILE_NPOS];
+    __shared__ float sg[9][TILE_NQ];
     __shared__ float sgeo[12];
-    __shared__ float red[LNT / 64];
-    const int b = blockIdx.z, tx0 = blockIdx.x * LT_W, ty0 = blockIdx.y * LT_H;
-    const int tid = threadIdx.y * LT_W + threadIdx.x;
+    __shared__ float red[TILE_NT / 64];
+    const int b = blockIdx.z, tx0 = blockIdx.x * TILE_W, ty0 = blockIdx.y * TILE_H;
+    const int tid = threadIdx.y * TILE_W + threadIdx.x;
     const int64_t N = (int64_t)H * W;
     const float* dep = depth + b * N;
     const float* sb = src + b * ss.sb;
@@ -134,10 +125,10 @@ __global__ __launch_bounds__(LNT) void k_warp_photo_lossgrad(
             ly = threadIdx.y * PPT + e + 2;
             lx = threadIdx.x + 2;
         } else {
-            const int h = (tid < N_HALO) ? tid : 0;
-            if (h < 2 * LX_W) { ly = h / LX_W; lx = h % LX_W; }
-            else if (h < 4 * LX_W) { ly = LX_H - 2 + (h - 2 * LX_W) / LX_W; lx = (h - 2 * LX_W) % LX_W; }
-            else { const int k4 = h - 4 * LX_W; ly = 2 + (k4 >> 2); const int k = k4 & 3; lx = (k < 2) ? k : LX_W - 4 + k; }
+            const int h = (tid < TILE_NHALO) ? tid : 0;
+            if (h < 2 * TILE_XW) { ly = h / TILE_XW; lx = h % TILE_XW; }
+            else if (h < 4 * TILE_XW) { ly = TILE_XH - 2 + (h - 2 * TILE_XW) / TILE_XW; lx = (h - 2 * TILE_XW) % TILE_XW; }
+            else { const int k4 = h - 4 * TILE_XW; ly = 2 + (k4 >> 2); const int k = k4 & 3; lx = (k < 2) ? k : TILE_XW - 4 + k; }
         }
         const int gy = ty0 + ly - 2, gx = tx0 + lx - 2;
         dom[e] = gx >= -1 && gx <= W && gy >= -1 && gy <= H;
@@ -150,9 +141,9 @@ __global__ __launch_bounds__(LNT) void k_warp_photo_lossgrad(
             }
         }
         // reflect, then clamp so that even unused slots address valid memory (their result is zeroed)
-        qxs[e] = min(max(reflect1(gx, W), 0), W - 1);
-        qys[e] = min(max(reflect1(gy, H), 0), H - 1);
-        lpos[e] = ly * LX_W + lx;
+        qxs[e] = tile_clamped(gx, W);
+        qys[e] = tile_clamped(gy, H);
+        lpos[e] = ly * TILE_XW + lx;
         dval[e] = dep[qys[e] * W + qxs[e]];
         if (NHWC) {
             const float* tp = tb + (qys[e] * W + qxs[e]) * 3;
@@ -243,7 +234,7 @@ __global__ __launch_bounds__(LNT) void k_warp_photo_lossgrad(
         const Taps& k = kp[e];
         const float w00 = (1.f - k.tx) * (1.f - k.ty), w01 = k.tx * (1.f - k.ty), w10 = (1.f - k.tx) * k.ty, w11 = k.tx * k.ty;
         const float m = dom[e] ? k.m : 0.f;           // outside the reflect domain: zeros
-        if (e < PPT || tid < N_HALO) {
+        if (e < PPT || tid < TILE_NHALO) {
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
                 const float sv = fmaf(k.nw[c], w00, fmaf(k.ne[c], w01, fmaf(k.sw[c], w10, k.se[c] * w11)));
@@ -262,28 +253,28 @@ __global__ __launch_bounds__(LNT) void k_warp_photo_lossgrad(
         // rows are read from LDS once per channel and their horizontal sums shared by the strip's q's; the q's are then
         // processed in vertical PAIRS so that the whole SSIM / gradient formula runs on v_pk_*_f32 (the kernel is
         // VALU-issue bound: profiles/r01_warp_photo_lossgrad_history.md).  Threads past the last strip skip the phase.
-        constexpr int RPS = 2 * PPT;                               // 4 (PPT 2) / 2 (PPT 1)
-        constexpr int NSTRIP = (LG_H + RPS - 1) / RPS;             // 5
-        constexpr int NUNIT = 3 * NSTRIP * LG_W;                   // (channel, strip, column) units: 510 -> 2 per thread
-        constexpr int UPT = (NUNIT + LNT - 1) / LNT;
+        constexpr int RPS = 2 * PPT;                               // 4
+        constexpr int NSTRIP = (TILE_GH + RPS - 1) / RPS;             // 5
+        constexpr int NUNIT = 3 * NSTRIP * TILE_GW;                   // (channel, strip, column) units: 510 -> 2 per thread
+        constexpr int UPT = (NUNIT + TILE_NT - 1) / TILE_NT;
         f2 lacc = (f2){0.f, 0.f};
 #pragma unroll 1
         for (int uu = 0; uu < UPT; ++uu) {
-            const int unit = tid + uu * LNT;
+            const int unit = tid + uu * TILE_NT;
             if (unit >= NUNIT) break;
-            const int c = unit / (NSTRIP * LG_W), rem = unit - c * (NSTRIP * LG_W);
-            const int strip = rem / LG_W, lx = rem - strip * LG_W;
+            const int c = unit / (NSTRIP * TILE_GW), rem = unit - c * (NSTRIP * TILE_GW);
+            const int strip = rem / TILE_GW, lx = rem - strip * TILE_GW;
             const int ly0 = strip * RPS;
             const int qx = tx0 + lx - 1;
             const bool col_ok = qx >= 0 && qx < W;
-            const bool own_col = lx >= 1 && lx <= LT_W;
+            const bool own_col = lx >= 1 && lx <= TILE_W;
             {
                 f2 hs1[RPS + 2], hs2[RPS + 2];
                 float hxy[RPS + 2], adf[RPS + 2];
 #pragma unroll
                 for (int r = 0; r < RPS + 2; ++r) {
-                    const int row = min(ly0 + r, LX_H - 1);        // rows past the region are never combined into a valid q
-                    const f2* w = &sxy[c][row * LX_W + lx];
+                    const int row = min(ly0 + r, TILE_XH - 1);        // rows past the region are never combined into a valid q
+                    const f2* w = &sxy[c][row * TILE_XW + lx];
                     const f2 e0 = w[0], e1 = w[1], e2 = w[2];
                     hs1[r] = e0 + e1 + e2;
                     hs2[r] = e0 * e0 + e1 * e1 + e2 * e2;
@@ -294,8 +285,8 @@ __global__ __launch_bounds__(LNT) void k_warp_photo_lossgrad(
                 for (int jp = 0; jp < RPS; jp += 2) {              // q rows (ly0+jp, ly0+jp+1) in the two halves of every f2
                     const int lya = ly0 + jp, lyb = lya + 1;
                     const int qya = ty0 + lya - 1, qyb = qya + 1;
-                    const bool in_a = col_ok && lya < LG_H && qya >= 0 && qya < H;
-                    const bool in_b = col_ok && lyb < LG_H && qyb >= 0 && qyb < H;
+                    const bool in_a = col_ok && lya < TILE_GH && qya >= 0 && qya < H;
+                    const bool in_b = col_ok && lyb < TILE_GH && qyb >= 0 && qyb < H;
                     const f2 m1 = hs1[jp + 1] + hs1[jp + 2], m2 = hs2[jp + 1] + hs2[jp + 2];
                     const float mxy = hxy[jp + 1] + hxy[jp + 2];
                     const f2 s1a = m1 + hs1[jp], s1b = m1 + hs1[jp + 3];
@@ -314,8 +305,8 @@ __global__ __launch_bounds__(LNT) void k_warp_photo_lossgrad(
                     const f2 S = A1 * A2 * INV;
                     const f2 TT = (f2){0.5f, 0.5f} - (f2){0.5f, 0.5f} * S;          // (1 - S)/2
                     const bool act_a = TT.x >= 0.f && TT.x <= 1.f, act_b = TT.y >= 0.f && TT.y <= 1.f;
-                    const bool own_a = in_a && own_col && lya >= 1 && lya <= LT_H;
-                    const bool own_b = in_b && own_col && lyb >= 1 && lyb <= LT_H;
+                    const bool own_a = in_a && own_col && lya >= 1 && lya <= TILE_H;
+                    const bool own_b = in_b && own_col && lyb >= 1 && lyb <= TILE_H;
                     const f2 lv = (f2){0.85f / 3.f, 0.85f / 3.f} * (f2){fminf(fmaxf(TT.x, 0.f), 1.f), fminf(fmaxf(TT.y, 0.f), 1.f)} +
                                   (f2){0.15f / 3.f, 0.15f / 3.f} * (f2){adf[jp + 1], adf[jp + 2]};
                     lacc += (f2){own_a ? lv.x : 0.f, own_b ? lv.y : 0.f};
@@ -324,14 +315,14 @@ __global__ __launch_bounds__(LNT) void k_warp_photo_lossgrad(
                     const f2 G1 = two * GI * (MY * (A2 - A1) - S * MX * (B2 - B1));
                     const f2 G2 = -(GI * S) * B1;
                     const f2 G3 = two * GI * A1;
-                    if (lya < LG_H) {
-                        const int i = lya * LG_W + lx;
+                    if (lya < TILE_GH) {
+                        const int i = lya * TILE_GW + lx;
                         sg[c * 3 + 0][i] = in_a ? G1.x : 0.f;
                         sg[c * 3 + 1][i] = in_a ? G2.x : 0.f;
                         sg[c * 3 + 2][i] = in_a ? G3.x : 0.f;
                     }
-                    if (lyb < LG_H) {
-                        const int i = lyb * LG_W + lx;
+                    if (lyb < TILE_GH) {
+                        const int i = lyb * TILE_GW + lx;
                         sg[c * 3 + 0][i] = in_b ? G1.y : 0.f;
                         sg[c * 3 + 1][i] = in_b ? G2.y : 0.f;
                         sg[c * 3 + 2][i] = in_b ? G3.y : 0.f;
@@ -353,7 +344,7 @@ __global__ __launch_bounds__(LNT) void k_warp_photo_lossgrad(
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             const int qx = px + k - 1;
-            wx[k] = (qx < 0 || qx >= W) ? 0.f : (((qx == 0 && px == 1) || (qx == W - 1 && px == W - 2)) ? 2.f : 1.f);
+            wx[k] = (qx < 0 || qx >= W) ? 0.f : refl_mult(px, qx, W);
         }
         float gsy[PPT][3];     // d loss / d synth per own pixel and channel
 #pragma unroll
@@ -363,7 +354,7 @@ __global__ __launch_bounds__(LNT) void k_warp_photo_lossgrad(
             for (int j = 0; j < 3; ++j)
 #pragma unroll
                 for (int r = 0; r < PPT + 2; ++r) {
-                    const float* row = &sg[c * 3 + j][(ly0 + r) * LG_W + lxc];
+                    const float* row = &sg[c * 3 + j][(ly0 + r) * TILE_GW + lxc];
                     rs[j][r] = fmaf(row[0], wx[0], fmaf(row[1], wx[1], row[2] * wx[2]));
                 }
 #pragma unroll
@@ -373,15 +364,15 @@ __global__ __launch_bounds__(LNT) void k_warp_photo_lossgrad(
 #pragma unroll
                 for (int k = 0; k < 3; ++k) {
                     const int qy = py + k - 1;
-                    const float wy = (qy < 0 || qy >= H) ? 0.f : (((qy == 0 && py == 1) || (qy == H - 1 && py == H - 2)) ? 2.f : 1.f);
+                    const float wy = (qy < 0 || qy >= H) ? 0.f : refl_mult(py, qy, H);
                     a1 = fmaf(rs[0][e + k], wy, a1);
                     a2 = fmaf(rs[1][e + k], wy, a2);
                     a3 = fmaf(rs[2][e + k], wy, a3);
                 }
-                const f2 ce = sxy[c][(ly0 + e + 2) * LX_W + lxc + 2];
+                const f2 ce = sxy[c][(ly0 + e + 2) * TILE_XW + lxc + 2];
                 float g = (a1 + 2.f * ce.x * a2 + ce.y * a3) * (1.f / 9.f);
                 const float df = ce.y - ce.x;
-                const float sgn = (df > 0.f) ? 1.f : ((df < 0.f) ? -1.f : 0.f);
+                const float sgn = tile_sign(df);
                 g = fmaf(-w_photo * kmean * (0.15f / 3.f), sgn, g);
                 gsy[e][c] = g * kp[e].m;                             // d/d synth = d/dx * mask
             }
@@ -486,20 +477,19 @@ __global__ __launch_bounds__(RED_T) void k_reduce_partials2(const float* __restr
     if (tid < 2) out[tid] = (float)((((sh[tid][0] + sh[tid][1]) + sh[tid][2]) + sh[tid][3]) * scale);
 }
 
-extern "C" int64_t e2e_warp_photo_lossgrad_workspace_floats(int B, int H, int W);
+// floats ahead of the chained mode's slot sets (8-byte aligned): 2 partial sums per workgroup.  The 8 is historical -- the size was
+// set for 32x8 tiles, twice the workgroups of today's 32x16 -- and stays: callers allocate by it and chain_area() addresses by it.
+static int64_t lossgrad_parts(int B, int H, int W) { return (2ll * e2e_ceil_div(W, TILE_W) * e2e_ceil_div(H, 8) * B + 1) / 2 * 2; }
 
 extern "C" {
 
 int64_t e2e_warp_photo_lossgrad_workspace_floats(int B, int H, int W) {
     if (B <= 0 || H <= 0 || W <= 0) return 0;
-    // 2 partial sums per workgroup of the finest tiling (32x8), then (8-byte aligned) the slot sets of the chained mode
-    const int64_t parts = (2ll * e2e_ceil_div(W, LT_W) * e2e_ceil_div(H, 8) * B + 1) / 2 * 2;
-    return parts + 2ll * CHAIN_SETS * CHAIN_SET_U64;
+    return lossgrad_parts(B, H, W) + 2ll * CHAIN_SETS * CHAIN_SET_U64;
 }
 
 static unsigned long long* chain_area(float* workspace, int B, int H, int W) {
-    const int64_t parts = (2ll * e2e_ceil_div(W, LT_W) * e2e_ceil_div(H, 8) * B + 1) / 2 * 2;
-    return (unsigned long long*)(workspace + parts);
+    return (unsigned long long*)(workspace + lossgrad_parts(B, H, W));
 }
 
 static int lossgrad_impl(const float* depth_tgt, const float* src, e2e_strides ss, const float* tgt, e2e_strides ts,
@@ -507,30 +497,18 @@ static int lossgrad_impl(const float* depth_tgt, const float* src, e2e_strides s
                          int reg_kind, const float* reg_init_tgt, const float* reg_init_src, const float* depth_src,
                          float w_photo, float w_reg, float* loss_out, float* g_depth_tgt, float* g_depth_src,
                          float* workspace, int B, int H, int W, void* stream, Chain chain = Chain{}) {
-    E2E_REQUIRE(B > 0 && H > 1 && W > 1 && (int64_t)B * H * W * 3 < (1ll << 31), E2E_ERR_ARG,
-                "e2e_warp_photo_lossgrad: bad dims B=%d H=%d W=%d", B, H, W);
-    E2E_REQUIRE(depth_tgt && src && tgt && (hg.use || (K && inv_K && T)) && g_depth_tgt && workspace, E2E_ERR_ARG,
-                "e2e_warp_photo_lossgrad: null pointer");
-    E2E_REQUIRE(padding_mode == E2E_PADDING_BORDER || padding_mode == E2E_PADDING_ZEROS, E2E_ERR_ARG,
-                "e2e_warp_photo_lossgrad: padding_mode %d not supported (zeros|border)", padding_mode);
-    E2E_REQUIRE(reg_kind >= 0 && reg_kind <= 2, E2E_ERR_ARG, "e2e_warp_photo_lossgrad: reg_kind %d (0 none, 1 l1, 2 l2)", reg_kind);
-    E2E_REQUIRE(!reg_kind || (reg_init_tgt && reg_init_src && depth_src && g_depth_src), E2E_ERR_ARG,
-                "e2e_warp_photo_lossgrad: regulariser buffers missing");
-    // two rows per thread (32x16 tiles) measured faster than one row (32x8) at both 1 and 8 pairs per launch
-    // (the one-row variant stays compiled for the A/B in profiles/r01_warp_photo_lossgrad_history.md; no per-launch environment lookup)
-    static const int ppt = [] { const char* ev = getenv("E2E_LOSSGRAD_PPT"); return (ev && ev[0] == '1') ? 1 : 2; }();
-    const dim3 g(e2e_ceil_div(W, LT_W), e2e_ceil_div(H, 8 * ppt), B);
+    if (const int rc = lossgrad_check_args("e2e_warp_photo_lossgrad", B, H, W,
+                                           depth_tgt && src && tgt && (hg.use || (K && inv_K && T)) && g_depth_tgt && workspace, padding_mode,
+                                           reg_kind, reg_init_tgt && reg_init_src && depth_src && g_depth_src))
+        return rc;
+    const dim3 g(e2e_ceil_div(W, TILE_W), e2e_ceil_div(H, TILE_H), B);
     const int nblk = g.x * g.y * g.z;
     // channels-last frames (the reference's memory layout) take the 12-byte-per-tap path
     const bool nhwc = ss.sc == 1 && ss.sw == 3 && ss.sh == 3ll * W && ts.sc == 1 && ts.sw == 3 && ts.sh == 3ll * W;
     hipStream_t st = (hipStream_t)stream;
 #define LG_ARGS depth_tgt, src, ss, tgt, ts, K, inv_K, T, use_mask, reg_kind, reg_init_tgt, reg_init_src, depth_src, w_photo, w_reg, \
                 g_depth_tgt, g_depth_src, workspace, B, H, W, hg, chain
-#define LG_LAUNCH(PADV, NH)                                                                                              \
-    do {                                                                                                                 \
-        if (ppt == 2) hipLaunchKernelGGL((k_warp_photo_lossgrad<PADV, NH, 2>), g, dim3(LT_W, 8), 0, st, LG_ARGS);        \
-        else hipLaunchKernelGGL((k_warp_photo_lossgrad<PADV, NH, 1>), g, dim3(LT_W, 8), 0, st, LG_ARGS);                 \
-    } while (0)
+#define LG_LAUNCH(PADV, NH) hipLaunchKernelGGL((k_warp_photo_lossgrad<PADV, NH>), g, dim3(TILE_W, 8), 0, st, LG_ARGS)
     if (padding_mode == E2E_PADDING_BORDER) {
         if (nhwc) LG_LAUNCH(E2E_PAD_BORDER, true);
         else LG_LAUNCH(E2E_PAD_BORDER, false);

@@ -16,9 +16,14 @@ VALUE_RTOL = 1e-4        # the bound csrc/warp_photo_fused.hip states for this p
 FLAG_SETS = [("geometric",), ("smoothness",), ("auto_masking",), ("min_reprojection",), ("geometric", "smoothness"),
              ("min_reprojection", "auto_masking"), ("geometric", "smoothness", "min_reprojection", "auto_masking")]
 SHAPES = [(120, 160), (118, 150), (480, 640)]
+# the terms kernel below one 32x16 tile and with a one-column last tile (the shapes tests/test_gpu_warp_photo.py gives the default kernel),
+# for the two configurations that need no 10000 valid projections
+SMALL_SHAPES = [(8, 33), (20, 70)]
+SMALL_FLAG_SETS = [("auto_masking",), ("min_reprojection", "auto_masking")]
+SHAPE_FLAGS = [(h, w, f) for h, w in SHAPES for f in FLAG_SETS] + [(h, w, f) for h, w in SMALL_SHAPES for f in SMALL_FLAG_SETS]
 # inputs per shape: seeds for which the fp32 oracle stays inside the kink allowance against the fp64 oracle for every configuration below
 # (evaluated on the CPU alone; _inputs' docstring) -- the allowance is then not spent on the comparand's own rounding
-SEEDS = {(120, 160): 5, (118, 150): 5, (480, 640): 5, (64, 96): 5}
+SEEDS = {(120, 160): 5, (118, 150): 5, (480, 640): 5, (64, 96): 5, (8, 33): 5, (20, 70): 5}
 W_GEO, W_SMOOTH, W_REG = 0.5, 1e-3, 1e-2
 NEAR_RY = 30.0           # degrees about y: 120x160 then keeps just under 10000 of its 19200 projections inside (asserted where used)
 
@@ -127,12 +132,13 @@ def compare(gpu, ora, ora32, n, what):
 @pytest.mark.parametrize("reg", [None, "l1", "l2"], ids=["noreg", "l1", "l2"])
 @pytest.mark.parametrize("mask", [True, False], ids=["mask", "nomask"])
 @pytest.mark.parametrize("padding", ["border", "zeros"])
-@pytest.mark.parametrize("flags", FLAG_SETS, ids=["+".join(f) for f in FLAG_SETS])
-@pytest.mark.parametrize("H,W", SHAPES, ids=[f"{h}x{w}" for h, w in SHAPES])
+@pytest.mark.parametrize("H,W,flags", SHAPE_FLAGS, ids=[f"{h}x{w}-" + "+".join(f) for h, w, f in SHAPE_FLAGS])
 def test_terms_lossgrad_vs_fp64_oracle(H, W, flags, padding, mask, reg):
     """Loss components and d/d depth_tgt, d/d depth_src, d/d disp[0] of the new entry points against the float64 oracle: values to
     1e-4 relative; gradients to 1e-4 of the tensor's maximum with at most max(4, 1e-3 N) pixels exempt (kinks), after checking that
-    the fp32 oracle itself stays inside that allowance on this input.  118x150 is no multiple of the 32x16 tile."""
+    the fp32 oracle itself stays inside that allowance on this input.  118x150 is no multiple of the 32x16 tile; 8x33 is lower than a
+    tile with one column in its last tile, 20x70 has a 4-row and a 6-column remainder.  The allowance max(4, 1e-3 N) is 4 pixels at both
+    small shapes, against the 8 pixels of 8x33's one-column tile: a fault in half of that column would pass, one in all of it would not."""
     s = _inputs(H, W, SEEDS[(H, W)])
     ora = oracle_eval(s, flags, padding, mask, reg, torch.float64)
     ora32 = oracle_eval(s, flags, padding, mask, reg, torch.float32)
