@@ -7,6 +7,7 @@
 // wave-shuffle + LDS block reductions, and a fixed-order second-stage reduction (no float
 // atomics => bitwise reproducible losses).
 #include "e2e_common.h"
+#include "warp_photo_pose.h"
 
 #define TW 32
 #define TH 8
@@ -485,15 +486,25 @@ __global__ void k_reduce_partials(const float* __restrict__ partials, int nblk, 
 
 // ---------------------------------------------------------------------------------------------
 // fused backward: photometric adjoint (3x3 box + reflect pad fold-back) -> warp adjoint -> d/d depth
+// POSE: the same launch also leaves, per workgroup, the 12 float64 sums of gc_r X_j | gc_r over its pixels (Pbar of the tile, row-major
+// 3x4; X = d cam, the back-projected point) in pose.partials[workgroup][12]: the gradient wrt T is their sum over the tiles times K^T
+// (k_warp_photo_bwd_pose_final, warp_photo_pose.hip).  No thread leaves before that reduction; pixels outside the image add zeros.
 // ---------------------------------------------------------------------------------------------
-template <int PAD>
+template <bool POSE>
+struct PoseOut {};                       // the last kernel argument: empty without the pose gradient, so that launch is the one it was
+template <>
+struct PoseOut<true> {
+    double* partials;
+};
+
+template <int PAD, bool POSE>
 __global__ __launch_bounds__(NTHREADS) void k_warp_photo_bwd(
     const float* __restrict__ depth, const float* __restrict__ src, e2e_strides ss,
     const float* __restrict__ tgt, e2e_strides ts, const float* __restrict__ K,
     const float* __restrict__ invK, const float* __restrict__ T, const float* __restrict__ synth,
     const float* __restrict__ valid, int use_mask, int reg_kind, const float* __restrict__ ri_t,
     const float* __restrict__ ri_s, const float* __restrict__ d_s, const float* __restrict__ g_loss,
-    float* __restrict__ g_dt, float* __restrict__ g_ds, int B, int H, int W) {
+    float* __restrict__ g_dt, float* __restrict__ g_ds, int B, int H, int W, PoseOut<POSE> pose) {
     __shared__ float lx[3][(TH + 4) * BP_LD], ly[3][(TH + 4) * BP_LD];
     __shared__ float lg[9][(TH + 2) * BG_LD];
     const int b = blockIdx.z, tx0 = blockIdx.x * TW, ty0 = blockIdx.y * TH;
@@ -544,77 +555,106 @@ __global__ __launch_bounds__(NTHREADS) void k_warp_photo_bwd(
     __syncthreads();
 
     const int px = tx0 + threadIdx.x, py = ty0 + threadIdx.y;
-    if (px >= W || py >= H) return;
-    const int64_t o = b * N + (int64_t)py * W + px;
-    float G[3];
-    {
-        float mult[9];
+    const bool live = px < W && py < H;
+    if (!POSE && !live) return;
+    [[maybe_unused]] double acc[12];                           // POSE only: this pixel's gc_r X_j | gc_r
 #pragma unroll
-        for (int dy = -1; dy <= 1; ++dy)
+    for (int k = 0; k < 12; ++k) acc[k] = 0.0;
+    if (live) {
+        const int64_t o = b * N + (int64_t)py * W + px;
+        float G[3];
+        {
+            float mult[9];
 #pragma unroll
-            for (int dx = -1; dx <= 1; ++dx) {
-                const int qx = px + dx, qy = py + dy;
-                mult[(dy + 1) * 3 + dx + 1] = (qx < 0 || qx >= W || qy < 0 || qy >= H) ? 0.f : refl_mult(px, qx, W) * refl_mult(py, qy, H);
+            for (int dy = -1; dy <= 1; ++dy)
+#pragma unroll
+                for (int dx = -1; dx <= 1; ++dx) {
+                    const int qx = px + dx, qy = py + dy;
+                    mult[(dy + 1) * 3 + dx + 1] = (qx < 0 || qx >= W || qy < 0 || qy >= H) ? 0.f : refl_mult(px, qx, W) * refl_mult(py, qy, H);
+                }
+            const int ctr = (threadIdx.y + 2) * BP_LD + threadIdx.x + 2;
+            const float m = use_mask ? valid[o] : 1.f;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                float s1 = 0.f, s2 = 0.f, s3 = 0.f;
+#pragma unroll
+                for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+                    for (int dx = 0; dx < 3; ++dx) {
+                        const int gi = (threadIdx.y + dy) * BG_LD + threadIdx.x + dx;
+                        const float mm = mult[dy * 3 + dx];
+                        s1 += mm * lg[c * 3 + 0][gi];
+                        s2 += mm * lg[c * 3 + 1][gi];
+                        s3 += mm * lg[c * 3 + 2][gi];
+                    }
+                const float xv = lx[c][ctr], yv = ly[c][ctr];
+                float gx_ = (s1 + 2.f * xv * s2 + yv * s3) / 9.f;
+                const float df = yv - xv;
+                const float sg = (df > 0.f) ? 1.f : ((df < 0.f) ? -1.f : 0.f);
+                gx_ -= gl0 * (0.15f / 3.f) * sg;
+                G[c] = gx_ * m;                                // d/d synth = d/dx * mask
             }
-        const int ctr = (threadIdx.y + 2) * BP_LD + threadIdx.x + 2;
-        const float m = use_mask ? valid[o] : 1.f;
+        }
+        // warp adjoint: d synth / d grid (bilinear), grid -> (u,v) -> c -> depth
+        const Geom g = load_geom(K + b * 16, invK + b * 16, T + b * 16);
+        const float d = depth[o];
+        const Proj p = project_pixel(g, (float)px, (float)py, d, W, H);
+        float mx, my;
+        const float ix = source_index<PAD, false>(p.gx, W, mx);
+        const float iy = source_index<PAD, false>(p.gy, H, my);
+        const Bilin bl = bilinear_setup(ix, iy, W, H);
+        const float* sp = src + b * ss.sb + bl.y0 * ss.sh + bl.x0 * ss.sw;
+        float gix = 0.f, giy = 0.f;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            float s1 = 0.f, s2 = 0.f, s3 = 0.f;
+            const float* pc = sp + c * ss.sc;
+            const float nw = (bl.in_y0 & bl.in_x0) ? pc[0] : 0.f;
+            const float ne = (bl.in_y0 & bl.in_x1) ? pc[ss.sw] : 0.f;
+            const float sw = (bl.in_y1 & bl.in_x0) ? pc[ss.sh] : 0.f;
+            const float se = (bl.in_y1 & bl.in_x1) ? pc[ss.sh + ss.sw] : 0.f;
+            gix += G[c] * ((ne - nw) * (1.f - bl.ty) + (se - sw) * bl.ty);
+            giy += G[c] * ((sw - nw) * (1.f - bl.tx) + (se - ne) * bl.tx);
+        }
+        const float gu = (mx * gix) * 2.f / (float)(W - 1);
+        const float gv = (my * giy) * 2.f / (float)(H - 1);
+        const float gc0 = gu / p.z, gc1 = gv / p.z, gc2 = -(gu * p.u + gv * p.v) / p.z;
+        float gd = gc0 * p.r[0] + gc1 * p.r[1] + gc2 * p.r[2];
+        if (reg_kind) {
+            const float gl1 = g_loss[1] * kmean;
+            const float e0 = ri_t[o] - d, e1 = ri_s[o] - d_s[o];
+            if (reg_kind == 2) {
+                gd += gl1 * (-2.f * e0);
+                g_ds[o] = gl1 * (-2.f * e1);
+            } else {
+                gd += gl1 * ((e0 > 0.f) ? -1.f : ((e0 < 0.f) ? 1.f : 0.f));
+                g_ds[o] = gl1 * ((e1 > 0.f) ? -1.f : ((e1 < 0.f) ? 1.f : 0.f));
+            }
+        }
+        g_dt[o] = gd;
+        if constexpr (POSE) {
+            const float gc[3] = {gc0, gc1, gc2};
 #pragma unroll
-            for (int dy = 0; dy < 3; ++dy)
+            for (int r = 0; r < 3; ++r) {
 #pragma unroll
-                for (int dx = 0; dx < 3; ++dx) {
-                    const int gi = (threadIdx.y + dy) * BG_LD + threadIdx.x + dx;
-                    const float mm = mult[dy * 3 + dx];
-                    s1 += mm * lg[c * 3 + 0][gi];
-                    s2 += mm * lg[c * 3 + 1][gi];
-                    s3 += mm * lg[c * 3 + 2][gi];
-                }
-            const float xv = lx[c][ctr], yv = ly[c][ctr];
-            float gx_ = (s1 + 2.f * xv * s2 + yv * s3) / 9.f;
-            const float df = yv - xv;
-            const float sg = (df > 0.f) ? 1.f : ((df < 0.f) ? -1.f : 0.f);
-            gx_ -= gl0 * (0.15f / 3.f) * sg;
-            G[c] = gx_ * m;                                // d/d synth = d/dx * mask
+                for (int j = 0; j < 3; ++j) acc[r * 4 + j] = (double)gc[r] * (double)(d * p.cam[j]);
+                acc[r * 4 + 3] = (double)gc[r];
+            }
         }
     }
-    // warp adjoint: d synth / d grid (bilinear), grid -> (u,v) -> c -> depth
-    const Geom g = load_geom(K + b * 16, invK + b * 16, T + b * 16);
-    const float d = depth[o];
-    const Proj p = project_pixel(g, (float)px, (float)py, d, W, H);
-    float mx, my;
-    const float ix = source_index<PAD, false>(p.gx, W, mx);
-    const float iy = source_index<PAD, false>(p.gy, H, my);
-    const Bilin bl = bilinear_setup(ix, iy, W, H);
-    const float* sp = src + b * ss.sb + bl.y0 * ss.sh + bl.x0 * ss.sw;
-    float gix = 0.f, giy = 0.f;
+    if constexpr (POSE) {  // every thread of the workgroup is here: wave shuffle, then the four waves in order through LDS
+        __shared__ double sh[12][NTHREADS / 64];
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float* pc = sp + c * ss.sc;
-        const float nw = (bl.in_y0 & bl.in_x0) ? pc[0] : 0.f;
-        const float ne = (bl.in_y0 & bl.in_x1) ? pc[ss.sw] : 0.f;
-        const float sw = (bl.in_y1 & bl.in_x0) ? pc[ss.sh] : 0.f;
-        const float se = (bl.in_y1 & bl.in_x1) ? pc[ss.sh + ss.sw] : 0.f;
-        gix += G[c] * ((ne - nw) * (1.f - bl.ty) + (se - sw) * bl.ty);
-        giy += G[c] * ((sw - nw) * (1.f - bl.tx) + (se - ne) * bl.tx);
-    }
-    const float gu = (mx * gix) * 2.f / (float)(W - 1);
-    const float gv = (my * giy) * 2.f / (float)(H - 1);
-    const float gc0 = gu / p.z, gc1 = gv / p.z, gc2 = -(gu * p.u + gv * p.v) / p.z;
-    float gd = gc0 * p.r[0] + gc1 * p.r[1] + gc2 * p.r[2];
-    if (reg_kind) {
-        const float gl1 = g_loss[1] * kmean;
-        const float e0 = ri_t[o] - d, e1 = ri_s[o] - d_s[o];
-        if (reg_kind == 2) {
-            gd += gl1 * (-2.f * e0);
-            g_ds[o] = gl1 * (-2.f * e1);
-        } else {
-            gd += gl1 * ((e0 > 0.f) ? -1.f : ((e0 < 0.f) ? 1.f : 0.f));
-            g_ds[o] = gl1 * ((e1 > 0.f) ? -1.f : ((e1 < 0.f) ? 1.f : 0.f));
+        for (int k = 0; k < 12; ++k) {
+            const double v = wave_sum_d(acc[k]);
+            if ((tid & 63) == 0) sh[k][tid >> 6] = v;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            double* out = pose.partials + (((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 12;
+#pragma unroll
+            for (int k = 0; k < 12; ++k) out[k] = ((sh[k][0] + sh[k][1]) + sh[k][2]) + sh[k][3];
         }
     }
-    g_dt[o] = gd;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -794,15 +834,36 @@ int e2e_warp_photo_bwd(const float* depth_tgt, const float* src, e2e_strides ss,
     E2E_REQUIRE(!reg_kind || (reg_init_tgt && reg_init_src && depth_src && g_depth_src), E2E_ERR_ARG, "e2e_warp_photo_bwd: regulariser buffers missing");
     const dim3 g = tile_grid(B, H, W);
     if (padding_mode == E2E_PADDING_BORDER)
-        hipLaunchKernelGGL(k_warp_photo_bwd<E2E_PAD_BORDER>, g, dim3(TW, TH), 0, (hipStream_t)stream, depth_tgt, src, ss,
+        hipLaunchKernelGGL((k_warp_photo_bwd<E2E_PAD_BORDER, false>), g, dim3(TW, TH), 0, (hipStream_t)stream, depth_tgt, src, ss,
                            tgt, ts, K, inv_K, T, synth, valid, use_mask, reg_kind, reg_init_tgt, reg_init_src, depth_src,
-                           g_loss, g_depth_tgt, g_depth_src, B, H, W);
+                           g_loss, g_depth_tgt, g_depth_src, B, H, W, PoseOut<false>{});
     else
-        hipLaunchKernelGGL(k_warp_photo_bwd<E2E_PAD_ZEROS>, g, dim3(TW, TH), 0, (hipStream_t)stream, depth_tgt, src, ss,
+        hipLaunchKernelGGL((k_warp_photo_bwd<E2E_PAD_ZEROS, false>), g, dim3(TW, TH), 0, (hipStream_t)stream, depth_tgt, src, ss,
                            tgt, ts, K, inv_K, T, synth, valid, use_mask, reg_kind, reg_init_tgt, reg_init_src, depth_src,
-                           g_loss, g_depth_tgt, g_depth_src, B, H, W);
+                           g_loss, g_depth_tgt, g_depth_src, B, H, W, PoseOut<false>{});
     E2E_LAUNCH_CHECK("e2e_warp_photo_bwd");
     return E2E_OK;
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// the pose form of that launch, for e2e_warp_photo_bwd_pose (warp_photo_pose.hip, which has checked every argument): the kernel lives
+// here because it is the same template
+// ---------------------------------------------------------------------------------------------
+int64_t warp_photo_bwd_tiles(int H, int W) { return (int64_t)e2e_ceil_div(W, TW) * e2e_ceil_div(H, TH); }
+
+void warp_photo_bwd_pose_launch(const float* depth_tgt, const float* src, e2e_strides ss, const float* tgt, e2e_strides ts, const float* K,
+                                const float* inv_K, const float* T, const float* synth, const float* valid, int use_mask, int padding_mode,
+                                int reg_kind, const float* reg_init_tgt, const float* reg_init_src, const float* depth_src, const float* g_loss,
+                                float* g_depth_tgt, float* g_depth_src, double* partials, int B, int H, int W, hipStream_t stream) {
+    const dim3 g = tile_grid(B, H, W);
+    if (padding_mode == E2E_PADDING_BORDER)
+        hipLaunchKernelGGL((k_warp_photo_bwd<E2E_PAD_BORDER, true>), g, dim3(TW, TH), 0, stream, depth_tgt, src, ss, tgt, ts, K, inv_K, T,
+                           synth, valid, use_mask, reg_kind, reg_init_tgt, reg_init_src, depth_src, g_loss, g_depth_tgt, g_depth_src, B, H,
+                           W, PoseOut<true>{partials});
+    else
+        hipLaunchKernelGGL((k_warp_photo_bwd<E2E_PAD_ZEROS, true>), g, dim3(TW, TH), 0, stream, depth_tgt, src, ss, tgt, ts, K, inv_K, T,
+                           synth, valid, use_mask, reg_kind, reg_init_tgt, reg_init_src, depth_src, g_loss, g_depth_tgt, g_depth_src, B, H,
+                           W, PoseOut<true>{partials});
+}

@@ -1,7 +1,8 @@
 """Pre-planned (allocation-free, hipGraph-capturable) launches of the fused refinement kernels.
 
 `WarpPhotoPlan` owns every intermediate buffer of the image-space part of one refinement step, so a
-step is exactly: e2e_warp_photo_fwd (+ its 1-block reduction) and e2e_warp_photo_bwd -- no
+step is exactly: e2e_warp_photo_fwd (+ its 1-block reduction) and e2e_warp_photo_bwd (or
+e2e_warp_photo_bwd_pose, which also returns the gradient with respect to T) -- no
 allocator traffic, no host synchronisation.  The build's driver and bench.py use it; the autograd
 form for ad-hoc use is ops.warp_photometric."""
 import ctypes
@@ -26,6 +27,7 @@ class WarpPhotoPlan:
         self.g_depth_tgt = torch.empty(B, 1, H, W, **f)
         self.g_depth_src = torch.empty(B, 1, H, W, **f)
         self.ws = torch.empty(L.load().e2e_warp_photo_workspace_floats(B, H, W), **f)
+        self.g_T = self.ws_pose = None             # backward(pose=True): the gradient wrt T and its float64 partial sums
 
     def bind(self, depth_tgt, depth_src, init_tgt, init_src, src, tgt, K, inv_K, T):
         """Fix the input tensors (they may be rewritten in place between steps)."""
@@ -59,10 +61,24 @@ class WarpPhotoPlan:
                workspace=L.ptr(self.ws))
         return self.loss
 
-    def backward(self):
-        L.call("e2e_warp_photo_bwd", geom=self._operands(), synth=L.ptr(self.synth), valid=L.ptr(self.valid), g_loss=L.ptr(self.g_loss),
-               g_depth_tgt=L.ptr(self.g_depth_tgt), g_depth_src=L.ptr(self.g_depth_src) if self.reg else None)
-        return self.g_depth_tgt, self.g_depth_src
+    def _pose_buffers(self):
+        if self.g_T is None:
+            dev = self.synth.device
+            self.g_T = torch.empty(self.B, 4, 4, device=dev, dtype=torch.float32)
+            self.ws_pose = torch.empty(L.load().e2e_warp_photo_bwd_pose_workspace_bytes(self.B, self.H, self.W), device=dev, dtype=torch.uint8)
+
+    def backward(self, pose=False):
+        """-> (g_depth_tgt, g_depth_src); with pose=True (e2e_warp_photo_bwd_pose) -> (g_depth_tgt, g_depth_src, g_T), g_T (B,4,4) the
+        gradient of g_loss[0] * photometric with respect to the bound T.  g_T and its workspace are allocated once, by the first such
+        call -- make that call before capturing a graph."""
+        outputs = dict(synth=L.ptr(self.synth), valid=L.ptr(self.valid), g_loss=L.ptr(self.g_loss), g_depth_tgt=L.ptr(self.g_depth_tgt),
+                       g_depth_src=L.ptr(self.g_depth_src) if self.reg else None)
+        if not pose:
+            L.call("e2e_warp_photo_bwd", geom=self._operands(), **outputs)
+            return self.g_depth_tgt, self.g_depth_src
+        self._pose_buffers()
+        L.call("e2e_warp_photo_bwd_pose", geom=self._operands(), g_T=L.ptr(self.g_T), workspace=L.ptr(self.ws_pose), **outputs)
+        return self.g_depth_tgt, self.g_depth_src, self.g_T
 
 
 class LossGradPlan(WarpPhotoPlan):

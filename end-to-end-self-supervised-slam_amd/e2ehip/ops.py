@@ -229,21 +229,36 @@ class _WarpPhotometric(torch.autograd.Function):
         gl = torch.stack([g0 if g0 is not None else z, g1 if g1 is not None else z]).contiguous()
         gdt = torch.empty(B, 1, H, W, device=dt.device, dtype=torch.float32)
         gds = torch.empty(B, 1, H, W, device=dt.device, dtype=torch.float32) if reg_kind else None
-        L.call("e2e_warp_photo_bwd", depth_tgt=L.ptr(dt), src=L.ptr(src), src_strides=L.strides4(src), tgt=L.ptr(tgt), tgt_strides=L.strides4(tgt), K=L.ptr(K),
-               inv_K=L.ptr(inv_K), T=L.ptr(T), synth=L.ptr(synth), valid=L.ptr(valid), use_mask=use_mask, padding_mode=pad, reg_kind=reg_kind,
-               reg_init_tgt=L.ptr(it), reg_init_src=L.ptr(is_), depth_src=L.ptr(ds), g_loss=L.ptr(gl), g_depth_tgt=L.ptr(gdt), g_depth_src=L.ptr(gds),
-               B=B, H=H, W=W, stream=L.stream())
-        return (gdt, gds) + (None,) * 11
+        common = dict(depth_tgt=L.ptr(dt), src=L.ptr(src), src_strides=L.strides4(src), tgt=L.ptr(tgt), tgt_strides=L.strides4(tgt), K=L.ptr(K),
+                      inv_K=L.ptr(inv_K), T=L.ptr(T), synth=L.ptr(synth), valid=L.ptr(valid), use_mask=use_mask, padding_mode=pad, reg_kind=reg_kind,
+                      reg_init_tgt=L.ptr(it), reg_init_src=L.ptr(is_), depth_src=L.ptr(ds), g_loss=L.ptr(gl), g_depth_tgt=L.ptr(gdt),
+                      g_depth_src=L.ptr(gds), B=B, H=H, W=W, stream=L.stream())
+        gT = None
+        if ctx.needs_input_grad[8]:          # the pose carries a graph (differentiable odometry, e2ehip.icp): the same kernel also sums d/dT
+            gT = torch.empty(B, 4, 4, device=dt.device, dtype=torch.float32)
+            ws = torch.empty(L.load().e2e_warp_photo_bwd_pose_workspace_bytes(B, H, W), device=dt.device, dtype=torch.uint8)
+            L.call("e2e_warp_photo_bwd_pose", g_T=L.ptr(gT), workspace=L.ptr(ws), **common)
+        else:
+            L.call("e2e_warp_photo_bwd", **common)
+        return (gdt, gds) + (None,) * 6 + (gT,) + (None,) * 4
 
 
 def warp_photometric(depth_tgt, src, tgt, K, inv_K, T, padding_mode="border", use_mask=True,
                      depth_src=None, init_tgt=None, init_src=None, reg_kind=None, want_pmap=False):
-    """Fused image-space part of one refinement step (2 launches forward, 1 backward).
+    """Fused image-space part of one refinement step (2 launches forward, 1 backward; 2 backward when T requires grad).
 
     depth_tgt (B,1,H,W); src/tgt (B,3,H,W) views (NHWC memory welcome); K, inv_K, T (B,4,4).
     reg_kind None | "l1" | "l2" adds mean-reg(init_tgt, depth_tgt) + mean-reg(init_src, depth_src).
     Returns dict(photometric, reg, synth, valid, pmap).
+
+    Differentiated: depth_tgt, depth_src (through the regulariser only) and T (e2e_warp_photo_bwd_pose; the gradient has the shape of
+    the T that was passed, so a pose expanded over the batch gets the sum).  The frames, init_tgt / init_src and the outputs synth, valid
+    and pmap are constants.  K and inv_K are constants too: one that requires grad raises NotImplementedError.
     reference: online_adaption.py:412-455, :544-564, :482-511, :612-623."""
+    if torch.is_grad_enabled():
+        for n, t in (("K", K), ("inv_K", inv_K)):
+            if torch.is_tensor(t) and t.requires_grad:
+                raise NotImplementedError(f"warp_photometric: {n} requires grad, and the fused kernels have no gradient with respect to the intrinsics")
     if depth_tgt.dim() != 4 or depth_tgt.shape[1] != 1:
         raise ValueError(f"depth_tgt: expected (B,1,H,W), got {tuple(depth_tgt.shape)}")
     B, _, H, W = depth_tgt.shape

@@ -14,7 +14,9 @@ novel_view_synthesis, :615-705 compute_losses); every tensor operation on the pa
 the reference's own operator names (BackprojectDepth / Project3D / grid_sample, SSIM / photometric_loss, the losses of
 loss/losses.py, PointFusion / RGBDImages, knn_points / ChamferDistance, the depth network, fused Adam).  With the reference's
 default flags (configs/config.yaml:37-58: masked photometric loss only) the image-space part of a step is the fused
-e2e_warp_photo_* pair instead of the operator-by-operator composition -- `fused_losses=False` keeps the latter.
+e2e_warp_photo_* pair instead of the operator-by-operator composition -- `fused_losses=False` keeps the latter.  That holds with
+estimated poses too (`DATA.use_gt_pose: False`): the pair's backward then also returns the gradient with respect to the relative pose
+(e2e_warp_photo_bwd_pose), which autograd carries on through the odometry.
 
 `MODEL.depth_network` selects the depth network as in the reference (train_depth.py:124-179): `indoor` is DispResNet_Indoor, `monodepth2`
 is ResnetEncoder + DepthDecoder with a sigmoid disparity at every scale of `DATA.scales`, turned into depth by convert_disp_to_depth
@@ -369,9 +371,9 @@ class Depth_Estimation:
 
     # ---------------------------------------------------------------------------------------------------------------------------
     def _fused_ok(self, poses=None):
+        # poses with a graph (DATA.use_gt_pose: False) stay on the fused pair: its backward returns the gradient for T as well
+        # (e2e_warp_photo_bwd_pose).  The three-frame window and the flagged terms take the operators.
         lo = self.args.LOSS
-        if poses is not None and poses.requires_grad:      # the fused warp kernel has no gradient for T: poses with a graph take the operators
-            return False
         return self.fused_losses and self.sequence_length == 2 and lo.photometric_mask is not None and not (
             lo.min_reprojection or lo.auto_masking or lo.geometric)
 

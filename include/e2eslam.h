@@ -157,6 +157,32 @@ int e2e_warp_photo_bwd(const float* depth_tgt, const float* src, e2e_strides src
                        const float* reg_init_src, const float* depth_src, const float* g_loss,
                        float* g_depth_tgt, float* g_depth_src, int B, int H, int W, void* stream);
 
+/* The same backward with the gradient with respect to the relative pose (DATA.use_gt_pose: False, train_depth.py:381-382, :395: the
+ * photometric loss is differentiated through T).  Two launches: the kernel of e2e_warp_photo_bwd with one reduction more, and a final
+ * kernel of one workgroup per batch element.
+ *   g_depth_tgt, g_depth_src   bit-identical to what e2e_warp_photo_bwd writes for the same arguments;
+ *   g_T (B,4,4) = d/dT of g_loss[0]*photometric (the regulariser does not depend on T).  T enters through P = (K T)[:3,:] only; the
+ *     validity mask is a constant (in the reference it is a comparison cast to float); the forward's conventions hold: z = c2 + 1e-7,
+ *     /(W-1) and /(H-1), align_corners=False, with border padding zero slope where the clamp is active, with zero padding the
+ *     out-of-range taps are zero.
+ *   Per pixel, with X = d * inv_K[:3,:3] [x,y,1]^T (fp32, the forward's own d * cam) and (gc0, gc1, gc2) the very fp32 adjoint of the
+ *     projected point that reaches g_depth_tgt:  Pbar[r][j] += gc_r X_j (j < 3),  Pbar[r][3] += gc_r;  then
+ *     g_T[k][j] = sum_{i<3} K[i][k] Pbar[i][j] for k = 0..3 -- the convention of e2e_project3d_bwd_t, its bottom row included.
+ *   The sums are float64 in a fixed order: wave shuffle, the four waves of a workgroup through LDS, 12 doubles per workgroup (32x8
+ *     pixels) in `workspace`, then one wave per sum over the workgroups of a batch element (lane l adds l, l + 64, ... in order, then a
+ *     shuffle tree) and K^T.  No atomics: two runs give the same bits.
+ *   workspace: e2e_warp_photo_bwd_pose_workspace_bytes(B,H,W) bytes = 96 B ceil(H/8) ceil(W/32) (0 for a non-positive size), all written.
+ *   A refused call (NULL g_T or workspace or any pointer e2e_warp_photo_bwd needs, bad dimensions, padding_mode or reg_kind) returns
+ *     E2E_ERR_ARG before any launch and writes nothing. */
+int64_t e2e_warp_photo_bwd_pose_workspace_bytes(int B, int H, int W);
+int e2e_warp_photo_bwd_pose(const float* depth_tgt, const float* src, e2e_strides src_strides,
+                            const float* tgt, e2e_strides tgt_strides, const float* K, const float* inv_K,
+                            const float* T, const float* synth, const float* valid, int use_mask,
+                            int padding_mode, int reg_kind, const float* reg_init_tgt,
+                            const float* reg_init_src, const float* depth_src, const float* g_loss,
+                            float* g_depth_tgt, float* g_depth_src, float* g_T, void* workspace, int B,
+                            int H, int W, void* stream);
+
 /* The step the build's driver actually launches: loss AND gradient in ONE pass (the gradient of a
  * mean does not depend on its value, so forward and backward of the image-space part collapse;
  * synth / valid / the loss map never reach HBM).  Same semantics as e2e_warp_photo_fwd followed by
