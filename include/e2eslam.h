@@ -191,7 +191,15 @@ int e2e_warp_photo_bwd_pose(const float* depth_tgt, const float* src, e2e_stride
  *   g_depth_tgt = d(w_photo*loss0 + w_reg*loss1)/d(depth_tgt), g_depth_src likewise (reg_kind != 0).
  * workspace: e2e_warp_photo_lossgrad_workspace_floats floats (per-workgroup partial sums; a
  * second-stage kernel adds them in a fixed order => bitwise reproducible loss).  loss_out == NULL
- * skips that second launch (gradients only). */
+ * skips that second launch (gradients only).
+ *   e2e_warp_photo_lossgrad_workspace_floats(B,H,W) = 2 B ceil(W/32) ceil(H/8), rounded up to even, + 2 x 8 x 129 floats (the
+ *     per-workgroup partial sums, then the chained form's 8 slot sets of 129 64-bit words); 0 for a non-positive size.  No launch
+ *     writes behind it.
+ *   loss_out[1] = 0 when reg_kind == 0 (the second-stage kernel and the chained form's finalisation both write it); g_depth_src is
+ *     not written then.
+ *   A refused call (a required pointer NULL -- loss_out is not required --, B <= 0, H or W < 2, a padding_mode or reg_kind outside
+ *     its range, a regulariser buffer or g_depth_src missing with reg_kind != 0; for the chained form and its flush also what their
+ *     comment rules out) returns E2E_ERR_ARG before any launch and writes nothing: outputs, loss and workspace stay as they were. */
 int64_t e2e_warp_photo_lossgrad_workspace_floats(int B, int H, int W);
 int e2e_warp_photo_lossgrad(const float* depth_tgt, const float* src, e2e_strides src_strides,
                             const float* tgt, e2e_strides tgt_strides, const float* K,
@@ -221,7 +229,13 @@ int e2e_warp_photo_lossgrad_hostgeo(const float* depth_tgt, const float* src, e2
  * is finished by e2e_warp_photo_lossgrad_chain_flush.  geometry12_host non-NULL (B == 1) replaces
  * K / inv_K / T as in e2e_warp_photo_lossgrad_hostgeo.  The workspace (same size function) must be
  * zero-filled once before the first chained launch.  A per-workgroup sum that is negative, not
- * finite or above 2.6e8 / #workgroups turns the loss into NaN (the gradients are unaffected). */
+ * finite or above 2.6e8 / #workgroups turns the loss into NaN (the gradients are unaffected): both
+ * numbers of that step's loss, and the flag is cleared with the set.  Refused: set_cur outside 0..7,
+ * set_prev above 7 or equal to set_cur, set_prev >= 0 without loss_prev_out, host geometry with
+ * B != 1; for the flush a NULL workspace or loss_out or a set outside 0..7.  reg_kind must not change
+ * along a chain: a launch (and the flush) finalises set_prev with the sum count of its OWN reg_kind,
+ * so a step's regulariser sum is reported only if the call that finalises it has a regulariser too
+ * (the slots are cleared either way). */
 int e2e_warp_photo_lossgrad_chain(const float* depth_tgt, const float* src, e2e_strides src_strides,
                                   const float* tgt, e2e_strides tgt_strides, const float* K,
                                   const float* inv_K, const float* T, const float* geometry12_host,

@@ -1,6 +1,7 @@
 """Host-only: every entry point that include/e2eslam.h declares and csrc/depth_ops.hip, aux_losses.hip or nn_misc.hip implements is
 called by one of the two contract modules (tests/test_gpu_depth_aux_contracts.py, tests/test_gpu_nn_misc_contracts.py); the same for
-csrc/icp.hip and tests/test_gpu_icp_contracts.py, for csrc/warp_photo.hip and tests/test_gpu_warp_photo_contracts.py, for the forward
+csrc/icp.hip and tests/test_gpu_icp_contracts.py, for csrc/warp_photo.hip and tests/test_gpu_warp_photo_contracts.py, for
+csrc/warp_photo_fused.hip and tests/test_gpu_lossgrad_contracts.py, for the forward
 entry points of csrc/conv.hip and tests/test_gpu_conv_fwd_contracts.py, and for the map side -- csrc/pointfusion.hip (but
 e2e_pf_active_subsample_dev, which the ICP gate owns) and csrc/knn.hip -- and tests/test_gpu_map_contracts.py."""
 import os
@@ -50,6 +51,18 @@ def test_every_entry_point_of_the_warp_photo_file_has_a_contract_case():
     assert len(names) >= 12, sorted(names)                                # 12 at the time of writing: the greps still find them
     assert implemented <= declared, sorted(implemented - declared)
     called = set(re.findall(r"[\"'.](e2e_\w+)[\"'(]", _read(ROOT, "tests", "test_gpu_warp_photo_contracts.py")))
+    assert not names - called, f"no contract case calls {sorted(names - called)}"
+
+
+def test_every_entry_point_of_the_fused_lossgrad_file_has_a_contract_case():
+    """csrc/warp_photo_fused.hip's entry points (the one-launch loss and gradient, its host-geometry and chained forms, the flush and the
+    workspace query) are all called by tests/test_gpu_lossgrad_contracts.py."""
+    declared = set(re.findall(r"^(?:int|int64_t|long long)\s+(e2e_\w+)\s*\(", _read(ROOT, "include", "e2eslam.h"), re.M))
+    implemented = set(re.findall(r"^(?:int|int64_t|long long)\s+(e2e_\w+)\s*\(", _read(CSRC, "warp_photo_fused.hip"), re.M))
+    names = declared & implemented
+    assert len(names) >= 5, sorted(names)                                 # 5 at the time of writing: the greps still find them
+    assert implemented <= declared, sorted(implemented - declared)
+    called = set(re.findall(r"[\"'.](e2e_\w+)[\"'(]", _read(ROOT, "tests", "test_gpu_lossgrad_contracts.py")))
     assert not names - called, f"no contract case calls {sorted(names - called)}"
 
 
