@@ -277,6 +277,99 @@ def warp_photometric(depth_tgt, src, tgt, K, inv_K, T, padding_mode="border", us
     return {"photometric": p, "reg": r, "synth": synth, "valid": valid, "pmap": pmap}
 
 
+TERM_AUTO_MASKING, TERM_MIN_REPROJECTION = 2, 4                # E2E_TERM_* of include/e2eslam.h
+
+
+class _WarpPhotometricWindow(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, depth_tgt, src0, src1, tgt, K, inv_K, T0, T1, tie_noise, pad, use_mask, terms, want_pmap):
+        B, _, H, W = depth_tgt.shape
+        S = 1 if src1 is None else 2
+        dt = L.dev(depth_tgt, "depth_tgt").contiguous()
+        src0, tgt = L.dev(src0, "source_frame"), L.dev(tgt, "target_frame")
+        if S == 2:
+            src1 = L.dev(src1, "source_frame")
+            if src1.stride() != src0.stride():                 # one stride set serves both sources: a copy of the second in the first's layout
+                if 0 in src0.stride():
+                    src0 = src0.contiguous()
+                src1 = torch.empty_strided(src0.shape, src0.stride(), device=src0.device, dtype=torch.float32).copy_(src1)
+        K, inv_K = _mat(K, "K", B), _mat(inv_K, "inv_K", B)
+        T = torch.stack([_mat(t, "T", B) for t in ((T0, T1) if S == 2 else (T0,))])
+        noise = L.dev(tie_noise, "tie_noise").contiguous() if tie_noise is not None else None
+        dev = dt.device
+        synth = torch.empty(S, B, 3, H, W, device=dev, dtype=torch.float32)
+        valid = torch.empty(S, B, 1, H, W, device=dev, dtype=torch.float32)
+        select = torch.empty(B, 1, H, W, device=dev, dtype=torch.int32)
+        pmap = torch.empty(B, 1, H, W, device=dev, dtype=torch.float32) if want_pmap else None
+        loss = torch.zeros(1, device=dev, dtype=torch.float32)
+        ws = torch.empty(L.load().e2e_warp_photo_window_workspace_floats(S, B, H, W), device=dev, dtype=torch.float32)
+        L.call("e2e_warp_photo_window_fwd", depth_tgt=L.ptr(dt), src0=L.ptr(src0), src1=L.ptr(src1), src_strides=L.strides4(src0), tgt=L.ptr(tgt),
+               tgt_strides=L.strides4(tgt), K=L.ptr(K), inv_K=L.ptr(inv_K), T=L.ptr(T), tie_noise=L.ptr(noise), synth=L.ptr(synth), valid=L.ptr(valid),
+               select=L.ptr(select), pmap=L.ptr(pmap), use_mask=int(use_mask), padding_mode=pad, terms=terms, loss_out=L.ptr(loss),
+               workspace=L.ptr(ws), S=S, B=B, H=H, W=W, stream=L.stream())
+        ctx.save_for_backward(dt, src0, src1, tgt, K, inv_K, T, synth, valid, select)
+        ctx.cfg = (pad, int(use_mask), terms, S, B, H, W)
+        ctx.mark_non_differentiable(synth, valid, select)
+        if pmap is not None:
+            ctx.mark_non_differentiable(pmap)
+        return loss[0], synth, valid, select, pmap
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g0, *_):
+        dt, src0, src1, tgt, K, inv_K, T, synth, valid, select = ctx.saved_tensors
+        pad, use_mask, terms, S, B, H, W = ctx.cfg
+        gl = g0.reshape(1).contiguous()
+        gdt = torch.empty(B, 1, H, W, device=dt.device, dtype=torch.float32)
+        gT = ws = None
+        if ctx.needs_input_grad[6] or (S == 2 and ctx.needs_input_grad[7]):      # a pose carries a graph: the same launch also sums d/dT
+            gT = torch.empty(S, B, 4, 4, device=dt.device, dtype=torch.float32)
+            ws = torch.empty(L.load().e2e_warp_photo_window_bwd_workspace_bytes(S, B, H, W), device=dt.device, dtype=torch.uint8)
+        L.call("e2e_warp_photo_window_bwd", depth_tgt=L.ptr(dt), src0=L.ptr(src0), src1=L.ptr(src1), src_strides=L.strides4(src0), tgt=L.ptr(tgt),
+               tgt_strides=L.strides4(tgt), K=L.ptr(K), inv_K=L.ptr(inv_K), T=L.ptr(T), synth=L.ptr(synth), valid=L.ptr(valid), select=L.ptr(select),
+               use_mask=use_mask, padding_mode=pad, terms=terms, g_loss=L.ptr(gl), g_depth_tgt=L.ptr(gdt), g_T=L.ptr(gT), workspace=L.ptr(ws),
+               S=S, B=B, H=H, W=W, stream=L.stream())
+        g_T0 = gT[0] if gT is not None and ctx.needs_input_grad[6] else None
+        g_T1 = gT[1] if gT is not None and S == 2 and ctx.needs_input_grad[7] else None
+        return (gdt,) + (None,) * 5 + (g_T0, g_T1) + (None,) * 5
+
+
+def warp_photometric_window(depth_tgt, srcs, tgt, K, inv_K, Ts, padding_mode="border", use_mask=True, min_reprojection=False,
+                            auto_masking=False, tie_noise=None, want_pmap=False):
+    """The fused pair over a window of one or two source frames with the candidate / minimum logic of train_depth.py:621-662
+    (e2e_warp_photo_window_fwd / _bwd: 2 launches forward, 1 backward; 2 backward when a pose requires grad).
+
+    depth_tgt (B,1,H,W); srcs: 1 or 2 (B,3,H,W) views, tgt likewise (NHWC memory welcome; sources whose strides differ cost one copy of
+    the second); K, inv_K (B,4,4); Ts: one (B,4,4) pose per source.  auto_masking puts the identity maps photometric(src m, tgt m) before
+    the reprojection maps; min_reprojection keeps one candidate per source instead of their mean, and with both tie_noise (B,S,H,W) --
+    None: nothing -- is added to the identity maps.  Returns dict(photometric, synth (S,B,3,H,W), valid (S,B,1,H,W), select (B,1,H,W) int32:
+    the index of the first minimal candidate, pmap (B,1,H,W): the minimum, when asked for).
+
+    Differentiated: depth_tgt and every T (the gradient has the shape of the T that was passed, so a pose expanded over the batch gets the
+    sum).  Frames, masks, tie_noise and the other outputs are constants; K or inv_K requiring grad raises NotImplementedError."""
+    if torch.is_grad_enabled():
+        for n, t in (("K", K), ("inv_K", inv_K)):
+            if torch.is_tensor(t) and t.requires_grad:
+                raise NotImplementedError(f"warp_photometric_window: {n} requires grad, and the fused kernels have no gradient with respect to the intrinsics")
+    if depth_tgt.dim() != 4 or depth_tgt.shape[1] != 1:
+        raise ValueError(f"depth_tgt: expected (B,1,H,W), got {tuple(depth_tgt.shape)}")
+    B, _, H, W = depth_tgt.shape
+    srcs, Ts = list(srcs), list(Ts)
+    S = len(srcs)
+    if S not in (1, 2) or len(Ts) != S:
+        raise ValueError(f"warp_photometric_window: expected 1 or 2 source frames and as many poses, got {S} and {len(Ts)}")
+    for n, t in [("source_frame", s) for s in srcs] + [("target_frame", tgt)]:
+        if tuple(t.shape) != (B, 3, H, W):
+            raise ValueError(f"{n}: expected ({B},3,{H},{W}), got {tuple(t.shape)}")
+    if tie_noise is not None and tuple(tie_noise.shape) != (B, S, H, W):
+        raise ValueError(f"tie_noise: expected ({B},{S},{H},{W}), got {tuple(tie_noise.shape)}")
+    terms = (TERM_AUTO_MASKING if auto_masking else 0) | (TERM_MIN_REPROJECTION if min_reprojection else 0)
+    p, synth, valid, select, pmap = _WarpPhotometricWindow.apply(depth_tgt, srcs[0], srcs[1] if S == 2 else None, tgt, K, inv_K, Ts[0],
+                                                                 Ts[1] if S == 2 else None, tie_noise, _padding(padding_mode), bool(use_mask),
+                                                                 terms, bool(want_pmap))
+    return {"photometric": p, "synth": synth, "valid": valid, "select": select, "pmap": pmap}
+
+
 # ---------------------------------------------------------------------------------------------
 # RGB-D unprojection, rigid transforms, nearest neighbours
 # ---------------------------------------------------------------------------------------------

@@ -16,7 +16,9 @@ loss/losses.py, PointFusion / RGBDImages, knn_points / ChamferDistance, the dept
 default flags (configs/config.yaml:37-58: masked photometric loss only) the image-space part of a step is the fused
 e2e_warp_photo_* pair instead of the operator-by-operator composition -- `fused_losses=False` keeps the latter.  That holds with
 estimated poses too (`DATA.use_gt_pose: False`): the pair's backward then also returns the gradient with respect to the relative pose
-(e2e_warp_photo_bwd_pose), which autograd carries on through the odometry.
+(e2e_warp_photo_bwd_pose), which autograd carries on through the odometry.  The three-frame window, LOSS.min_reprojection and
+LOSS.auto_masking run on the window form of the pair (e2e_warp_photo_window_fwd / _bwd: the candidates and the per-pixel minimum of
+:621-662 in the kernel, a gradient for every pose); LOSS.geometric keeps the operators.
 
 `MODEL.depth_network` selects the depth network as in the reference (train_depth.py:124-179): `indoor` is DispResNet_Indoor, `monodepth2`
 is ResnetEncoder + DepthDecoder with a sigmoid disparity at every scale of `DATA.scales`, turned into depth by convert_disp_to_depth
@@ -372,19 +374,33 @@ class Depth_Estimation:
     # ---------------------------------------------------------------------------------------------------------------------------
     def _fused_ok(self, poses=None):
         # poses with a graph (DATA.use_gt_pose: False) stay on the fused pair: its backward returns the gradient for T as well
-        # (e2e_warp_photo_bwd_pose).  The three-frame window and the flagged terms take the operators.
+        # (e2e_warp_photo_bwd_pose).  The three-frame window, LOSS.min_reprojection and LOSS.auto_masking take the window form of the
+        # pair (e2e_warp_photo_window_fwd / _bwd), which returns a gradient for every pose.  LOSS.geometric takes the operators.
         lo = self.args.LOSS
-        return self.fused_losses and self.sequence_length == 2 and lo.photometric_mask is not None and not (
-            lo.min_reprojection or lo.auto_masking or lo.geometric)
+        return self.fused_losses and lo.photometric_mask is not None and not lo.geometric
 
     def compute_losses_fused(self, inputs):
-        """compute_losses for the reference's default flag set with the image-space part as ONE fused forward (warp + mask + SSIM/L1 +
-        mean) and ONE fused backward (e2e_warp_photo_fwd / _bwd): photometric [+ regulariser], then the remaining terms."""
+        """compute_losses with the image-space part as ONE fused forward (warp + mask + SSIM/L1 + mean) and ONE fused backward: the
+        reference's default flag set on a two-frame window is e2e_warp_photo_fwd / _bwd; the three-frame window, LOSS.min_reprojection and
+        LOSS.auto_masking are e2e_warp_photo_window_fwd / _bwd (candidates and per-pixel minimum of train_depth.py:621-662 in the
+        kernel).  Then the remaining terms."""
         a = self.args
-        frame = a.DATA.frames[1]
+        frames = a.DATA.frames[1:]
         self.optimizer.zero_grad()
-        out = ops.warp_photometric(inputs["target_depth"], inputs["source_frame", frame], inputs["target_frame"], inputs["K"], inputs["Inverse_K"],
-                                   inputs["T", frame], padding_mode=a.MODEL.padding_mode, use_mask=bool(a.LOSS.photometric_mask))
+        if len(frames) == 2 or a.LOSS.min_reprojection or a.LOSS.auto_masking:
+            noise = None
+            if a.LOSS.min_reprojection and a.LOSS.auto_masking:
+                B, _, H, W = inputs["target_depth"].shape
+                noise = torch.randn((B, len(frames), H, W), device=inputs["target_depth"].device) * 0.00001     # "Break tie's" (:650)
+            out = ops.warp_photometric_window(inputs["target_depth"], [inputs["source_frame", f] for f in frames], inputs["target_frame"],
+                                              inputs["K"], inputs["Inverse_K"], [inputs["T", f] for f in frames],
+                                              padding_mode=a.MODEL.padding_mode, use_mask=bool(a.LOSS.photometric_mask),
+                                              min_reprojection=bool(a.LOSS.min_reprojection), auto_masking=bool(a.LOSS.auto_masking),
+                                              tie_noise=noise)
+        else:
+            out = ops.warp_photometric(inputs["target_depth"], inputs["source_frame", frames[0]], inputs["target_frame"], inputs["K"],
+                                       inputs["Inverse_K"], inputs["T", frames[0]], padding_mode=a.MODEL.padding_mode,
+                                       use_mask=bool(a.LOSS.photometric_mask))
         loss = out["photometric"]
         loss = self._add_common_terms(loss, inputs, None)
         loss.backward()

@@ -280,6 +280,46 @@ int e2e_warp_photo_terms_lossgrad(const float* depth_tgt, const float* depth_src
                                   float w_reg, float w_geometric, float* loss_out, float* g_depth_tgt,
                                   float* g_depth_src, float* workspace, int B, int H, int W, void* stream);
 
+/* The fused forward / backward pair over a WINDOW of S = 1 or 2 source frames (DATA.frames: [0,-1,1] is S = 2), with the candidate /
+ * minimum logic of train_depth.py:621-662.  Forward: one tile launch over the sources + the fixed-order reduction; backward: one tile
+ * launch over the sources, + one final kernel of S B workgroups when g_T is asked for.
+ *   src0, src1          the source frames, (B,3,H,W) through the SAME strides (src1 may be NULL with S = 1); tgt likewise through its own
+ *   T (S,B,4,4)         the relative pose of each source;  K, inv_K (B,4,4)
+ *   terms               E2E_TERM_AUTO_MASKING | E2E_TERM_MIN_REPROJECTION (E2E_TERM_GEOMETRIC is refused: that term stays on the operators)
+ *   For source s with its validity mask m_s (1 when use_mask == 0):
+ *     R_s = photometric(synth_s m_s, tgt m_s);   I_s = photometric(src_s m_s, tgt m_s), src_s read at the target pixel.
+ *   Candidates, in this order:  identity candidates, only with AUTO_MASKING -- with MIN_REPROJECTION  I_0 + n_0, ..., I_{S-1} + n_{S-1}
+ *     (n = tie_noise (B,S,H,W); NULL: nothing added), without it the one map mean_s I_s;  then the reprojection candidates -- with
+ *     MIN_REPROJECTION  R_0, ..., R_{S-1},  without it the one map mean_s R_s.
+ *   loss_out[0] = the mean of the one candidate, or of the per-pixel minimum of several;  pmap (B,H,W) or NULL = that map;
+ *   select (B,H,W) int32 = the index of the FIRST minimal candidate (a NaN wins, as in torch.min and e2e_min_reprojection_lossgrad); 0 with
+ *     one candidate;  synth (S,B,3,H,W), valid (S,B,H,W): each source's sample and mask, kept for the backward.
+ *   Gradient, nI = the number of identity candidates: select < nI -- none (frames and masks are constants); select - nI = r under
+ *     MIN_REPROJECTION -- the pixel's g_loss[0] / (B H W) goes to R_r alone; otherwise 1/S of it to each R_s.  Per source the rest is
+ *     e2e_warp_photo_bwd_pose's: z = c2 + 1e-7, align_corners=False, zero slope under an active border clamp, the mask a constant.
+ *   g_depth_tgt (B,H,W): the sum over the sources, one store per pixel.
+ *   g_T (S,B,4,4) or NULL (no pose sums; workspace may then be NULL, and g_depth_tgt has the same bits): the convention of
+ *     e2e_project3d_bwd_t, bottom row included; float64 sums in the fixed order of e2e_warp_photo_bwd_pose.  No atomics anywhere: two runs
+ *     give the same bits.
+ *   workspace: forward e2e_warp_photo_window_workspace_floats(S,B,H,W) = B ceil(H/8) ceil(W/32) floats, backward
+ *     e2e_warp_photo_window_bwd_workspace_bytes(S,B,H,W) = 96 S B ceil(H/8) ceil(W/32) bytes, both all written (0 for a non-positive size or
+ *     an S outside 1..2).
+ *   A refused call (S outside 1..2, src1 NULL with S = 2, H or W < 2, B <= 0 or > 65535, an unknown padding mode or term, a NULL required
+ *     pointer -- tie_noise, pmap and g_T are not required; workspace is, except for the backward without g_T) returns E2E_ERR_ARG before
+ *     any launch and writes nothing. */
+int64_t e2e_warp_photo_window_workspace_floats(int S, int B, int H, int W);
+int e2e_warp_photo_window_fwd(const float* depth_tgt, const float* src0, const float* src1, e2e_strides src_strides,
+                              const float* tgt, e2e_strides tgt_strides, const float* K, const float* inv_K,
+                              const float* T, const float* tie_noise, float* synth, float* valid, int* select,
+                              float* pmap, int use_mask, int padding_mode, int terms, float* loss_out,
+                              float* workspace, int S, int B, int H, int W, void* stream);
+int64_t e2e_warp_photo_window_bwd_workspace_bytes(int S, int B, int H, int W);
+int e2e_warp_photo_window_bwd(const float* depth_tgt, const float* src0, const float* src1, e2e_strides src_strides,
+                              const float* tgt, e2e_strides tgt_strides, const float* K, const float* inv_K,
+                              const float* T, const float* synth, const float* valid, const int* select, int use_mask,
+                              int padding_mode, int terms, const float* g_loss, float* g_depth_tgt, float* g_T,
+                              void* workspace, int S, int B, int H, int W, void* stream);
+
 /* online_adaption.py:600-610 + losses.py:119-132 for ONE frame: edge-aware first-order smoothness of
  * disp / (mean(disp) + 1e-7) with the edges of img (3,H,W through strides; the batch stride is not used), fused
  * mean -> normalise -> loss + gradient.  loss_out[0] = the term (unweighted);  g_disp (H,W) += weight * d(term)/d(disp),
