@@ -7,11 +7,7 @@
 // wave-shuffle + LDS block reductions, and a fixed-order second-stage reduction (no float
 // atomics => bitwise reproducible losses).
 #include "e2e_common.h"
-#include "warp_photo_pose.h"
-
-#define TW 32
-#define TH 8
-#define NTHREADS (TW * TH)
+#include "warp_photo_tile.h"
 
 // ---------------------------------------------------------------------------------------------
 // small element-wise / per-pixel kernels behind the reference's module-level API
@@ -198,67 +194,9 @@ __global__ void k_grid_sample_bwd(const float* __restrict__ in, e2e_strides s, c
 }
 
 // ---------------------------------------------------------------------------------------------
-// SSIM statistics on an LDS plane.  xs/ys point at the window's top-left element, `ld` = row pitch.
-// Summation order = avg_pool2d's (rows outer, columns inner), then /9 -- losses.py:27-32.
-// ---------------------------------------------------------------------------------------------
-struct Stats {
-    float mux, muy, sxx, syy, sxy;
-};
-__device__ __forceinline__ Stats window_stats(const float* xs, const float* ys, int ld) {
-    float sx = 0.f, sy = 0.f, sxx = 0.f, syy = 0.f, sxy = 0.f;
-#pragma unroll
-    for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-        for (int dx = 0; dx < 3; ++dx) {
-            const float a = xs[dy * ld + dx], b = ys[dy * ld + dx];
-            sx += a;
-            sy += b;
-            sxx += a * a;
-            syy += b * b;
-            sxy += a * b;
-        }
-    Stats s;
-    s.mux = sx / 9.f;
-    s.muy = sy / 9.f;
-    s.sxx = sxx / 9.f;
-    s.syy = syy / 9.f;
-    s.sxy = sxy / 9.f;
-    return s;
-}
-
-#define SSIM_C1 1e-4f   // 0.01**2  losses.py:20
-#define SSIM_C2 9e-4f   // 0.03**2  losses.py:21
-
-__device__ __forceinline__ float ssim_value(const Stats& s) {
-    const float sigx = s.sxx - s.mux * s.mux;
-    const float sigy = s.syy - s.muy * s.muy;
-    const float sigxy = s.sxy - s.mux * s.muy;
-    const float n = (2.f * s.mux * s.muy + SSIM_C1) * (2.f * sigxy + SSIM_C2);
-    const float d = (s.mux * s.mux + s.muy * s.muy + SSIM_C1) * (sigx + sigy + SSIM_C2);
-    return fminf(fmaxf((1.f - n / d) / 2.f, 0.f), 1.f);
-}
-
-// d(ssim_c)/d(mux, sxx, sxy) scaled by the upstream gradient g of ssim_c  
-__device__ __forceinline__ void ssim_partials(const Stats& s, float g, float& G1, float& G2, float& G3) {
-    const float sigx = s.sxx - s.mux * s.mux;
-    const float sigy = s.syy - s.muy * s.muy;
-    const float sigxy = s.sxy - s.mux * s.muy;
-    const float A1 = 2.f * s.mux * s.muy + SSIM_C1, A2 = 2.f * sigxy + SSIM_C2;
-    const float B1 = s.mux * s.mux + s.muy * s.muy + SSIM_C1, B2 = sigx + sigy + SSIM_C2;
-    const float S = (A1 * A2) / (B1 * B2);
-    const float t = (1.f - S) / 2.f;
-    const float gS = (t >= 0.f && t <= 1.f) ? -0.5f * g : 0.f;   // clamp passes grad on the closed interval
-    const float inv = 1.f / (B1 * B2);
-    G1 = gS * (2.f * s.muy * (A2 - A1) * inv - S * 2.f * s.mux * (1.f / B1 - 1.f / B2));
-    G2 = gS * (-S / B2);
-    G3 = gS * (2.f * A1 * inv);
-}
-
-// ---------------------------------------------------------------------------------------------
 // modular photometric forward / backward: C channels, one LDS plane pair per channel pass
 // SSIM.forward losses.py:23-37, photometric_loss losses.py:97-117
 // ---------------------------------------------------------------------------------------------
-#define FP_LD (TW + 2)
 __global__ __launch_bounds__(NTHREADS) void k_photometric_fwd(
     const float* __restrict__ x, e2e_strides xs, const float* __restrict__ y, e2e_strides ys,
     float* __restrict__ ssim_out, float* __restrict__ pmap_out, int C, int H, int W) {
@@ -295,8 +233,6 @@ __global__ __launch_bounds__(NTHREADS) void k_photometric_fwd(
     if (live && pmap_out) pmap_out[((int64_t)b * H + py) * W + px] = 0.85f * (ssim_acc / (float)C) + 0.15f * (l1_acc / (float)C);
 }
 
-#define BP_LD (TW + 4)
-#define BG_LD (TW + 2)
 __global__ __launch_bounds__(NTHREADS) void k_photometric_bwd(
     const float* __restrict__ x, e2e_strides xs, const float* __restrict__ y, e2e_strides ys,
     const float* __restrict__ g_pmap, const float* __restrict__ g_ssim, float* __restrict__ g_x,
@@ -368,20 +304,6 @@ __global__ __launch_bounds__(NTHREADS) void k_photometric_bwd(
 // fused forward: warp + mask + photometric (+ depth regulariser) -> synth, valid, pmap, partial sums
 // online_adaption.py:412-455 (novel_view_synthesis), :544-564, :482-511, :612-623
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void sample3(const float* __restrict__ base, const e2e_strides& s, const Bilin& bl, float* out) {
-    const float* p = base + bl.y0 * s.sh + bl.x0 * s.sw;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float* pc = p + c * s.sc;
-        float acc = 0.f;
-        if (bl.in_y0 & bl.in_x0) acc += pc[0] * bl.wnw;
-        if (bl.in_y0 & bl.in_x1) acc += pc[s.sw] * bl.wne;
-        if (bl.in_y1 & bl.in_x0) acc += pc[s.sh] * bl.wsw;
-        if (bl.in_y1 & bl.in_x1) acc += pc[s.sh + s.sw] * bl.wse;
-        out[c] = acc;
-    }
-}
-
 template <int PAD>
 __global__ __launch_bounds__(NTHREADS) void k_warp_photo_fwd(
     const float* __restrict__ depth, const float* __restrict__ src, e2e_strides ss,
@@ -660,7 +582,6 @@ __global__ __launch_bounds__(NTHREADS) void k_warp_photo_bwd(
 // ---------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------
-static inline dim3 tile_grid(int B, int H, int W) { return dim3(e2e_ceil_div(W, TW), e2e_ceil_div(H, TH), B); }
 static inline dim3 flat_grid(int B, int64_t N) {
     int g = e2e_ceil_div(N, 256);
     if (g > 2048) g = 2048;
@@ -669,6 +590,24 @@ static inline dim3 flat_grid(int B, int64_t N) {
 #define CHECK_DIMS(name)                                                                      \
     E2E_REQUIRE(B > 0 && H > 1 && W > 1 && (int64_t)B * H * W < (1ll << 31), E2E_ERR_ARG,     \
                 name ": bad dims B=%d H=%d W=%d", B, H, W)
+
+// the one launch of k_warp_photo_bwd: e2e_warp_photo_bwd (POSE = false) and warp_photo_bwd_pose_launch.  Arguments are not checked here.
+template <bool POSE>
+static void warp_photo_bwd_launch(const float* depth_tgt, const float* src, e2e_strides ss, const float* tgt, e2e_strides ts, const float* K,
+                                  const float* inv_K, const float* T, const float* synth, const float* valid, int use_mask, int padding_mode,
+                                  int reg_kind, const float* reg_init_tgt, const float* reg_init_src, const float* depth_src,
+                                  const float* g_loss, float* g_depth_tgt, float* g_depth_src, int B, int H, int W, PoseOut<POSE> pose,
+                                  hipStream_t stream) {
+    const dim3 g = tile_grid(B, H, W);
+    if (padding_mode == E2E_PADDING_BORDER)
+        hipLaunchKernelGGL((k_warp_photo_bwd<E2E_PAD_BORDER, POSE>), g, dim3(TW, TH), 0, stream, depth_tgt, src, ss, tgt, ts, K, inv_K, T,
+                           synth, valid, use_mask, reg_kind, reg_init_tgt, reg_init_src, depth_src, g_loss, g_depth_tgt, g_depth_src, B, H,
+                           W, pose);
+    else
+        hipLaunchKernelGGL((k_warp_photo_bwd<E2E_PAD_ZEROS, POSE>), g, dim3(TW, TH), 0, stream, depth_tgt, src, ss, tgt, ts, K, inv_K, T,
+                           synth, valid, use_mask, reg_kind, reg_init_tgt, reg_init_src, depth_src, g_loss, g_depth_tgt, g_depth_src, B, H,
+                           W, pose);
+}
 
 extern "C" {
 
@@ -796,13 +735,10 @@ int e2e_warp_photo_fwd(const float* depth_tgt, const float* src, e2e_strides ss,
                        int use_mask, int padding_mode, int reg_kind, const float* reg_init_tgt,
                        const float* reg_init_src, const float* depth_src, float* loss_out, float* workspace, int B,
                        int H, int W, void* stream) {
-    CHECK_DIMS("e2e_warp_photo_fwd");
-    E2E_REQUIRE(depth_tgt && src && tgt && K && inv_K && T && synth && valid && loss_out && workspace, E2E_ERR_ARG,
-                "e2e_warp_photo_fwd: null pointer");
-    E2E_REQUIRE(padding_mode == E2E_PADDING_BORDER || padding_mode == E2E_PADDING_ZEROS, E2E_ERR_ARG,
-                "e2e_warp_photo_fwd: padding_mode %d not supported (zeros|border)", padding_mode);
-    E2E_REQUIRE(reg_kind >= 0 && reg_kind <= 2, E2E_ERR_ARG, "e2e_warp_photo_fwd: reg_kind %d (0 none, 1 l1, 2 l2)", reg_kind);
-    E2E_REQUIRE(!reg_kind || (reg_init_tgt && reg_init_src && depth_src), E2E_ERR_ARG, "e2e_warp_photo_fwd: regulariser buffers missing");
+    if (const int rc = warp_photo_check_args("e2e_warp_photo_fwd", B, H, W,
+                                             depth_tgt && src && tgt && K && inv_K && T && synth && valid && loss_out && workspace,
+                                             padding_mode, reg_kind, reg_init_tgt && reg_init_src && depth_src))
+        return rc;
     const dim3 g = tile_grid(B, H, W);
     const int nblk = g.x * g.y * g.z;
     if (padding_mode == E2E_PADDING_BORDER)
@@ -815,7 +751,7 @@ int e2e_warp_photo_fwd(const float* depth_tgt, const float* src, e2e_strides ss,
                            depth_src, workspace, H, W);
     E2E_LAUNCH_CHECK("e2e_warp_photo_fwd");
     const float scale = (float)(1.0 / ((double)B * H * W));
-    hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(256), 0, (hipStream_t)stream, workspace, nblk, reg_kind ? 2 : 1, scale, loss_out);
+    warp_photo_reduce_launch(workspace, nblk, reg_kind ? 2 : 1, scale, loss_out, (hipStream_t)stream);
     E2E_LAUNCH_CHECK("e2e_warp_photo_fwd(reduce)");
     return E2E_OK;
 }
@@ -825,22 +761,12 @@ int e2e_warp_photo_bwd(const float* depth_tgt, const float* src, e2e_strides ss,
                        int use_mask, int padding_mode, int reg_kind, const float* reg_init_tgt,
                        const float* reg_init_src, const float* depth_src, const float* g_loss, float* g_depth_tgt,
                        float* g_depth_src, int B, int H, int W, void* stream) {
-    CHECK_DIMS("e2e_warp_photo_bwd");
-    E2E_REQUIRE(depth_tgt && src && tgt && K && inv_K && T && synth && valid && g_loss && g_depth_tgt, E2E_ERR_ARG,
-                "e2e_warp_photo_bwd: null pointer");
-    E2E_REQUIRE(padding_mode == E2E_PADDING_BORDER || padding_mode == E2E_PADDING_ZEROS, E2E_ERR_ARG,
-                "e2e_warp_photo_bwd: padding_mode %d not supported (zeros|border)", padding_mode);
-    E2E_REQUIRE(reg_kind >= 0 && reg_kind <= 2, E2E_ERR_ARG, "e2e_warp_photo_bwd: reg_kind %d (0 none, 1 l1, 2 l2)", reg_kind);
-    E2E_REQUIRE(!reg_kind || (reg_init_tgt && reg_init_src && depth_src && g_depth_src), E2E_ERR_ARG, "e2e_warp_photo_bwd: regulariser buffers missing");
-    const dim3 g = tile_grid(B, H, W);
-    if (padding_mode == E2E_PADDING_BORDER)
-        hipLaunchKernelGGL((k_warp_photo_bwd<E2E_PAD_BORDER, false>), g, dim3(TW, TH), 0, (hipStream_t)stream, depth_tgt, src, ss,
-                           tgt, ts, K, inv_K, T, synth, valid, use_mask, reg_kind, reg_init_tgt, reg_init_src, depth_src,
-                           g_loss, g_depth_tgt, g_depth_src, B, H, W, PoseOut<false>{});
-    else
-        hipLaunchKernelGGL((k_warp_photo_bwd<E2E_PAD_ZEROS, false>), g, dim3(TW, TH), 0, (hipStream_t)stream, depth_tgt, src, ss,
-                           tgt, ts, K, inv_K, T, synth, valid, use_mask, reg_kind, reg_init_tgt, reg_init_src, depth_src,
-                           g_loss, g_depth_tgt, g_depth_src, B, H, W, PoseOut<false>{});
+    if (const int rc = warp_photo_check_args("e2e_warp_photo_bwd", B, H, W,
+                                             depth_tgt && src && tgt && K && inv_K && T && synth && valid && g_loss && g_depth_tgt,
+                                             padding_mode, reg_kind, reg_init_tgt && reg_init_src && depth_src && g_depth_src))
+        return rc;
+    warp_photo_bwd_launch<false>(depth_tgt, src, ss, tgt, ts, K, inv_K, T, synth, valid, use_mask, padding_mode, reg_kind, reg_init_tgt,
+                                 reg_init_src, depth_src, g_loss, g_depth_tgt, g_depth_src, B, H, W, PoseOut<false>{}, (hipStream_t)stream);
     E2E_LAUNCH_CHECK("e2e_warp_photo_bwd");
     return E2E_OK;
 }
@@ -848,22 +774,17 @@ int e2e_warp_photo_bwd(const float* depth_tgt, const float* src, e2e_strides ss,
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------------------
-// the pose form of that launch, for e2e_warp_photo_bwd_pose (warp_photo_pose.hip, which has checked every argument): the kernel lives
-// here because it is the same template
+// what this file lends to the rest of the family (warp_photo_tile.h): the launches of kernels that live here.  The callers have checked
+// every argument.
 // ---------------------------------------------------------------------------------------------
-int64_t warp_photo_bwd_tiles(int H, int W) { return (int64_t)e2e_ceil_div(W, TW) * e2e_ceil_div(H, TH); }
+void warp_photo_reduce_launch(const float* partials, int nblk, int nsets, float scale, float* out, hipStream_t stream) {
+    hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(256), 0, stream, partials, nblk, nsets, scale, out);
+}
 
 void warp_photo_bwd_pose_launch(const float* depth_tgt, const float* src, e2e_strides ss, const float* tgt, e2e_strides ts, const float* K,
                                 const float* inv_K, const float* T, const float* synth, const float* valid, int use_mask, int padding_mode,
                                 int reg_kind, const float* reg_init_tgt, const float* reg_init_src, const float* depth_src, const float* g_loss,
                                 float* g_depth_tgt, float* g_depth_src, double* partials, int B, int H, int W, hipStream_t stream) {
-    const dim3 g = tile_grid(B, H, W);
-    if (padding_mode == E2E_PADDING_BORDER)
-        hipLaunchKernelGGL((k_warp_photo_bwd<E2E_PAD_BORDER, true>), g, dim3(TW, TH), 0, stream, depth_tgt, src, ss, tgt, ts, K, inv_K, T,
-                           synth, valid, use_mask, reg_kind, reg_init_tgt, reg_init_src, depth_src, g_loss, g_depth_tgt, g_depth_src, B, H,
-                           W, PoseOut<true>{partials});
-    else
-        hipLaunchKernelGGL((k_warp_photo_bwd<E2E_PAD_ZEROS, true>), g, dim3(TW, TH), 0, stream, depth_tgt, src, ss, tgt, ts, K, inv_K, T,
-                           synth, valid, use_mask, reg_kind, reg_init_tgt, reg_init_src, depth_src, g_loss, g_depth_tgt, g_depth_src, B, H,
-                           W, PoseOut<true>{partials});
+    warp_photo_bwd_launch<true>(depth_tgt, src, ss, tgt, ts, K, inv_K, T, synth, valid, use_mask, padding_mode, reg_kind, reg_init_tgt,
+                                reg_init_src, depth_src, g_loss, g_depth_tgt, g_depth_src, B, H, W, PoseOut<true>{partials}, stream);
 }

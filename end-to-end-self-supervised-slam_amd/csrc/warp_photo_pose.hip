@@ -3,20 +3,19 @@
 // of warp_photo.hip, which already forms the adjoint (gc0, gc1, gc2) of the projected point on its way to g_depth_tgt; with POSE it also
 // leaves Pbar = sum gc X^T | sum gc per workgroup as 12 float64 sums.  Here: the entry points, and the second stage that folds the
 // workgroups' sums per batch element in a fixed order and applies K^T, as k_project3d_bwd_T_final (pose_grad.hip) does for the operator.
+// The three-frame window (warp_photo_window.hip) runs the same second stage with one grid row per source.
 // No atomics anywhere: bitwise reproducible run to run.
 #include "e2e_common.h"
-#include "warp_photo_pose.h"
+#include "warp_photo_tile.h"
 
-#define WP_NSUM 12           // a 3x4 block: sum gc X^T (3x3) | sum gc (3x1), row-major
-
-// wave w of workgroup b folds sum w of batch element b: lane l adds the tiles l, l + 64, ... in order, then a fixed shuffle tree;
-// then g_T[k][j] = sum_{i<3} K[i][k] Pbar[i][j], k = 0..3 (T enters through P = (K T)[:3,:] only)
+// grid (B, S): wave w of workgroup (b, s) folds sum w of source s and batch element b: lane l adds the tiles l, l + 64, ... in order, then a
+// fixed shuffle tree; then g_T[k][j] = sum_{i<3} K[i][k] Pbar[i][j], k = 0..3 (T enters through P = (K T)[:3,:] only).  K is per batch element.
 __global__ __launch_bounds__(WP_NSUM * 64) void k_warp_photo_bwd_pose_final(const double* __restrict__ partials, int tiles, const float* __restrict__ K,
                                                                             float* __restrict__ g_T) {
     __shared__ double Pb[WP_NSUM];
-    const int b = blockIdx.x, w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int b = blockIdx.x, sb = blockIdx.y * gridDim.x + b, w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     double s = 0.0;
-    for (int i = lane; i < tiles; i += 64) s += partials[((int64_t)b * tiles + i) * WP_NSUM + w];
+    for (int i = lane; i < tiles; i += 64) s += partials[((int64_t)sb * tiles + i) * WP_NSUM + w];
     s = wave_sum_d(s);
     if (lane == 0) Pb[w] = s;
     __syncthreads();
@@ -24,15 +23,19 @@ __global__ __launch_bounds__(WP_NSUM * 64) void k_warp_photo_bwd_pose_final(cons
         const int k = threadIdx.x >> 2, j = threadIdx.x & 3;
         double v = 0.0;
         for (int i = 0; i < 3; ++i) v += (double)K[b * 16 + i * 4 + k] * Pb[i * 4 + j];
-        g_T[b * 16 + threadIdx.x] = (float)v;
+        g_T[sb * 16 + threadIdx.x] = (float)v;
     }
+}
+
+void warp_photo_pose_final_launch(const double* partials, int tiles, const float* K, float* g_T, int S, int B, hipStream_t stream) {
+    hipLaunchKernelGGL(k_warp_photo_bwd_pose_final, dim3(B, S), dim3(WP_NSUM * 64), 0, stream, partials, tiles, K, g_T);
 }
 
 extern "C" {
 
 int64_t e2e_warp_photo_bwd_pose_workspace_bytes(int B, int H, int W) {
     if (B <= 0 || H <= 0 || W <= 0) return 0;
-    return (int64_t)B * warp_photo_bwd_tiles(H, W) * WP_NSUM * 8;
+    return (int64_t)B * tile_count(H, W) * WP_NSUM * 8;
 }
 
 int e2e_warp_photo_bwd_pose(const float* depth_tgt, const float* src, e2e_strides src_strides, const float* tgt, e2e_strides tgt_strides,
@@ -40,21 +43,16 @@ int e2e_warp_photo_bwd_pose(const float* depth_tgt, const float* src, e2e_stride
                             int padding_mode, int reg_kind, const float* reg_init_tgt, const float* reg_init_src, const float* depth_src,
                             const float* g_loss, float* g_depth_tgt, float* g_depth_src, float* g_T, void* workspace, int B, int H, int W,
                             void* stream) {
-    E2E_REQUIRE(B > 0 && H > 1 && W > 1 && (int64_t)B * H * W < (1ll << 31), E2E_ERR_ARG, "e2e_warp_photo_bwd_pose: bad dims B=%d H=%d W=%d", B, H, W);
+    if (const int rc = warp_photo_check_args("e2e_warp_photo_bwd_pose", B, H, W,
+                                             depth_tgt && src && tgt && K && inv_K && T && synth && valid && g_loss && g_depth_tgt && g_T && workspace,
+                                             padding_mode, reg_kind, reg_init_tgt && reg_init_src && depth_src && g_depth_src))
+        return rc;
     E2E_REQUIRE(B <= 65535, E2E_ERR_ARG, "e2e_warp_photo_bwd_pose: B=%d exceeds the grid", B);
-    E2E_REQUIRE(depth_tgt && src && tgt && K && inv_K && T && synth && valid && g_loss && g_depth_tgt && g_T && workspace, E2E_ERR_ARG,
-                "e2e_warp_photo_bwd_pose: null pointer");
-    E2E_REQUIRE(padding_mode == E2E_PADDING_BORDER || padding_mode == E2E_PADDING_ZEROS, E2E_ERR_ARG,
-                "e2e_warp_photo_bwd_pose: padding_mode %d not supported (zeros|border)", padding_mode);
-    E2E_REQUIRE(reg_kind >= 0 && reg_kind <= 2, E2E_ERR_ARG, "e2e_warp_photo_bwd_pose: reg_kind %d (0 none, 1 l1, 2 l2)", reg_kind);
-    E2E_REQUIRE(!reg_kind || (reg_init_tgt && reg_init_src && depth_src && g_depth_src), E2E_ERR_ARG,
-                "e2e_warp_photo_bwd_pose: regulariser buffers missing");
     hipStream_t st = (hipStream_t)stream;
     warp_photo_bwd_pose_launch(depth_tgt, src, src_strides, tgt, tgt_strides, K, inv_K, T, synth, valid, use_mask, padding_mode, reg_kind,
                                reg_init_tgt, reg_init_src, depth_src, g_loss, g_depth_tgt, g_depth_src, (double*)workspace, B, H, W, st);
     E2E_LAUNCH_CHECK("e2e_warp_photo_bwd_pose");
-    hipLaunchKernelGGL(k_warp_photo_bwd_pose_final, dim3(B), dim3(WP_NSUM * 64), 0, st, (const double*)workspace, (int)warp_photo_bwd_tiles(H, W), K,
-                       g_T);
+    warp_photo_pose_final_launch((const double*)workspace, (int)tile_count(H, W), K, g_T, 1, B, st);
     E2E_LAUNCH_CHECK("e2e_warp_photo_bwd_pose(final)");
     return E2E_OK;
 }

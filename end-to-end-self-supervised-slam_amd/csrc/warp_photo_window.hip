@@ -19,85 +19,17 @@
 // the mask is a constant, the g_T convention of e2e_project3d_bwd_t (bottom row included), float64 fixed-order sums and no atomics: two runs
 // give the same bits.
 //
-// The small device functions (SSIM statistics, the three-channel bilinear sample, the tile constants) are restated from warp_photo.hip rather
-// than moved into a shared header: moving them reorders the existing kernels' instructions (lossgrad_tile.h explains the precedent).
+// The small device functions (SSIM statistics, the three-channel bilinear sample), the tile constants and the two second stages
+// (k_reduce_partials, k_warp_photo_bwd_pose_final) are the pair's, through warp_photo_tile.h: a function that is moved compiles to the
+// instructions it had (profiles/warp_family_refactor.txt).  The tile kernels' phase bodies stay written out here and in warp_photo.hip:
+// extracting written-out arithmetic into new functions does reorder a kernel (profiles/lossgrad_tile_refactor.txt §3).
 #include "e2e_common.h"
+#include "warp_photo_tile.h"
 
 namespace {
 
-constexpr int TW = 32, TH = 8, NTHREADS = TW * TH;
-constexpr int FP_LD = TW + 2;                          // forward planes: tile + 1-px halo, 34 floats a row (lanes read consecutive words)
-constexpr int FP_N = (TH + 2) * FP_LD;
-constexpr int BP_LD = TW + 4, BP_N = (TH + 4) * BP_LD; // backward image planes: tile + 2-px halo
-constexpr int BG_LD = TW + 2, BG_N = (TH + 2) * BG_LD; // backward statistics planes: tile + 1-px halo
-constexpr int WP_NSUM = 12;                            // a 3x4 block: sum gc X^T (3x3) | sum gc (3x1), row-major
+constexpr int FP_N = (TH + 2) * FP_LD, BP_N = (TH + 4) * BP_LD, BG_N = (TH + 2) * BG_LD;     // floats per LDS plane
 constexpr int MAX_S = 2;
-constexpr float SSIM_C1 = 1e-4f, SSIM_C2 = 9e-4f;      // 0.01**2, 0.03**2  losses.py:20-21
-
-struct Stats {
-    float mux, muy, sxx, syy, sxy;
-};
-// summation order = avg_pool2d's (rows outer, columns inner), then /9 -- losses.py:27-32
-__device__ __forceinline__ Stats window_stats(const float* xs, const float* ys, int ld) {
-    float sx = 0.f, sy = 0.f, sxx = 0.f, syy = 0.f, sxy = 0.f;
-#pragma unroll
-    for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-        for (int dx = 0; dx < 3; ++dx) {
-            const float a = xs[dy * ld + dx], b = ys[dy * ld + dx];
-            sx += a;
-            sy += b;
-            sxx += a * a;
-            syy += b * b;
-            sxy += a * b;
-        }
-    Stats s;
-    s.mux = sx / 9.f;
-    s.muy = sy / 9.f;
-    s.sxx = sxx / 9.f;
-    s.syy = syy / 9.f;
-    s.sxy = sxy / 9.f;
-    return s;
-}
-
-__device__ __forceinline__ float ssim_value(const Stats& s) {
-    const float sigx = s.sxx - s.mux * s.mux;
-    const float sigy = s.syy - s.muy * s.muy;
-    const float sigxy = s.sxy - s.mux * s.muy;
-    const float n = (2.f * s.mux * s.muy + SSIM_C1) * (2.f * sigxy + SSIM_C2);
-    const float d = (s.mux * s.mux + s.muy * s.muy + SSIM_C1) * (sigx + sigy + SSIM_C2);
-    return fminf(fmaxf((1.f - n / d) / 2.f, 0.f), 1.f);
-}
-
-// d(ssim_c)/d(mux, sxx, sxy) scaled by the upstream gradient g of ssim_c  
-__device__ __forceinline__ void ssim_partials(const Stats& s, float g, float& G1, float& G2, float& G3) {
-    const float sigx = s.sxx - s.mux * s.mux;
-    const float sigy = s.syy - s.muy * s.muy;
-    const float sigxy = s.sxy - s.mux * s.muy;
-    const float A1 = 2.f * s.mux * s.muy + SSIM_C1, A2 = 2.f * sigxy + SSIM_C2;
-    const float B1 = s.mux * s.mux + s.muy * s.muy + SSIM_C1, B2 = sigx + sigy + SSIM_C2;
-    const float S = (A1 * A2) / (B1 * B2);
-    const float t = (1.f - S) / 2.f;
-    const float gS = (t >= 0.f && t <= 1.f) ? -0.5f * g : 0.f;   // clamp passes grad on the closed interval
-    const float inv = 1.f / (B1 * B2);
-    G1 = gS * (2.f * s.muy * (A2 - A1) * inv - S * 2.f * s.mux * (1.f / B1 - 1.f / B2));
-    G2 = gS * (-S / B2);
-    G3 = gS * (2.f * A1 * inv);
-}
-
-__device__ __forceinline__ void sample3(const float* __restrict__ base, const e2e_strides& s, const Bilin& bl, float* out) {
-    const float* p = base + bl.y0 * s.sh + bl.x0 * s.sw;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float* pc = p + c * s.sc;
-        float acc = 0.f;
-        if (bl.in_y0 & bl.in_x0) acc += pc[0] * bl.wnw;
-        if (bl.in_y0 & bl.in_x1) acc += pc[s.sw] * bl.wne;
-        if (bl.in_y1 & bl.in_x0) acc += pc[s.sh] * bl.wsw;
-        if (bl.in_y1 & bl.in_x1) acc += pc[s.sh + s.sw] * bl.wse;
-        out[c] = acc;
-    }
-}
 
 // photometric value of the thread's pixel from two plane triples (x = prediction, y = target), w0 = the window's top-left element
 __device__ __forceinline__ float photo_value(const float (*x)[FP_N], const float (*y)[FP_N], int w0) {
@@ -224,21 +156,6 @@ __global__ __launch_bounds__(NTHREADS) void k_warp_photo_window_fwd(
     const int blk = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
     const float s0 = block_sum(val, red);
     if (tid == 0) partials[blk] = s0;
-}
-
-// second stage: fixed-order double-precision sum of the per-workgroup partials (1 workgroup), as k_reduce_partials of warp_photo.hip
-__global__ void k_warp_photo_window_reduce(const float* __restrict__ partials, int nblk, float scale, float* __restrict__ out) {
-    __shared__ double sh[4];
-    double acc = 0.0;
-    for (int i = threadIdx.x; i < nblk; i += blockDim.x) acc += (double)partials[i];
-    acc = wave_sum_d(acc);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += sh[w];
-        out[0] = (float)(t * (double)scale);
-    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -414,28 +331,6 @@ __global__ __launch_bounds__(NTHREADS) void k_warp_photo_window_bwd(
     if (live) g_dt[b * N + pix] = gd;
 }
 
-// wave w of workgroup (s, b) folds sum w of that source and batch element: lane l adds the tiles l, l + 64, ... in order, then a fixed shuffle
-// tree (the lane order of k_warp_photo_bwd_pose_final); then g_T[k][j] = sum_{i<3} K[i][k] Pbar[i][j], k = 0..3
-__global__ __launch_bounds__(WP_NSUM * 64) void k_warp_photo_window_bwd_pose_final(const double* __restrict__ partials, int tiles, int B,
-                                                                                   const float* __restrict__ K, float* __restrict__ g_T) {
-    __shared__ double Pb[WP_NSUM];
-    const int sb = blockIdx.x, b = sb % B, w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    double s = 0.0;
-    for (int i = lane; i < tiles; i += 64) s += partials[((int64_t)sb * tiles + i) * WP_NSUM + w];
-    s = wave_sum_d(s);
-    if (lane == 0) Pb[w] = s;
-    __syncthreads();
-    if (threadIdx.x < 16) {
-        const int k = threadIdx.x >> 2, j = threadIdx.x & 3;
-        double v = 0.0;
-        for (int i = 0; i < 3; ++i) v += (double)K[b * 16 + i * 4 + k] * Pb[i * 4 + j];
-        g_T[sb * 16 + threadIdx.x] = (float)v;
-    }
-}
-
-inline dim3 tile_grid(int B, int H, int W) { return dim3(e2e_ceil_div(W, TW), e2e_ceil_div(H, TH), B); }
-inline int64_t tile_count(int H, int W) { return (int64_t)e2e_ceil_div(W, TW) * e2e_ceil_div(H, TH); }
-
 // what both entry points refuse before they look at their own pointers
 int check_window(const char* name, int S, int B, int H, int W, int padding_mode, int terms) {
     E2E_REQUIRE(S >= 1 && S <= MAX_S, E2E_ERR_ARG, "%s: S=%d source frames (1 or 2)", name, S);
@@ -475,7 +370,7 @@ int e2e_warp_photo_window_fwd(const float* depth_tgt, const float* src0, const f
                            K, inv_K, T, tie_noise, synth, valid, select, pmap, use_mask, terms, workspace, S, B, H, W);
     E2E_LAUNCH_CHECK("e2e_warp_photo_window_fwd");
     const float scale = (float)(1.0 / ((double)B * H * W));
-    hipLaunchKernelGGL(k_warp_photo_window_reduce, dim3(1), dim3(256), 0, st, workspace, (int)(g.x * g.y * g.z), scale, loss_out);
+    warp_photo_reduce_launch(workspace, (int)(g.x * g.y * g.z), 1, scale, loss_out, st);
     E2E_LAUNCH_CHECK("e2e_warp_photo_window_fwd(reduce)");
     return E2E_OK;
 }
@@ -509,8 +404,7 @@ int e2e_warp_photo_window_bwd(const float* depth_tgt, const float* src0, const f
 #undef WINDOW_BWD
     E2E_LAUNCH_CHECK("e2e_warp_photo_window_bwd");
     if (g_T) {
-        hipLaunchKernelGGL(k_warp_photo_window_bwd_pose_final, dim3(S * B), dim3(WP_NSUM * 64), 0, st, (const double*)workspace,
-                           (int)tile_count(H, W), B, K, g_T);
+        warp_photo_pose_final_launch((const double*)workspace, (int)tile_count(H, W), K, g_T, S, B, st);
         E2E_LAUNCH_CHECK("e2e_warp_photo_window_bwd(final)");
     }
     return E2E_OK;

@@ -192,6 +192,24 @@ def photometric(prediction, target):
 
 
 # ---------------------------------------------------------------------------------------------
+def _check_warp_inputs(fn, depth_tgt, srcs, tgt, K, inv_K, n_poses=None):
+    """What warp_photometric and warp_photometric_window (`fn`) refuse alike: intrinsics that require grad, a depth_tgt that is not (B,1,H,W),
+    for the window (n_poses given) anything but 1 or 2 sources and as many poses, frames that are not (B,3,H,W).  Returns (B, H, W)."""
+    if torch.is_grad_enabled():
+        for n, t in (("K", K), ("inv_K", inv_K)):
+            if torch.is_tensor(t) and t.requires_grad:
+                raise NotImplementedError(f"{fn}: {n} requires grad, and the fused kernels have no gradient with respect to the intrinsics")
+    if depth_tgt.dim() != 4 or depth_tgt.shape[1] != 1:
+        raise ValueError(f"depth_tgt: expected (B,1,H,W), got {tuple(depth_tgt.shape)}")
+    B, _, H, W = depth_tgt.shape
+    if n_poses is not None and (len(srcs) not in (1, 2) or n_poses != len(srcs)):
+        raise ValueError(f"{fn}: expected 1 or 2 source frames and as many poses, got {len(srcs)} and {n_poses}")
+    for n, t in [("source_frame", s) for s in srcs] + [("target_frame", tgt)]:
+        if tuple(t.shape) != (B, 3, H, W):
+            raise ValueError(f"{n}: expected ({B},3,{H},{W}), got {tuple(t.shape)}")
+    return B, H, W
+
+
 class _WarpPhotometric(torch.autograd.Function):
     @staticmethod
     def forward(ctx, depth_tgt, depth_src, init_tgt, init_src, src, tgt, K, inv_K, T, pad, use_mask, reg_kind, want_pmap):
@@ -255,16 +273,7 @@ def warp_photometric(depth_tgt, src, tgt, K, inv_K, T, padding_mode="border", us
     the T that was passed, so a pose expanded over the batch gets the sum).  The frames, init_tgt / init_src and the outputs synth, valid
     and pmap are constants.  K and inv_K are constants too: one that requires grad raises NotImplementedError.
     reference: online_adaption.py:412-455, :544-564, :482-511, :612-623."""
-    if torch.is_grad_enabled():
-        for n, t in (("K", K), ("inv_K", inv_K)):
-            if torch.is_tensor(t) and t.requires_grad:
-                raise NotImplementedError(f"warp_photometric: {n} requires grad, and the fused kernels have no gradient with respect to the intrinsics")
-    if depth_tgt.dim() != 4 or depth_tgt.shape[1] != 1:
-        raise ValueError(f"depth_tgt: expected (B,1,H,W), got {tuple(depth_tgt.shape)}")
-    B, _, H, W = depth_tgt.shape
-    for n, t in (("source_frame", src), ("target_frame", tgt)):
-        if tuple(t.shape) != (B, 3, H, W):
-            raise ValueError(f"{n}: expected ({B},3,{H},{W}), got {tuple(t.shape)}")
+    B, H, W = _check_warp_inputs("warp_photometric", depth_tgt, [src], tgt, K, inv_K)
     rk = {None: 0, "l1": 1, "l2": 2}.get(reg_kind, -1)
     if rk < 0:
         raise ValueError("please specify a correct norm")          # losses.py:146
@@ -347,20 +356,9 @@ def warp_photometric_window(depth_tgt, srcs, tgt, K, inv_K, Ts, padding_mode="bo
 
     Differentiated: depth_tgt and every T (the gradient has the shape of the T that was passed, so a pose expanded over the batch gets the
     sum).  Frames, masks, tie_noise and the other outputs are constants; K or inv_K requiring grad raises NotImplementedError."""
-    if torch.is_grad_enabled():
-        for n, t in (("K", K), ("inv_K", inv_K)):
-            if torch.is_tensor(t) and t.requires_grad:
-                raise NotImplementedError(f"warp_photometric_window: {n} requires grad, and the fused kernels have no gradient with respect to the intrinsics")
-    if depth_tgt.dim() != 4 or depth_tgt.shape[1] != 1:
-        raise ValueError(f"depth_tgt: expected (B,1,H,W), got {tuple(depth_tgt.shape)}")
-    B, _, H, W = depth_tgt.shape
     srcs, Ts = list(srcs), list(Ts)
     S = len(srcs)
-    if S not in (1, 2) or len(Ts) != S:
-        raise ValueError(f"warp_photometric_window: expected 1 or 2 source frames and as many poses, got {S} and {len(Ts)}")
-    for n, t in [("source_frame", s) for s in srcs] + [("target_frame", tgt)]:
-        if tuple(t.shape) != (B, 3, H, W):
-            raise ValueError(f"{n}: expected ({B},3,{H},{W}), got {tuple(t.shape)}")
+    B, H, W = _check_warp_inputs("warp_photometric_window", depth_tgt, srcs, tgt, K, inv_K, n_poses=len(Ts))
     if tie_noise is not None and tuple(tie_noise.shape) != (B, S, H, W):
         raise ValueError(f"tie_noise: expected ({B},{S},{H},{W}), got {tuple(tie_noise.shape)}")
     terms = (TERM_AUTO_MASKING if auto_masking else 0) | (TERM_MIN_REPROJECTION if min_reprojection else 0)

@@ -1,7 +1,12 @@
 """Host-only: what tests/warp_window_ref.py claims about its cases, proved for the generator and the salts as they are -- the 2 % cap on every
 case, no pixel in the band of the validity mask, an empty exclusion set on every pose case, both winners in every non-trivial mode, exact
 ties present (and compared), the float32 and float64 selections equal outside the near-ties, and the reference's own selection logic
-(torch.cat + torch.min over dim 1, as oracle.train_depth forms it) equal to the module's first minimum, value, index and gradient."""
+(torch.cat + torch.min over dim 1, as oracle.train_depth forms it) equal to the module's first minimum, value, index and gradient.  And, over
+the sources: the device code the window shares with the pair is defined once."""
+import glob
+import os
+import re
+
 import pytest
 import torch
 
@@ -123,3 +128,20 @@ def test_crafted_case_has_one_winner_everywhere():
         b = Wr.maps(case["scene"], case["pad"], case["use_mask"], F64, srcs=case["srcs"])
         g, = torch.autograd.grad(b["rep"][:, 1 - winner].mean(), b["T"][1 - winner])
         assert float(g.abs().max()) > 0
+
+
+def test_shared_device_code_of_the_pair_family_is_defined_once():
+    """across csrc/*.hip and csrc/*.h: one struct Stats, one definition each of window_stats, ssim_value, ssim_partials and sample3, one
+    __global__ whose name ends in reduce_partials and one whose name ends in bwd_pose_final (the window uses the pair's)"""
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "end-to-end-self-supervised-slam_amd", "csrc")
+    files = sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h")))
+    assert len(files) >= 20                                                            # 25 at the time of writing: the glob still finds them
+    text = {os.path.basename(f): open(f).read() for f in files}
+    kernel = r"__global__\s+(?:__launch_bounds__\s*\([^)]*\)\s+)?void\s+\w*%s\s*\("
+    patterns = {"struct Stats": r"\bstruct\s+Stats\b\s*\{", "reduce_partials": kernel % "reduce_partials", "bwd_pose_final": kernel % "bwd_pose_final"}
+    for fn in ("window_stats", "ssim_value", "ssim_partials", "sample3"):
+        patterns[fn + "("] = r"^__device__[^;{(\n]*\b" + fn + r"\s*\([^;{]*\{"          # a definition: a body follows the parameter list
+    for what, pat in patterns.items():
+        found = [name for name, src in text.items() for _ in re.finditer(pat, src, re.M)]
+        assert len(found) == 1, f"{what}: defined {len(found)} times, in {found}"
+    assert "k_warp_photo_bwd_pose_final" in text["warp_photo_pose.hip"] and "k_reduce_partials" in text["warp_photo.hip"]
