@@ -1,5 +1,5 @@
 // warp_photo_tile.h -- what the 32x8 warp-photometric family shares: the pair (warp_photo.hip), its pose gradient (warp_photo_pose.hip) and
-// the three-frame window (warp_photo_window.hip).  Tile constants, the SSIM device functions, the three-channel sample, the pair's host
+// the three-frame window (warp_photo_window.hip) and the window with the geometric-consistency term (warp_photo_geo.hip).  Tile constants, the SSIM device functions, the three-channel sample, the pair's host
 // argument checks, and the host launchers of the two second stages, each of which lives in one file and serves the others.
 // The device functions were MOVED here as they stood: a function that already exists compiles to the same instructions wherever it is
 // defined (profiles/warp_family_refactor.txt: 0 differing lines in every tile kernel).  Arithmetic that is written out in a kernel is not

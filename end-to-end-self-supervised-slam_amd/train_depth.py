@@ -18,7 +18,9 @@ e2e_warp_photo_* pair instead of the operator-by-operator composition -- `fused_
 estimated poses too (`DATA.use_gt_pose: False`): the pair's backward then also returns the gradient with respect to the relative pose
 (e2e_warp_photo_bwd_pose), which autograd carries on through the odometry.  The three-frame window, LOSS.min_reprojection and
 LOSS.auto_masking run on the window form of the pair (e2e_warp_photo_window_fwd / _bwd: the candidates and the per-pixel minimum of
-:621-662 in the kernel, a gradient for every pose); LOSS.geometric keeps the operators.
+:621-662 in the kernel, a gradient for every pose).  LOSS.geometric runs on the pair that carries the geometric-consistency term
+(e2e_warp_photo_geo_fwd / _bwd: the image sampled with align_corners=True and the source depth with False, as :570-573 do; gradients for the
+target depth, every source depth and every pose; the `mask.sum() > 10000` gate of losses.py:84-95 decided on the device).
 
 `MODEL.depth_network` selects the depth network as in the reference (train_depth.py:124-179): `indoor` is DispResNet_Indoor, `monodepth2`
 is ResnetEncoder + DepthDecoder with a sigmoid disparity at every scale of `DATA.scales`, turned into depth by convert_disp_to_depth
@@ -375,19 +377,21 @@ class Depth_Estimation:
     def _fused_ok(self, poses=None):
         # poses with a graph (DATA.use_gt_pose: False) stay on the fused pair: its backward returns the gradient for T as well
         # (e2e_warp_photo_bwd_pose).  The three-frame window, LOSS.min_reprojection and LOSS.auto_masking take the window form of the
-        # pair (e2e_warp_photo_window_fwd / _bwd), which returns a gradient for every pose.  LOSS.geometric takes the operators.
+        # pair (e2e_warp_photo_window_fwd / _bwd), which returns a gradient for every pose.  LOSS.geometric takes the pair that carries
+        # the term (e2e_warp_photo_geo_fwd / _bwd), for every window: faster than the operators in every measured row.
         lo = self.args.LOSS
-        return self.fused_losses and lo.photometric_mask is not None and not lo.geometric
+        return self.fused_losses and lo.photometric_mask is not None
 
     def compute_losses_fused(self, inputs):
         """compute_losses with the image-space part as ONE fused forward (warp + mask + SSIM/L1 + mean) and ONE fused backward: the
         reference's default flag set on a two-frame window is e2e_warp_photo_fwd / _bwd; the three-frame window, LOSS.min_reprojection and
         LOSS.auto_masking are e2e_warp_photo_window_fwd / _bwd (candidates and per-pixel minimum of train_depth.py:621-662 in the
-        kernel).  Then the remaining terms."""
+        kernel); LOSS.geometric, on any window, is e2e_warp_photo_geo_fwd / _bwd, which adds the geometric-consistency term of every
+        source.  Then the remaining terms."""
         a = self.args
         frames = a.DATA.frames[1:]
         self.optimizer.zero_grad()
-        if len(frames) == 2 or a.LOSS.min_reprojection or a.LOSS.auto_masking:
+        if len(frames) == 2 or a.LOSS.min_reprojection or a.LOSS.auto_masking or a.LOSS.geometric:
             noise = None
             if a.LOSS.min_reprojection and a.LOSS.auto_masking:
                 B, _, H, W = inputs["target_depth"].shape
@@ -396,12 +400,15 @@ class Depth_Estimation:
                                               inputs["K"], inputs["Inverse_K"], [inputs["T", f] for f in frames],
                                               padding_mode=a.MODEL.padding_mode, use_mask=bool(a.LOSS.photometric_mask),
                                               min_reprojection=bool(a.LOSS.min_reprojection), auto_masking=bool(a.LOSS.auto_masking),
-                                              tie_noise=noise)
+                                              tie_noise=noise, geometric=bool(a.LOSS.geometric),
+                                              depth_srcs=[inputs["source_depth", f] for f in frames] if a.LOSS.geometric else None)
         else:
             out = ops.warp_photometric(inputs["target_depth"], inputs["source_frame", frames[0]], inputs["target_frame"], inputs["K"],
                                        inputs["Inverse_K"], inputs["T", frames[0]], padding_mode=a.MODEL.padding_mode,
                                        use_mask=bool(a.LOSS.photometric_mask))
         loss = out["photometric"]
+        if a.LOSS.geometric:
+            loss = loss + out["geometric"].mean() * a.LOSS.geometric_weight
         loss = self._add_common_terms(loss, inputs, None)
         loss.backward()
         self.optimizer.step()
@@ -431,7 +438,7 @@ class Depth_Estimation:
 
     def _add_common_terms(self, loss, inputs, outputs):
         a = self.args
-        if a.LOSS.geometric:
+        if a.LOSS.geometric and outputs is not None:                                  # the fused route (outputs is None) has added the term
             geometric = self.compute_geometric_loss(outputs).mean()
             loss = loss + geometric * a.LOSS.geometric_weight
         if a.LOSS.smoothness:

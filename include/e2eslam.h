@@ -285,7 +285,7 @@ int e2e_warp_photo_terms_lossgrad(const float* depth_tgt, const float* depth_src
  * launch over the sources, + one final kernel of S B workgroups when g_T is asked for.
  *   src0, src1          the source frames, (B,3,H,W) through the SAME strides (src1 may be NULL with S = 1); tgt likewise through its own
  *   T (S,B,4,4)         the relative pose of each source;  K, inv_K (B,4,4)
- *   terms               E2E_TERM_AUTO_MASKING | E2E_TERM_MIN_REPROJECTION (E2E_TERM_GEOMETRIC is refused: that term stays on the operators)
+ *   terms               E2E_TERM_AUTO_MASKING | E2E_TERM_MIN_REPROJECTION (E2E_TERM_GEOMETRIC is refused: that term is e2e_warp_photo_geo_fwd / _bwd)
  *   For source s with its validity mask m_s (1 when use_mask == 0):
  *     R_s = photometric(synth_s m_s, tgt m_s);   I_s = photometric(src_s m_s, tgt m_s), src_s read at the target pixel.
  *   Candidates, in this order:  identity candidates, only with AUTO_MASKING -- with MIN_REPROJECTION  I_0 + n_0, ..., I_{S-1} + n_{S-1}
@@ -319,6 +319,45 @@ int e2e_warp_photo_window_bwd(const float* depth_tgt, const float* src0, const f
                               const float* T, const float* synth, const float* valid, const int* select, int use_mask,
                               int padding_mode, int terms, const float* g_loss, float* g_depth_tgt, float* g_T,
                               void* workspace, int S, int B, int H, int W, void* stream);
+
+/* The window pair WITH the geometric-consistency term of LOSS.geometric (train_depth.py:558-576, view_synthesis.py:54-78, losses.py:84-95).
+ * Everything of e2e_warp_photo_window_fwd / _bwd holds (candidates, order, select, pmap, the NaN rule, tie_noise, g_T), with one difference
+ * on the photometric side: the source image is sampled with align_corners=True (sic, as the reference does under this flag), so synth
+ * holds that sample and its adjoint uses that index; the identity maps still read the source at the target pixel.
+ *   depth_src0, depth_src1 (B,H,W) contiguous: the depth of each source frame (depth_src1 may be NULL with S = 1)
+ *   Per source s and target pixel, with c the projected point:  wd = max(c2, 1e-3);  id = the bilinear sample of depth_src_s on the same grid
+ *     with align_corners=False and the same padding mode;  diff = clamp(|wd - id| / (wd + id), 0, 1);  valid_s = max|grid| <= 1 whatever use_mask.
+ *   geo_count[s] int32 = n_s = the number of valid projections of source s over the batch (an exact integer count of the fp32 decision);
+ *   loss_out[0] = the window's photometric loss;  loss_out[1 + s] = G_s = sum(diff valid_s) / n_s if n_s > geo_min_valid, else 0 (the
+ *     reference's gate is geo_min_valid = 10000).  Fixed-order float64 second stages.
+ *   Backward: gradients of g_loss[0] loss[0] + sum_s g_loss[1 + s] G_s.  Where the gate of s is open (geo_count[s] > geo_min_valid, read on
+ *     the device) a valid pixel adds, with e = g_loss[1 + s] / n_s and sg = sign(wd - id) (0 at 0; the clamp passes on [0,1]):
+ *     e sg 2 id / (wd + id)^2 to c2 where c2 >= 1e-3, and -e sg 2 wd / (wd + id)^2 to id, which goes to the four taps of depth_src_s
+ *     (e2e_grid_sample_bwd's g_input conventions) and to the sampling position (its g_grid conventions, align_corners=False) and on through
+ *     z = c2 + 1e-7.  All of it enters the same per-pixel adjoint as the photometric part, so g_depth_tgt and g_T carry the term.
+ *     A closed gate, or g_loss[1 + s] == 0, skips the piece: g_depth_tgt and g_T have the bits of the photometric part, g_depth_src[s] is 0.
+ *   g_depth_src (S,B,H,W): fully written.  The scatter is summed as 2^-48 fixed-point integers (order-independent, as in
+ *     e2e_grid_sample_bwd_exact): a contribution that is not finite or not below 4096 turns that source's plane into NaN.
+ *   Every output is bitwise reproducible run to run; g_T = NULL gives the same g_depth_tgt and g_depth_src bits.
+ *   workspace: forward e2e_warp_photo_geo_workspace_floats = (1 + 2 S) B ceil(H/8) ceil(W/32) floats, all written; backward
+ *     e2e_warp_photo_geo_bwd_workspace_bytes = 8 (S B H W + S) + 96 S B ceil(H/8) ceil(W/32) bytes: the fixed-point sums, zeroed by the call,
+ *     then the pose sums, written only with g_T.  Both are needed (0 for a non-positive size or an S outside 1..2).
+ *   A refused call (the window's refusals, a NULL depth_src0, a NULL depth_src1 with S = 2, a NULL geo_count, g_depth_src or workspace,
+ *     geo_min_valid < 0, E2E_TERM_GEOMETRIC or an unknown bit in terms) returns E2E_ERR_ARG before any launch and writes nothing. */
+int64_t e2e_warp_photo_geo_workspace_floats(int S, int B, int H, int W);
+int e2e_warp_photo_geo_fwd(const float* depth_tgt, const float* depth_src0, const float* depth_src1, const float* src0,
+                           const float* src1, e2e_strides src_strides, const float* tgt, e2e_strides tgt_strides,
+                           const float* K, const float* inv_K, const float* T, const float* tie_noise, float* synth,
+                           float* valid, int* select, float* pmap, int* geo_count, int use_mask, int padding_mode,
+                           int terms, int geo_min_valid, float* loss_out, float* workspace, int S, int B, int H, int W,
+                           void* stream);
+int64_t e2e_warp_photo_geo_bwd_workspace_bytes(int S, int B, int H, int W);
+int e2e_warp_photo_geo_bwd(const float* depth_tgt, const float* depth_src0, const float* depth_src1, const float* src0,
+                           const float* src1, e2e_strides src_strides, const float* tgt, e2e_strides tgt_strides,
+                           const float* K, const float* inv_K, const float* T, const float* synth, const float* valid,
+                           const int* select, const int* geo_count, int use_mask, int padding_mode, int terms,
+                           int geo_min_valid, const float* g_loss, float* g_depth_tgt, float* g_depth_src, float* g_T,
+                           void* workspace, int S, int B, int H, int W, void* stream);
 
 /* online_adaption.py:600-610 + losses.py:119-132 for ONE frame: edge-aware first-order smoothness of
  * disp / (mean(disp) + 1e-7) with the edges of img (3,H,W through strides; the batch stride is not used), fused
