@@ -3,7 +3,8 @@
 // of warp_photo.hip, which already forms the adjoint (gc0, gc1, gc2) of the projected point on its way to g_depth_tgt; with POSE it also
 // leaves Pbar = sum gc X^T | sum gc per workgroup as 12 float64 sums.  Here: the entry points, and the second stage that folds the
 // workgroups' sums per batch element in a fixed order and applies K^T, as k_project3d_bwd_T_final (pose_grad.hip) does for the operator.
-// The three-frame window (warp_photo_window.hip) runs the same second stage with one grid row per source.
+// The three-frame window, with or without the geometric-consistency term (k_warp_photo_window_bwd<pad, POSE, GEO> of warp_photo_window.hip),
+// runs the same second stage with one grid row per source.
 // No atomics anywhere: bitwise reproducible run to run.
 #include "e2e_common.h"
 #include "warp_photo_tile.h"

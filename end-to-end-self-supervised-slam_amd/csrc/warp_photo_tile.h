@@ -1,6 +1,7 @@
 // warp_photo_tile.h -- what the 32x8 warp-photometric family shares: the pair (warp_photo.hip), its pose gradient (warp_photo_pose.hip) and
-// the three-frame window (warp_photo_window.hip) and the window with the geometric-consistency term (warp_photo_geo.hip).  Tile constants, the SSIM device functions, the three-channel sample, the pair's host
-// argument checks, and the host launchers of the two second stages, each of which lives in one file and serves the others.
+// the three-frame window with and without the geometric-consistency term (warp_photo_window.hip: one kernel template pair for both).  Tile
+// constants, the SSIM device functions, the three-channel sample, the pair's host argument checks, and the host launchers of the two second
+// stages, each of which lives in one file and serves the others.
 // The device functions were MOVED here as they stood: a function that already exists compiles to the same instructions wherever it is
 // defined (profiles/warp_family_refactor.txt: 0 differing lines in every tile kernel).  Arithmetic that is written out in a kernel is not
 // extracted into new functions: that does reorder the kernel (profiles/lossgrad_tile_refactor.txt §3).

@@ -1,9 +1,13 @@
 // warp_photo_window.hip -- the fused warp-photometric pair over a window of S = 1 or 2 source frames (DATA.frames: [0,-1,1], [0,-1], [0,1]) with
-// the candidate / minimum logic of the reference's train_depth.py:621-662 (LOSS.auto_masking, LOSS.min_reprojection).  One tile launch forward
-// (+ the fixed-order reduction of the workgroups' partial sums), one tile launch backward (+ a final kernel per source and batch element when
-// the gradient with respect to the poses is asked for).
+// the candidate / minimum logic of the reference's train_depth.py:621-662 (LOSS.auto_masking, LOSS.min_reprojection), and the same window WITH
+// the geometric-consistency term of the reference's LOSS.geometric branch (train_depth.py:558-576, view_synthesis.py:54-78, losses.py:84-95).
+// ONE forward template <PAD, GEO> and ONE backward template <PAD, POSE, GEO> serve e2e_warp_photo_window_* (GEO = false) and
+// e2e_warp_photo_geo_* (GEO = true): the text is the geometric kernel's, and the compile-time constant GEO deletes the geometric pieces
+// from the window's instantiation (profiles/warp_window_geo_merge.txt).  One tile launch forward (+ the fixed-order reduction of the workgroups'
+// partial sums), one tile launch backward (+ a final kernel per source and batch element when the gradient with respect to the poses is
+// asked for).
 //
-// Semantics.  For source s with its validity mask m_s (1 everywhere when use_mask == 0):
+// Semantics of the window.  For source s with its validity mask m_s (1 everywhere when use_mask == 0):
 //     R_s = photometric(synth_s m_s, tgt m_s)                    the reprojection map
 //     I_s = photometric(src_s m_s, tgt m_s)                      the identity map: src_s read at the target pixel
 // Candidate list, in this order:
@@ -19,6 +23,32 @@
 // the mask is a constant, the g_T convention of e2e_project3d_bwd_t (bottom row included), float64 fixed-order sums and no atomics: two runs
 // give the same bits.
 //
+// Semantics with the geometric term (GEO).  The photometric side is the window's to the letter (candidates, order, select, pmap, NaN rule,
+// tie_noise, the g_T convention), with ONE difference: under LOSS.geometric the reference samples the source image with align_corners=True
+// (sic), so synth and its adjoint use that index.
+//
+// The geometric term of source s, per target pixel with c = d M [x,y,1]^T + p4 and the grid of z = c2 + 1e-7:
+//     wd = max(c2, 1e-3);   id = bilinear sample of depth_src_s on the same grid with align_corners=False (same padding mode);
+//     diff = clamp(|wd - id| / (wd + id), 0, 1);   n_s = sum(valid_s) over the batch;   G_s = sum(diff valid_s) / n_s if n_s > geo_min_valid, else 0.
+// valid_s = max|grid| <= 1 whatever use_mask says.  The piece is per pixel: no halo and no LDS plane.  n_s is an integer sum of the fp32
+// validity decision (per-workgroup int partials, added by k_geo_final); the diff sums are float per workgroup in the fixed order of
+// block_sum, then float64 in a fixed order.
+//
+// Backward of g_loss[0] loss[0] + sum_s g_loss[1+s] G_s.  The geometric adjoint of a valid pixel, only when the gate of s is open
+// (geo_count[s] > geo_min_valid, read on the device):  e = g_loss[1+s] / n_s,  sg = sign(wd - id) (0 at 0), the clamp passes on [0,1];
+//     d/dwd = e sg 2 id / (wd + id)^2, reaching c2 where c2 >= 1e-3;     d/did = -e sg 2 wd / (wd + id)^2, which goes
+//     (i) to the four taps of depth_src_s (e2e_grid_sample_bwd's g_input conventions) and (ii) to the sampling position (its g_grid
+//     conventions: align_corners=False scaling, zero slope under an active border clamp) and from there through z into gc.
+// Both add into the gc of the photometric adjoint, so g_depth_tgt = gc . r and the 12 float64 pose sums carry the term.  A closed gate -- or
+// an upstream g_loss[1+s] of exactly 0 -- skips the piece: g_depth_tgt and g_T then have the bits of the photometric part alone and
+// g_depth_src[s] is all zero.
+//
+// (i) is a data-dependent scatter.  It is made order-independent as in e2e_grid_sample_bwd_exact: 2^-48 fixed-point int64 atomic adds into
+// workspace zeroed by the call, then a conversion pass that writes all of g_depth_src; a contribution that is not finite or not below 4096
+// is not added and turns that source's plane into NaN (one poison word per source).  Size: 4 taps x 8 B per valid pixel, 19.7 MB at
+// 480x640 with S = 2, about 15 us at the chip-wide atomic rate of 1.3 TB/s -- below the tile kernel's own time, and spread over rows as
+// the sampling positions are.  Two runs give the same bits on every output.
+//
 // The small device functions (SSIM statistics, the three-channel bilinear sample), the tile constants and the two second stages
 // (k_reduce_partials, k_warp_photo_bwd_pose_final) are the pair's, through warp_photo_tile.h: a function that is moved compiles to the
 // instructions it had (profiles/warp_family_refactor.txt).  The tile kernels' phase bodies stay written out here and in warp_photo.hip:
@@ -30,6 +60,7 @@ namespace {
 
 constexpr int FP_N = (TH + 2) * FP_LD, BP_N = (TH + 4) * BP_LD, BG_N = (TH + 2) * BG_LD;     // floats per LDS plane
 constexpr int MAX_S = 2;
+constexpr double FX_ONE = 281474976710656.0;                                                  // 2^48
 
 // photometric value of the thread's pixel from two plane triples (x = prediction, y = target), w0 = the window's top-left element
 __device__ __forceinline__ float photo_value(const float (*x)[FP_N], const float (*y)[FP_N], int w0) {
@@ -57,18 +88,46 @@ struct FirstMin {
     }
 };
 
+// the four taps of a one-channel (H,W) plane at one position, zeros outside
+struct Taps {
+    float nw, ne, sw, se;
+};
+__device__ __forceinline__ Taps load_taps(const float* __restrict__ plane, int W, const Bilin& bl) {
+    const float* p = plane + (int64_t)bl.y0 * W + bl.x0;
+    Taps t;
+    t.nw = (bl.in_y0 & bl.in_x0) ? p[0] : 0.f;
+    t.ne = (bl.in_y0 & bl.in_x1) ? p[1] : 0.f;
+    t.sw = (bl.in_y1 & bl.in_x0) ? p[W] : 0.f;
+    t.se = (bl.in_y1 & bl.in_x1) ? p[W + 1] : 0.f;
+    return t;
+}
+
+// the workgroup's integer sum, valid in thread 0; `scratch` holds NTHREADS / 64 ints and is this call's alone
+__device__ __forceinline__ int block_sum_i(int v, int* scratch) {
+    const int tid = threadIdx.y * TW + threadIdx.x;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    if ((tid & 63) == 0) scratch[tid >> 6] = v;
+    __syncthreads();
+    return tid == 0 ? ((scratch[0] + scratch[1]) + scratch[2]) + scratch[3] : 0;
+}
+
 // ---------------------------------------------------------------------------------------------
 // forward: per source warp + mask into the LDS planes (lx = synth m, ly = tgt m, ls = src m at the target pixel), R_s and I_s of the own
-// pixel into registers; a barrier, the next source over the same planes; then the candidates, select, pmap and one partial sum per workgroup
+// pixel into registers; a barrier, the next source over the same planes; then the candidates, select, pmap and one partial sum per workgroup.
+// GEO: the image index is align_corners=True; the thread that projects a real tile-interior pixel for the planes also takes that pixel's
+// depth sample and adds diff | 1 to its own sums of source s.  Without GEO dsrc0 / dsrc1 / gpart / cpart are not read (the window passes NULL).
 // ---------------------------------------------------------------------------------------------
-template <int PAD>
+template <int PAD, bool GEO>
 __global__ __launch_bounds__(NTHREADS) void k_warp_photo_window_fwd(
-    const float* __restrict__ depth, const float* __restrict__ src0, const float* __restrict__ src1, e2e_strides ss,
-    const float* __restrict__ tgt, e2e_strides ts, const float* __restrict__ K, const float* __restrict__ invK,
-    const float* __restrict__ T, const float* __restrict__ noise, float* __restrict__ synth, float* __restrict__ valid,
-    int* __restrict__ select, float* __restrict__ pmap, int use_mask, int terms, float* __restrict__ partials, int S, int B, int H, int W) {
+    const float* __restrict__ depth, const float* __restrict__ dsrc0, const float* __restrict__ dsrc1, const float* __restrict__ src0,
+    const float* __restrict__ src1, e2e_strides ss, const float* __restrict__ tgt, e2e_strides ts, const float* __restrict__ K,
+    const float* __restrict__ invK, const float* __restrict__ T, const float* __restrict__ noise, float* __restrict__ synth,
+    float* __restrict__ valid, int* __restrict__ select, float* __restrict__ pmap, int use_mask, int terms, float* __restrict__ partials,
+    float* __restrict__ gpart, int* __restrict__ cpart, int S, int B, int H, int W) {
     __shared__ float lx[3][FP_N], ly[3][FP_N], ls[3][FP_N];
-    __shared__ float red[NTHREADS / 64];
+    __shared__ float red[GEO ? 1 + MAX_S : 1][NTHREADS / 64];
+    __shared__ int redi[GEO ? MAX_S : 1][NTHREADS / 64];
     const int b = blockIdx.z, tx0 = blockIdx.x * TW, ty0 = blockIdx.y * TH;
     const int tid = threadIdx.y * TW + threadIdx.x;
     const int64_t N = (int64_t)H * W;
@@ -79,6 +138,8 @@ __global__ __launch_bounds__(NTHREADS) void k_warp_photo_window_fwd(
     const bool live = px < W && py < H;
     const int w0 = threadIdx.y * FP_LD + threadIdx.x;
     float Rv[MAX_S] = {0.f, 0.f}, Iv[MAX_S] = {0.f, 0.f};
+    float gsum[MAX_S] = {0.f, 0.f};
+    int gcnt[MAX_S] = {0, 0};
 
 #pragma unroll
     for (int s = 0; s < MAX_S; ++s) {
@@ -86,6 +147,7 @@ __global__ __launch_bounds__(NTHREADS) void k_warp_photo_window_fwd(
         const int64_t sbi = (int64_t)s * B + b;
         const Geom g = load_geom(K + b * 16, invK + b * 16, T + sbi * 16);
         const float* sb = (s ? src1 : src0) + b * ss.sb;
+        const float* dsb = (s ? dsrc1 : dsrc0) + b * N;
         if (s) __syncthreads();                          // every thread has taken source s-1's values out of the planes
         for (int i = tid; i < FP_N; i += NTHREADS) {
             const int l_y = i / FP_LD, l_x = i % FP_LD;
@@ -93,10 +155,11 @@ __global__ __launch_bounds__(NTHREADS) void k_warp_photo_window_fwd(
             float xv[3] = {0.f, 0.f, 0.f}, yv[3] = {0.f, 0.f, 0.f}, sv[3] = {0.f, 0.f, 0.f};
             if (gx >= -1 && gx <= W && gy >= -1 && gy <= H) {
                 const int qx = reflect1(gx, W), qy = reflect1(gy, H);
-                const Proj p = project_pixel(g, (float)qx, (float)qy, dep[(int64_t)qy * W + qx], W, H);
+                const float dq = dep[(int64_t)qy * W + qx];
+                const Proj p = project_pixel(g, (float)qx, (float)qy, dq, W, H);
                 float mx, my;
-                const float ix = source_index<PAD, false>(p.gx, W, mx);
-                const float iy = source_index<PAD, false>(p.gy, H, my);
+                const float ix = source_index<PAD, GEO>(p.gx, W, mx);       // GEO: align_corners=True for the image (train_depth.py:570)
+                const float iy = source_index<PAD, GEO>(p.gy, H, my);
                 const Bilin bl = bilinear_setup(ix, iy, W, H);
                 float sm[3];
                 sample3(sb, ss, bl, sm);
@@ -113,6 +176,19 @@ __global__ __launch_bounds__(NTHREADS) void k_warp_photo_window_fwd(
                     valid[sbi * N + (int64_t)qy * W + qx] = p.mask;
 #pragma unroll
                     for (int c = 0; c < 3; ++c) synth[(sbi * 3 + c) * N + (int64_t)qy * W + qx] = sm[c];
+                    if (GEO && p.mask != 0.f) {          // the geometric term of this pixel: the depth sample with align_corners=False
+                        const float c2 = fmaf(dq, p.r[2], g.P[11]);
+                        const float wd = fmaxf(c2, 1e-3f);
+                        float mdx, mdy;
+                        const float idx_ = source_index<PAD, false>(p.gx, W, mdx);
+                        const float idy_ = source_index<PAD, false>(p.gy, H, mdy);
+                        const Bilin bd = bilinear_setup(idx_, idy_, W, H);
+                        const Taps t = load_taps(dsb, W, bd);
+                        const float id = ((t.nw * bd.wnw + t.ne * bd.wne) + t.sw * bd.wsw) + t.se * bd.wse;
+                        const float r = fabsf(wd - id) / (wd + id);
+                        gsum[s] += (r != r) ? r : fminf(fmaxf(r, 0.f), 1.f);      // torch.clamp keeps a NaN
+                        gcnt[s] += 1;
+                    }
                 }
             }
 #pragma unroll
@@ -154,14 +230,46 @@ __global__ __launch_bounds__(NTHREADS) void k_warp_photo_window_fwd(
         if (pmap) pmap[b * N + pix] = val;
     }
     const int blk = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-    const float s0 = block_sum(val, red);
+    const int nblk = gridDim.x * gridDim.y * gridDim.z;
+    const float s0 = block_sum(val, red[0]);
     if (tid == 0) partials[blk] = s0;
+#pragma unroll
+    for (int s = 0; s < MAX_S; ++s) {
+        if (!GEO || s >= S) break;
+        const float gs = block_sum(gsum[s], red[1 + s]);
+        const int gn = block_sum_i(gcnt[s], redi[s]);
+        if (tid == 0) {
+            gpart[(int64_t)s * nblk + blk] = gs;
+            cpart[(int64_t)s * nblk + blk] = gn;
+        }
+    }
+}
+
+// one wave per source: lane l adds the workgroups' partials l, l + 64, ... in order, then a fixed shuffle tree; the count is an integer sum
+__global__ __launch_bounds__(64) void k_geo_final(const float* __restrict__ gpart, const int* __restrict__ cpart, int nblk, int geo_min_valid,
+                                                  int* __restrict__ geo_count, float* __restrict__ loss_out) {
+    const int s = blockIdx.x, lane = threadIdx.x;
+    double a = 0.0;
+    long long n = 0;
+    for (int i = lane; i < nblk; i += 64) {
+        a += (double)gpart[(int64_t)s * nblk + i];
+        n += cpart[(int64_t)s * nblk + i];
+    }
+    a = wave_sum_d(a);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) n += __shfl_down(n, o, 64);
+    if (lane == 0) {
+        geo_count[s] = (int)n;
+        loss_out[1 + s] = (n > (long long)geo_min_valid) ? (float)(a / (double)n) : 0.f;
+    }
 }
 
 // ---------------------------------------------------------------------------------------------
 // backward: per source the photometric adjoint (3x3 box + reflect pad fold-back) with the per-pixel weight of that source's reprojection map,
 // then the warp adjoint; g_depth_tgt accumulates in a register over the sources and is stored once.  POSE: per source the workgroup's 12
 // float64 sums of gc_r X_j | gc_r in partials[((s B + b) tiles + tile) * 12 + r * 4 + j]; every thread takes part, dead pixels add zeros.
+// GEO: the image index is align_corners=True, and per source the geometric adjoint of the own pixel is added.  Without GEO dsrc0 / dsrc1 /
+// geo_count / geo_min_valid / fx and g_loss[1..] are not read (the window passes NULL and 0).
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ float source_weight(int sel, int s, int nI, bool minrep, float gl, float gl_mean) {
     if (sel < nI) return 0.f;                            // an identity candidate won: constants only
@@ -169,13 +277,20 @@ __device__ __forceinline__ float source_weight(int sel, int s, int nI, bool minr
     return gl_mean;
 }
 
-template <int PAD, bool POSE>
+// one tap of the depth scatter: a 2^-48 fixed-point integer add, or the source's poison word (the range rule of e2e_grid_sample_bwd_exact)
+__device__ __forceinline__ void scatter_tap(unsigned long long* dst, unsigned long long* poison, float v) {
+    if (fabsf(v) < 4096.f) atomicAdd(dst, (unsigned long long)__double2ll_rn((double)v * FX_ONE));
+    else atomicOr(poison, 1ull);
+}
+
+template <int PAD, bool POSE, bool GEO>
 __global__ __launch_bounds__(NTHREADS) void k_warp_photo_window_bwd(
-    const float* __restrict__ depth, const float* __restrict__ src0, const float* __restrict__ src1, e2e_strides ss,
-    const float* __restrict__ tgt, e2e_strides ts, const float* __restrict__ K, const float* __restrict__ invK,
-    const float* __restrict__ T, const float* __restrict__ synth, const float* __restrict__ valid, const int* __restrict__ select,
-    int use_mask, int terms, const float* __restrict__ g_loss, float* __restrict__ g_dt, double* __restrict__ partials, int S, int B, int H,
-    int W) {
+    const float* __restrict__ depth, const float* __restrict__ dsrc0, const float* __restrict__ dsrc1, const float* __restrict__ src0,
+    const float* __restrict__ src1, e2e_strides ss, const float* __restrict__ tgt, e2e_strides ts, const float* __restrict__ K,
+    const float* __restrict__ invK, const float* __restrict__ T, const float* __restrict__ synth, const float* __restrict__ valid,
+    const int* __restrict__ select, const int* __restrict__ geo_count, int use_mask, int terms, int geo_min_valid,
+    const float* __restrict__ g_loss, float* __restrict__ g_dt, unsigned long long* __restrict__ fx, double* __restrict__ partials, int S,
+    int B, int H, int W) {
     __shared__ float lx[3][BP_N], ly[3][BP_N];
     __shared__ float lg[9][BG_N];
     __shared__ double sh[POSE ? WP_NSUM : 1][NTHREADS / 64];
@@ -210,6 +325,8 @@ __global__ __launch_bounds__(NTHREADS) void k_warp_photo_window_bwd(
         const int64_t sbi = (int64_t)s * B + b;
         const float* syn = synth + sbi * 3 * N;
         const float* val = valid + sbi * N;
+        const int ns = GEO ? geo_count[s] : 0;
+        const float e = (GEO && ns > geo_min_valid && ns > 0) ? g_loss[1 + s] / (float)ns : 0.f;      // 0: the gate is closed, the piece is skipped
         if (s) __syncthreads();                          // source s-1's planes (and its pose sums) have been read
         for (int i = tid; i < BP_N; i += NTHREADS) {
             const int l_y = i / BP_LD, l_x = i % BP_LD;
@@ -258,7 +375,8 @@ __global__ __launch_bounds__(NTHREADS) void k_warp_photo_window_bwd(
         if (live) {
             const float w_own = source_weight(sel_own, s, nI, minrep, gl, gl_mean);
             const int ctr = (threadIdx.y + 2) * BP_LD + threadIdx.x + 2;
-            const float m = use_mask ? val[pix] : 1.f;
+            const float vown = (GEO || use_mask) ? val[pix] : 1.f;
+            const float m = use_mask ? vown : 1.f;
             float G[3];
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
@@ -280,12 +398,12 @@ __global__ __launch_bounds__(NTHREADS) void k_warp_photo_window_bwd(
                 gx_ -= w_own * (0.15f / 3.f) * sg;
                 G[c] = gx_ * m;                          // d/d synth = d/dx * mask
             }
-            // warp adjoint: d synth / d grid (bilinear), grid -> (u,v) -> c -> depth
+            // warp adjoint: d synth / d grid (bilinear, align_corners = GEO), grid -> (u,v) -> c -> depth
             const Geom g = load_geom(K + b * 16, invK + b * 16, T + sbi * 16);
             const Proj p = project_pixel(g, (float)px, (float)py, d, W, H);
             float mx, my;
-            const float ix = source_index<PAD, false>(p.gx, W, mx);
-            const float iy = source_index<PAD, false>(p.gy, H, my);
+            const float ix = source_index<PAD, GEO>(p.gx, W, mx);
+            const float iy = source_index<PAD, GEO>(p.gy, H, my);
             const Bilin bl = bilinear_setup(ix, iy, W, H);
             const float* sp = (s ? src1 : src0) + b * ss.sb + bl.y0 * ss.sh + bl.x0 * ss.sw;
             float gix = 0.f, giy = 0.f;
@@ -299,9 +417,39 @@ __global__ __launch_bounds__(NTHREADS) void k_warp_photo_window_bwd(
                 gix += G[c] * ((ne - nw) * (1.f - bl.ty) + (se - sw) * bl.ty);
                 giy += G[c] * ((sw - nw) * (1.f - bl.tx) + (se - ne) * bl.tx);
             }
-            const float gu = (mx * gix) * 2.f / (float)(W - 1);
-            const float gv = (my * giy) * 2.f / (float)(H - 1);
-            const float gc0 = gu / p.z, gc1 = gv / p.z, gc2 = -(gu * p.u + gv * p.v) / p.z;
+            float gu = (mx * gix) * 2.f / (float)(W - 1);
+            float gv = (my * giy) * 2.f / (float)(H - 1);
+            float gwd = 0.f;                             // the geometric adjoint on c2 through wd
+            const bool geo = GEO && e != 0.f && vown != 0.f;
+            if (geo) {
+                const float c2 = fmaf(d, p.r[2], g.P[11]);
+                const float wd = fmaxf(c2, 1e-3f);
+                float mdx, mdy;
+                const float idx_ = source_index<PAD, false>(p.gx, W, mdx);
+                const float idy_ = source_index<PAD, false>(p.gy, H, mdy);
+                const Bilin bd = bilinear_setup(idx_, idy_, W, H);
+                const Taps t = load_taps((s ? dsrc1 : dsrc0) + b * N, W, bd);
+                const float id = ((t.nw * bd.wnw + t.ne * bd.wne) + t.sw * bd.wsw) + t.se * bd.wse;
+                const float df = wd - id, sum = wd + id;
+                const float r = fabsf(df) / sum;
+                const float sg = (df > 0.f) ? 1.f : ((df < 0.f) ? -1.f : 0.f);
+                const float k = (r >= 0.f && r <= 1.f) ? e * sg * 2.f / (sum * sum) : 0.f;     // the clamp passes on the closed interval
+                const float gid = -k * wd;
+                if (c2 >= 1e-3f) gwd = k * id;
+                unsigned long long* dst = fx + sbi * N + (int64_t)bd.y0 * W + bd.x0;
+                unsigned long long* poison = fx + (int64_t)S * B * N + s;
+                if (bd.in_y0 & bd.in_x0) scatter_tap(dst, poison, gid * bd.wnw);
+                if (bd.in_y0 & bd.in_x1) scatter_tap(dst + 1, poison, gid * bd.wne);
+                if (bd.in_y1 & bd.in_x0) scatter_tap(dst + W, poison, gid * bd.wsw);
+                if (bd.in_y1 & bd.in_x1) scatter_tap(dst + W + 1, poison, gid * bd.wse);
+                const float gdx = gid * ((t.ne - t.nw) * (1.f - bd.ty) + (t.se - t.sw) * bd.ty);
+                const float gdy = gid * ((t.sw - t.nw) * (1.f - bd.tx) + (t.se - t.ne) * bd.tx);
+                gu += (mdx * gdx) * 2.f / (float)(W - 1);
+                gv += (mdy * gdy) * 2.f / (float)(H - 1);
+            }
+            const float gc0 = gu / p.z, gc1 = gv / p.z;
+            float gc2 = -(gu * p.u + gv * p.v) / p.z;
+            if (geo) gc2 += gwd;
             gd += gc0 * p.r[0] + gc1 * p.r[1] + gc2 * p.r[2];
             if constexpr (POSE) {
                 const float gc[3] = {gc0, gc1, gc2};
@@ -331,16 +479,48 @@ __global__ __launch_bounds__(NTHREADS) void k_warp_photo_window_bwd(
     if (live) g_dt[b * N + pix] = gd;
 }
 
-// what both entry points refuse before they look at their own pointers
-int check_window(const char* name, int S, int B, int H, int W, int padding_mode, int terms) {
+// g_depth_src (S, B H W) from the fixed-point sums; a source whose poison word is set becomes NaN
+__global__ void k_geo_fixed48_to_float(const long long* __restrict__ fx, float* __restrict__ out, int64_t per_source, int S) {
+    const int64_t n = per_source * S;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const bool poisoned = fx[n + i / per_source] != 0;
+        out[i] = poisoned ? __uint_as_float(0x7FC00000u) : (float)((double)fx[i] * (1.0 / FX_ONE));
+    }
+}
+
+// what the four entry points refuse before they look at their own pointers (`name` = the entry point, geo = its geometric form; the
+// messages are part of the interface)
+int check_window(const char* name, bool geo, int S, int B, int H, int W, int padding_mode, int terms, int geo_min_valid) {
     E2E_REQUIRE(S >= 1 && S <= MAX_S, E2E_ERR_ARG, "%s: S=%d source frames (1 or 2)", name, S);
     E2E_REQUIRE(B > 0 && B <= 65535 && H > 1 && W > 1 && (int64_t)B * H * W < (1ll << 31), E2E_ERR_ARG, "%s: bad dims B=%d H=%d W=%d", name,
                 B, H, W);
     E2E_REQUIRE(padding_mode == E2E_PADDING_BORDER || padding_mode == E2E_PADDING_ZEROS, E2E_ERR_ARG,
                 "%s: padding_mode %d not supported (zeros|border)", name, padding_mode);
     E2E_REQUIRE((terms & ~(E2E_TERM_AUTO_MASKING | E2E_TERM_MIN_REPROJECTION)) == 0, E2E_ERR_ARG,
-                "%s: terms %d (E2E_TERM_AUTO_MASKING | E2E_TERM_MIN_REPROJECTION; the geometric term stays on the operators)", name, terms);
+                "%s: terms %d (E2E_TERM_AUTO_MASKING | E2E_TERM_MIN_REPROJECTION; the geometric term %s)", name, terms,
+                geo ? "is always on here" : "stays on the operators");
+    E2E_REQUIRE(!geo || geo_min_valid >= 0, E2E_ERR_ARG, "%s: geo_min_valid %d is negative", name, geo_min_valid);
     return E2E_OK;
+}
+
+int64_t fixed_words(int S, int B, int H, int W) { return (int64_t)S * B * H * W + S; }          // the sums and one poison word per source
+
+// the PAD and the PAD x POSE selection of the tile launches, once per direction; `a` is the kernel's argument list
+template <bool GEO, class... A>
+void launch_fwd(int padding_mode, dim3 g, hipStream_t st, A... a) {
+    if (padding_mode == E2E_PADDING_BORDER) hipLaunchKernelGGL((k_warp_photo_window_fwd<E2E_PAD_BORDER, GEO>), g, dim3(TW, TH), 0, st, a...);
+    else hipLaunchKernelGGL((k_warp_photo_window_fwd<E2E_PAD_ZEROS, GEO>), g, dim3(TW, TH), 0, st, a...);
+}
+
+template <bool GEO, class... A>
+void launch_bwd(int padding_mode, bool pose, dim3 g, hipStream_t st, A... a) {
+    if (padding_mode == E2E_PADDING_BORDER) {
+        if (pose) hipLaunchKernelGGL((k_warp_photo_window_bwd<E2E_PAD_BORDER, true, GEO>), g, dim3(TW, TH), 0, st, a...);
+        else hipLaunchKernelGGL((k_warp_photo_window_bwd<E2E_PAD_BORDER, false, GEO>), g, dim3(TW, TH), 0, st, a...);
+    } else {
+        if (pose) hipLaunchKernelGGL((k_warp_photo_window_bwd<E2E_PAD_ZEROS, true, GEO>), g, dim3(TW, TH), 0, st, a...);
+        else hipLaunchKernelGGL((k_warp_photo_window_bwd<E2E_PAD_ZEROS, false, GEO>), g, dim3(TW, TH), 0, st, a...);
+    }
 }
 
 }  // namespace
@@ -356,18 +536,14 @@ int e2e_warp_photo_window_fwd(const float* depth_tgt, const float* src0, const f
                               e2e_strides tgt_strides, const float* K, const float* inv_K, const float* T, const float* tie_noise, float* synth,
                               float* valid, int* select, float* pmap, int use_mask, int padding_mode, int terms, float* loss_out,
                               float* workspace, int S, int B, int H, int W, void* stream) {
-    const int rc = check_window("e2e_warp_photo_window_fwd", S, B, H, W, padding_mode, terms);
+    const int rc = check_window("e2e_warp_photo_window_fwd", false, S, B, H, W, padding_mode, terms, 0);
     if (rc != E2E_OK) return rc;
     E2E_REQUIRE(depth_tgt && src0 && (src1 || S == 1) && tgt && K && inv_K && T && synth && valid && select && loss_out && workspace, E2E_ERR_ARG,
                 "e2e_warp_photo_window_fwd: null pointer");
     hipStream_t st = (hipStream_t)stream;
     const dim3 g = tile_grid(B, H, W);
-    if (padding_mode == E2E_PADDING_BORDER)
-        hipLaunchKernelGGL(k_warp_photo_window_fwd<E2E_PAD_BORDER>, g, dim3(TW, TH), 0, st, depth_tgt, src0, src1, src_strides, tgt, tgt_strides,
-                           K, inv_K, T, tie_noise, synth, valid, select, pmap, use_mask, terms, workspace, S, B, H, W);
-    else
-        hipLaunchKernelGGL(k_warp_photo_window_fwd<E2E_PAD_ZEROS>, g, dim3(TW, TH), 0, st, depth_tgt, src0, src1, src_strides, tgt, tgt_strides,
-                           K, inv_K, T, tie_noise, synth, valid, select, pmap, use_mask, terms, workspace, S, B, H, W);
+    launch_fwd<false>(padding_mode, g, st, depth_tgt, (const float*)nullptr, (const float*)nullptr, src0, src1, src_strides, tgt, tgt_strides, K,
+                      inv_K, T, tie_noise, synth, valid, select, pmap, use_mask, terms, workspace, (float*)nullptr, (int*)nullptr, S, B, H, W);
     E2E_LAUNCH_CHECK("e2e_warp_photo_window_fwd");
     const float scale = (float)(1.0 / ((double)B * H * W));
     warp_photo_reduce_launch(workspace, (int)(g.x * g.y * g.z), 1, scale, loss_out, st);
@@ -384,28 +560,86 @@ int e2e_warp_photo_window_bwd(const float* depth_tgt, const float* src0, const f
                               e2e_strides tgt_strides, const float* K, const float* inv_K, const float* T, const float* synth,
                               const float* valid, const int* select, int use_mask, int padding_mode, int terms, const float* g_loss,
                               float* g_depth_tgt, float* g_T, void* workspace, int S, int B, int H, int W, void* stream) {
-    const int rc = check_window("e2e_warp_photo_window_bwd", S, B, H, W, padding_mode, terms);
+    const int rc = check_window("e2e_warp_photo_window_bwd", false, S, B, H, W, padding_mode, terms, 0);
     if (rc != E2E_OK) return rc;
     E2E_REQUIRE(depth_tgt && src0 && (src1 || S == 1) && tgt && K && inv_K && T && synth && valid && select && g_loss && g_depth_tgt, E2E_ERR_ARG,
                 "e2e_warp_photo_window_bwd: null pointer");
     E2E_REQUIRE(!g_T || workspace, E2E_ERR_ARG, "e2e_warp_photo_window_bwd: g_T without workspace");
     hipStream_t st = (hipStream_t)stream;
-    const dim3 g = tile_grid(B, H, W);
-#define WINDOW_BWD(PADV, POSEV)                                                                                                            \
-    hipLaunchKernelGGL((k_warp_photo_window_bwd<PADV, POSEV>), g, dim3(TW, TH), 0, st, depth_tgt, src0, src1, src_strides, tgt, tgt_strides, K, \
-                       inv_K, T, synth, valid, select, use_mask, terms, g_loss, g_depth_tgt, (double*)workspace, S, B, H, W)
-    if (padding_mode == E2E_PADDING_BORDER) {
-        if (g_T) WINDOW_BWD(E2E_PAD_BORDER, true);
-        else WINDOW_BWD(E2E_PAD_BORDER, false);
-    } else {
-        if (g_T) WINDOW_BWD(E2E_PAD_ZEROS, true);
-        else WINDOW_BWD(E2E_PAD_ZEROS, false);
-    }
-#undef WINDOW_BWD
+    launch_bwd<false>(padding_mode, g_T != nullptr, tile_grid(B, H, W), st, depth_tgt, (const float*)nullptr, (const float*)nullptr, src0, src1,
+                      src_strides, tgt, tgt_strides, K, inv_K, T, synth, valid, select, (const int*)nullptr, use_mask, terms, 0, g_loss,
+                      g_depth_tgt, (unsigned long long*)nullptr, (double*)workspace, S, B, H, W);
     E2E_LAUNCH_CHECK("e2e_warp_photo_window_bwd");
     if (g_T) {
         warp_photo_pose_final_launch((const double*)workspace, (int)tile_count(H, W), K, g_T, S, B, st);
         E2E_LAUNCH_CHECK("e2e_warp_photo_window_bwd(final)");
+    }
+    return E2E_OK;
+}
+
+int64_t e2e_warp_photo_geo_workspace_floats(int S, int B, int H, int W) {
+    if (S < 1 || S > MAX_S || B <= 0 || H <= 0 || W <= 0) return 0;
+    return (int64_t)B * tile_count(H, W) * (1 + 2 * S);
+}
+
+int e2e_warp_photo_geo_fwd(const float* depth_tgt, const float* depth_src0, const float* depth_src1, const float* src0, const float* src1,
+                           e2e_strides src_strides, const float* tgt, e2e_strides tgt_strides, const float* K, const float* inv_K, const float* T,
+                           const float* tie_noise, float* synth, float* valid, int* select, float* pmap, int* geo_count, int use_mask,
+                           int padding_mode, int terms, int geo_min_valid, float* loss_out, float* workspace, int S, int B, int H, int W,
+                           void* stream) {
+    const int rc = check_window("e2e_warp_photo_geo_fwd", true, S, B, H, W, padding_mode, terms, geo_min_valid);
+    if (rc != E2E_OK) return rc;
+    E2E_REQUIRE(depth_tgt && depth_src0 && (depth_src1 || S == 1) && src0 && (src1 || S == 1) && tgt && K && inv_K && T && synth && valid &&
+                    select && geo_count && loss_out && workspace,
+                E2E_ERR_ARG, "e2e_warp_photo_geo_fwd: null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 g = tile_grid(B, H, W);
+    const int nblk = (int)(g.x * g.y * g.z);
+    float* gpart = workspace + nblk;                     // [S][nblk] floats, then [S][nblk] ints
+    int* cpart = (int*)(workspace + (int64_t)nblk * (1 + S));
+    launch_fwd<true>(padding_mode, g, st, depth_tgt, depth_src0, depth_src1, src0, src1, src_strides, tgt, tgt_strides, K, inv_K, T, tie_noise,
+                     synth, valid, select, pmap, use_mask, terms, workspace, gpart, cpart, S, B, H, W);
+    E2E_LAUNCH_CHECK("e2e_warp_photo_geo_fwd");
+    const float scale = (float)(1.0 / ((double)B * H * W));
+    warp_photo_reduce_launch(workspace, nblk, 1, scale, loss_out, st);
+    E2E_LAUNCH_CHECK("e2e_warp_photo_geo_fwd(reduce)");
+    hipLaunchKernelGGL(k_geo_final, dim3(S), dim3(64), 0, st, gpart, cpart, nblk, geo_min_valid, geo_count, loss_out);
+    E2E_LAUNCH_CHECK("e2e_warp_photo_geo_fwd(geometric)");
+    return E2E_OK;
+}
+
+int64_t e2e_warp_photo_geo_bwd_workspace_bytes(int S, int B, int H, int W) {
+    if (S < 1 || S > MAX_S || B <= 0 || H <= 0 || W <= 0) return 0;
+    return (fixed_words(S, B, H, W) + (int64_t)S * B * tile_count(H, W) * WP_NSUM) * 8;
+}
+
+int e2e_warp_photo_geo_bwd(const float* depth_tgt, const float* depth_src0, const float* depth_src1, const float* src0, const float* src1,
+                           e2e_strides src_strides, const float* tgt, e2e_strides tgt_strides, const float* K, const float* inv_K, const float* T,
+                           const float* synth, const float* valid, const int* select, const int* geo_count, int use_mask, int padding_mode,
+                           int terms, int geo_min_valid, const float* g_loss, float* g_depth_tgt, float* g_depth_src, float* g_T,
+                           void* workspace, int S, int B, int H, int W, void* stream) {
+    const int rc = check_window("e2e_warp_photo_geo_bwd", true, S, B, H, W, padding_mode, terms, geo_min_valid);
+    if (rc != E2E_OK) return rc;
+    E2E_REQUIRE(depth_tgt && depth_src0 && (depth_src1 || S == 1) && src0 && (src1 || S == 1) && tgt && K && inv_K && T && synth && valid &&
+                    select && geo_count && g_loss && g_depth_tgt && g_depth_src && workspace,
+                E2E_ERR_ARG, "e2e_warp_photo_geo_bwd: null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t words = fixed_words(S, B, H, W);
+    unsigned long long* fx = (unsigned long long*)workspace;
+    double* partials = (double*)workspace + words;       // written only when g_T is asked for
+    E2E_REQUIRE(hipMemsetAsync(fx, 0, (size_t)words * 8, st) == hipSuccess, E2E_ERR_LAUNCH,
+                "e2e_warp_photo_geo_bwd: hipMemsetAsync of the fixed-point scratch failed");
+    launch_bwd<true>(padding_mode, g_T != nullptr, tile_grid(B, H, W), st, depth_tgt, depth_src0, depth_src1, src0, src1, src_strides, tgt,
+                     tgt_strides, K, inv_K, T, synth, valid, select, geo_count, use_mask, terms, geo_min_valid, g_loss, g_depth_tgt, fx, partials,
+                     S, B, H, W);
+    E2E_LAUNCH_CHECK("e2e_warp_photo_geo_bwd");
+    const int64_t per_source = (int64_t)B * H * W, n = per_source * S;
+    hipLaunchKernelGGL(k_geo_fixed48_to_float, dim3((unsigned)((n + 255) / 256 > 4096 ? 4096 : (n + 255) / 256)), dim3(256), 0, st,
+                       (const long long*)fx, g_depth_src, per_source, S);
+    E2E_LAUNCH_CHECK("e2e_warp_photo_geo_bwd(depth_src)");
+    if (g_T) {
+        warp_photo_pose_final_launch(partials, (int)tile_count(H, W), K, g_T, S, B, st);
+        E2E_LAUNCH_CHECK("e2e_warp_photo_geo_bwd(final)");
     }
     return E2E_OK;
 }

@@ -290,69 +290,18 @@ TERM_AUTO_MASKING, TERM_MIN_REPROJECTION = 2, 4                # E2E_TERM_* of i
 
 
 class _WarpPhotometricWindow(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, depth_tgt, src0, src1, tgt, K, inv_K, T0, T1, tie_noise, pad, use_mask, terms, want_pmap):
-        B, _, H, W = depth_tgt.shape
-        S = 1 if src1 is None else 2
-        dt = L.dev(depth_tgt, "depth_tgt").contiguous()
-        src0, tgt = L.dev(src0, "source_frame"), L.dev(tgt, "target_frame")
-        if S == 2:
-            src1 = L.dev(src1, "source_frame")
-            if src1.stride() != src0.stride():                 # one stride set serves both sources: a copy of the second in the first's layout
-                if 0 in src0.stride():
-                    src0 = src0.contiguous()
-                src1 = torch.empty_strided(src0.shape, src0.stride(), device=src0.device, dtype=torch.float32).copy_(src1)
-        K, inv_K = _mat(K, "K", B), _mat(inv_K, "inv_K", B)
-        T = torch.stack([_mat(t, "T", B) for t in ((T0, T1) if S == 2 else (T0,))])
-        noise = L.dev(tie_noise, "tie_noise").contiguous() if tie_noise is not None else None
-        dev = dt.device
-        synth = torch.empty(S, B, 3, H, W, device=dev, dtype=torch.float32)
-        valid = torch.empty(S, B, 1, H, W, device=dev, dtype=torch.float32)
-        select = torch.empty(B, 1, H, W, device=dev, dtype=torch.int32)
-        pmap = torch.empty(B, 1, H, W, device=dev, dtype=torch.float32) if want_pmap else None
-        loss = torch.zeros(1, device=dev, dtype=torch.float32)
-        ws = torch.empty(L.load().e2e_warp_photo_window_workspace_floats(S, B, H, W), device=dev, dtype=torch.float32)
-        L.call("e2e_warp_photo_window_fwd", depth_tgt=L.ptr(dt), src0=L.ptr(src0), src1=L.ptr(src1), src_strides=L.strides4(src0), tgt=L.ptr(tgt),
-               tgt_strides=L.strides4(tgt), K=L.ptr(K), inv_K=L.ptr(inv_K), T=L.ptr(T), tie_noise=L.ptr(noise), synth=L.ptr(synth), valid=L.ptr(valid),
-               select=L.ptr(select), pmap=L.ptr(pmap), use_mask=int(use_mask), padding_mode=pad, terms=terms, loss_out=L.ptr(loss),
-               workspace=L.ptr(ws), S=S, B=B, H=H, W=W, stream=L.stream())
-        ctx.save_for_backward(dt, src0, src1, tgt, K, inv_K, T, synth, valid, select)
-        ctx.cfg = (pad, int(use_mask), terms, S, B, H, W)
-        ctx.mark_non_differentiable(synth, valid, select)
-        if pmap is not None:
-            ctx.mark_non_differentiable(pmap)
-        return loss[0], synth, valid, select, pmap
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, g0, *_):
-        dt, src0, src1, tgt, K, inv_K, T, synth, valid, select = ctx.saved_tensors
-        pad, use_mask, terms, S, B, H, W = ctx.cfg
-        gl = g0.reshape(1).contiguous()
-        gdt = torch.empty(B, 1, H, W, device=dt.device, dtype=torch.float32)
-        gT = ws = None
-        if ctx.needs_input_grad[6] or (S == 2 and ctx.needs_input_grad[7]):      # a pose carries a graph: the same launch also sums d/dT
-            gT = torch.empty(S, B, 4, 4, device=dt.device, dtype=torch.float32)
-            ws = torch.empty(L.load().e2e_warp_photo_window_bwd_workspace_bytes(S, B, H, W), device=dt.device, dtype=torch.uint8)
-        L.call("e2e_warp_photo_window_bwd", depth_tgt=L.ptr(dt), src0=L.ptr(src0), src1=L.ptr(src1), src_strides=L.strides4(src0), tgt=L.ptr(tgt),
-               tgt_strides=L.strides4(tgt), K=L.ptr(K), inv_K=L.ptr(inv_K), T=L.ptr(T), synth=L.ptr(synth), valid=L.ptr(valid), select=L.ptr(select),
-               use_mask=use_mask, padding_mode=pad, terms=terms, g_loss=L.ptr(gl), g_depth_tgt=L.ptr(gdt), g_T=L.ptr(gT), workspace=L.ptr(ws),
-               S=S, B=B, H=H, W=W, stream=L.stream())
-        g_T0 = gT[0] if gT is not None and ctx.needs_input_grad[6] else None
-        g_T1 = gT[1] if gT is not None and S == 2 and ctx.needs_input_grad[7] else None
-        return (gdt,) + (None,) * 5 + (g_T0, g_T1) + (None,) * 5
-
-
-class _WarpPhotometricGeo(torch.autograd.Function):
-    """the window with the geometric-consistency term: e2e_warp_photo_geo_fwd / _bwd"""
+    """the window (e2e_warp_photo_window_fwd / _bwd), or -- with geo_min_valid and one depth per source -- the window with the
+    geometric-consistency term (e2e_warp_photo_geo_fwd / _bwd); geo_min_valid None: dsrc0 / dsrc1 are None, and so are the outputs geo and count"""
 
     @staticmethod
     def forward(ctx, depth_tgt, dsrc0, dsrc1, src0, src1, tgt, K, inv_K, T0, T1, tie_noise, pad, use_mask, terms, geo_min_valid, want_pmap):
         B, _, H, W = depth_tgt.shape
         S = 1 if src1 is None else 2
+        geo = geo_min_valid is not None
+        name = "e2e_warp_photo_geo" if geo else "e2e_warp_photo_window"
         dt = L.dev(depth_tgt, "depth_tgt").contiguous()
-        ds0 = L.dev(dsrc0, "depth_src").contiguous()
-        ds1 = L.dev(dsrc1, "depth_src").contiguous() if S == 2 else None
+        ds0 = L.dev(dsrc0, "depth_src").contiguous() if geo else None
+        ds1 = L.dev(dsrc1, "depth_src").contiguous() if geo and S == 2 else None
         src0, tgt = L.dev(src0, "source_frame"), L.dev(tgt, "target_frame")
         if S == 2:
             src1 = L.dev(src1, "source_frame")
@@ -368,43 +317,47 @@ class _WarpPhotometricGeo(torch.autograd.Function):
         valid = torch.empty(S, B, 1, H, W, device=dev, dtype=torch.float32)
         select = torch.empty(B, 1, H, W, device=dev, dtype=torch.int32)
         pmap = torch.empty(B, 1, H, W, device=dev, dtype=torch.float32) if want_pmap else None
-        count = torch.empty(S, device=dev, dtype=torch.int32)
-        loss = torch.zeros(1 + S, device=dev, dtype=torch.float32)
-        ws = torch.empty(L.load().e2e_warp_photo_geo_workspace_floats(S, B, H, W), device=dev, dtype=torch.float32)
-        L.call("e2e_warp_photo_geo_fwd", depth_tgt=L.ptr(dt), depth_src0=L.ptr(ds0), depth_src1=L.ptr(ds1), src0=L.ptr(src0), src1=L.ptr(src1),
-               src_strides=L.strides4(src0), tgt=L.ptr(tgt), tgt_strides=L.strides4(tgt), K=L.ptr(K), inv_K=L.ptr(inv_K), T=L.ptr(T),
-               tie_noise=L.ptr(noise), synth=L.ptr(synth), valid=L.ptr(valid), select=L.ptr(select), pmap=L.ptr(pmap), geo_count=L.ptr(count),
-               use_mask=int(use_mask), padding_mode=pad, terms=terms, geo_min_valid=geo_min_valid, loss_out=L.ptr(loss), workspace=L.ptr(ws),
-               S=S, B=B, H=H, W=W, stream=L.stream())
+        count = torch.empty(S, device=dev, dtype=torch.int32) if geo else None
+        loss = torch.zeros(1 + S if geo else 1, device=dev, dtype=torch.float32)
+        ws = torch.empty(L.query(name + "_workspace_floats", S, B, H, W), device=dev, dtype=torch.float32)
+        more = dict(depth_src0=L.ptr(ds0), depth_src1=L.ptr(ds1), geo_count=L.ptr(count), geo_min_valid=geo_min_valid) if geo else {}
+        L.call(name + "_fwd", depth_tgt=L.ptr(dt), src0=L.ptr(src0), src1=L.ptr(src1), src_strides=L.strides4(src0), tgt=L.ptr(tgt),
+               tgt_strides=L.strides4(tgt), K=L.ptr(K), inv_K=L.ptr(inv_K), T=L.ptr(T), tie_noise=L.ptr(noise), synth=L.ptr(synth), valid=L.ptr(valid),
+               select=L.ptr(select), pmap=L.ptr(pmap), use_mask=int(use_mask), padding_mode=pad, terms=terms, loss_out=L.ptr(loss),
+               workspace=L.ptr(ws), S=S, B=B, H=H, W=W, stream=L.stream(), **more)
         ctx.save_for_backward(dt, ds0, ds1, src0, src1, tgt, K, inv_K, T, synth, valid, select, count)
         ctx.cfg = (pad, int(use_mask), terms, geo_min_valid, S, B, H, W)
-        ctx.mark_non_differentiable(synth, valid, select, count)
-        if pmap is not None:
-            ctx.mark_non_differentiable(pmap)
-        return loss[0], loss[1:], synth, valid, select, count, pmap
+        ctx.mark_non_differentiable(*(t for t in (synth, valid, select, count, pmap) if t is not None))
+        return loss[0], (loss[1:] if geo else None), synth, valid, select, count, pmap
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g0, g1, *_):
         dt, ds0, ds1, src0, src1, tgt, K, inv_K, T, synth, valid, select, count = ctx.saved_tensors
         pad, use_mask, terms, geo_min_valid, S, B, H, W = ctx.cfg
+        geo = geo_min_valid is not None
+        name = "e2e_warp_photo_geo" if geo else "e2e_warp_photo_window"
         dev = dt.device
-        gl = torch.cat([(g0 if g0 is not None else torch.zeros((), device=dev)).reshape(1),
-                        g1 if g1 is not None else torch.zeros(S, device=dev)]).contiguous()
+        gl = (g0 if g0 is not None else torch.zeros((), device=dev)).reshape(1)
+        if geo:
+            gl = torch.cat([gl, g1 if g1 is not None else torch.zeros(S, device=dev)])
+        gl = gl.contiguous()
         gdt = torch.empty(B, 1, H, W, device=dev, dtype=torch.float32)
-        gds = torch.empty(S, B, 1, H, W, device=dev, dtype=torch.float32)
-        gT = None
+        gds = torch.empty(S, B, 1, H, W, device=dev, dtype=torch.float32) if geo else None
+        gT = ws = None
         if ctx.needs_input_grad[8] or (S == 2 and ctx.needs_input_grad[9]):      # a pose carries a graph: the same launch also sums d/dT
             gT = torch.empty(S, B, 4, 4, device=dev, dtype=torch.float32)
-        ws = torch.empty(L.load().e2e_warp_photo_geo_bwd_workspace_bytes(S, B, H, W), device=dev, dtype=torch.uint8)
-        L.call("e2e_warp_photo_geo_bwd", depth_tgt=L.ptr(dt), depth_src0=L.ptr(ds0), depth_src1=L.ptr(ds1), src0=L.ptr(src0), src1=L.ptr(src1),
-               src_strides=L.strides4(src0), tgt=L.ptr(tgt), tgt_strides=L.strides4(tgt), K=L.ptr(K), inv_K=L.ptr(inv_K), T=L.ptr(T),
-               synth=L.ptr(synth), valid=L.ptr(valid), select=L.ptr(select), geo_count=L.ptr(count), use_mask=use_mask, padding_mode=pad,
-               terms=terms, geo_min_valid=geo_min_valid, g_loss=L.ptr(gl), g_depth_tgt=L.ptr(gdt), g_depth_src=L.ptr(gds), g_T=L.ptr(gT),
-               workspace=L.ptr(ws), S=S, B=B, H=H, W=W, stream=L.stream())
+        if geo or gT is not None:                              # the pose sums; the geometric form's depth scatter always needs its scratch
+            ws = torch.empty(L.query(name + "_bwd_workspace_bytes", S, B, H, W), device=dev, dtype=torch.uint8)
+        more = dict(depth_src0=L.ptr(ds0), depth_src1=L.ptr(ds1), geo_count=L.ptr(count), geo_min_valid=geo_min_valid,
+                    g_depth_src=L.ptr(gds)) if geo else {}
+        L.call(name + "_bwd", depth_tgt=L.ptr(dt), src0=L.ptr(src0), src1=L.ptr(src1), src_strides=L.strides4(src0), tgt=L.ptr(tgt),
+               tgt_strides=L.strides4(tgt), K=L.ptr(K), inv_K=L.ptr(inv_K), T=L.ptr(T), synth=L.ptr(synth), valid=L.ptr(valid), select=L.ptr(select),
+               use_mask=use_mask, padding_mode=pad, terms=terms, g_loss=L.ptr(gl), g_depth_tgt=L.ptr(gdt), g_T=L.ptr(gT), workspace=L.ptr(ws),
+               S=S, B=B, H=H, W=W, stream=L.stream(), **more)
         g_T0 = gT[0] if gT is not None and ctx.needs_input_grad[8] else None
         g_T1 = gT[1] if gT is not None and S == 2 and ctx.needs_input_grad[9] else None
-        return (gdt, gds[0], gds[1] if S == 2 else None) + (None,) * 5 + (g_T0, g_T1) + (None,) * 6
+        return (gdt, gds[0] if geo else None, gds[1] if geo and S == 2 else None) + (None,) * 5 + (g_T0, g_T1) + (None,) * 6
 
 
 def warp_photometric_window(depth_tgt, srcs, tgt, K, inv_K, Ts, padding_mode="border", use_mask=True, min_reprojection=False,
@@ -437,14 +390,16 @@ def warp_photometric_window(depth_tgt, srcs, tgt, K, inv_K, Ts, padding_mode="bo
             raise ValueError(f"warp_photometric_window: geometric=True needs depth_srcs, one ({B},1,{H},{W}) depth per source")
         if int(geo_min_valid) < 0:
             raise ValueError(f"geo_min_valid: {geo_min_valid} is negative")
-        p, geo, synth, valid, select, count, pmap = _WarpPhotometricGeo.apply(
-            depth_tgt, depth_srcs[0], depth_srcs[1] if S == 2 else None, srcs[0], srcs[1] if S == 2 else None, tgt, K, inv_K, Ts[0],
-            Ts[1] if S == 2 else None, tie_noise, _padding(padding_mode), bool(use_mask), terms, int(geo_min_valid), bool(want_pmap))
-        return {"photometric": p, "synth": synth, "valid": valid, "select": select, "pmap": pmap, "geometric": geo, "geo_count": count}
-    p, synth, valid, select, pmap = _WarpPhotometricWindow.apply(depth_tgt, srcs[0], srcs[1] if S == 2 else None, tgt, K, inv_K, Ts[0],
-                                                                 Ts[1] if S == 2 else None, tie_noise, _padding(padding_mode), bool(use_mask),
-                                                                 terms, bool(want_pmap))
-    return {"photometric": p, "synth": synth, "valid": valid, "select": select, "pmap": pmap}
+        geo_min_valid = int(geo_min_valid)
+    else:
+        depth_srcs, geo_min_valid = [None, None], None
+    p, geo, synth, valid, select, count, pmap = _WarpPhotometricWindow.apply(
+        depth_tgt, depth_srcs[0], depth_srcs[1] if S == 2 else None, srcs[0], srcs[1] if S == 2 else None, tgt, K, inv_K, Ts[0],
+        Ts[1] if S == 2 else None, tie_noise, _padding(padding_mode), bool(use_mask), terms, geo_min_valid, bool(want_pmap))
+    out = {"photometric": p, "synth": synth, "valid": valid, "select": select, "pmap": pmap}
+    if geometric:
+        out.update(geometric=geo, geo_count=count)
+    return out
 
 
 # ---------------------------------------------------------------------------------------------

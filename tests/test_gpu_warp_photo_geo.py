@@ -1,4 +1,4 @@
-"""e2e_warp_photo_geo_fwd / _bwd (csrc/warp_photo_geo.hip) and what is built on them: the fused warp-photometric pair over a window of one or
+"""e2e_warp_photo_geo_fwd / _bwd (csrc/warp_photo_window.hip) and what is built on them: the fused warp-photometric pair over a window of one or
 two source frames WITH the geometric-consistency term of LOSS.geometric (train_depth.py:558-576, losses.py:84-95), against float64.
 
   1. the entry points at geo_min_valid = 0: loss, G_s, geo_count, pmap, select, synth / valid per source, g_depth_tgt, g_depth_src, and g_T on

@@ -132,16 +132,25 @@ def test_crafted_case_has_one_winner_everywhere():
 
 def test_shared_device_code_of_the_pair_family_is_defined_once():
     """across csrc/*.hip and csrc/*.h: one struct Stats, one definition each of window_stats, ssim_value, ssim_partials and sample3, one
-    __global__ whose name ends in reduce_partials and one whose name ends in bwd_pose_final (the window uses the pair's)"""
+    __global__ whose name ends in reduce_partials and one whose name ends in bwd_pose_final (the window uses the pair's); one struct FirstMin,
+    one definition each of photo_value and source_weight, and one tile kernel per direction for the window and its geometric form together:
+    one __global__ named k_warp_photo_window_fwd or k_warp_photo_geo*_fwd and one named ..._bwd (templates <PAD, GEO> and <PAD, POSE, GEO>
+    of warp_photo_window.hip), and no file warp_photo_geo.hip"""
     csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "end-to-end-self-supervised-slam_amd", "csrc")
     files = sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h")))
-    assert len(files) >= 20                                                            # 25 at the time of writing: the glob still finds them
+    assert len(files) >= 20                                                            # 22 at the time of writing: the glob still finds them
     text = {os.path.basename(f): open(f).read() for f in files}
     kernel = r"__global__\s+(?:__launch_bounds__\s*\([^)]*\)\s+)?void\s+\w*%s\s*\("
     patterns = {"struct Stats": r"\bstruct\s+Stats\b\s*\{", "reduce_partials": kernel % "reduce_partials", "bwd_pose_final": kernel % "bwd_pose_final"}
-    for fn in ("window_stats", "ssim_value", "ssim_partials", "sample3"):
+    patterns["struct FirstMin"] = r"\bstruct\s+FirstMin\b\s*\{"
+    for d in ("fwd", "bwd"):                                                           # the window's and the geometric form's tile kernel are ONE template
+        what = f"k_warp_photo_window_{d} (the one tile kernel of e2e_warp_photo_window_{d} and e2e_warp_photo_geo_{d})"
+        patterns[what] = kernel % (r"k_warp_photo_(?:window|geo)\w*_" + d)
+    for fn in ("window_stats", "ssim_value", "ssim_partials", "sample3", "photo_value", "source_weight"):
         patterns[fn + "("] = r"^__device__[^;{(\n]*\b" + fn + r"\s*\([^;{]*\{"          # a definition: a body follows the parameter list
     for what, pat in patterns.items():
         found = [name for name, src in text.items() for _ in re.finditer(pat, src, re.M)]
         assert len(found) == 1, f"{what}: defined {len(found)} times, in {found}"
     assert "k_warp_photo_bwd_pose_final" in text["warp_photo_pose.hip"] and "k_reduce_partials" in text["warp_photo.hip"]
+    assert "warp_photo_geo.hip" not in text, "warp_photo_geo.hip is back: the geometric form is the GEO = true instantiation of warp_photo_window.hip"
+    assert "k_warp_photo_window_fwd" in text["warp_photo_window.hip"] and "k_warp_photo_window_bwd" in text["warp_photo_window.hip"]
