@@ -16,11 +16,13 @@ import icp_grad_ref as I
 import pointfusion_grad_ref as P
 
 
-def ne_bwd_tgt_closed_form(src, tgt, tgt_n, idx, keep, adj):
+def ne_bwd_tgt_closed_form(src, tgt, tgt_n, idx, keep, adj, with_scale=False):
     """The target-side adjoint of one ICP reduction as include/e2eslam.h states it, float64: adj (28,) in out29's order
     -> g_tgt, g_tgt_normals (m,3).  With U the upper-triangular unpacking of adj[:21], M = U + U^T, A_i = [n, s x n], b_i = n.(t - s):
     Abar_i = M A_i + b_i gbar, bbar_i = gbar.A_i + 2 ebar b_i; row j: sum over kept i with idx[i] == j of bbar_i n_j, and of
-    bbar_i (t_j - s_i) + Abar_i[0:3] + Abar_i[3:6] x s_i."""
+    bbar_i (t_j - s_i) + Abar_i[0:3] + Abar_i[3:6] x s_i.
+    with_scale: also S_tgt, S_tgt_normals (m,3), per element the sum of the absolute values of the terms that were added (one term per
+    kept row), the scale a bound on the summation error is stated against."""
     src, tgt, tgt_n, adj = src.double(), tgt.double(), tgt_n.double(), adj.double()
     U = torch.zeros(6, 6, dtype=torch.float64)
     k = 0
@@ -35,8 +37,11 @@ def ne_bwd_tgt_closed_form(src, tgt, tgt_n, idx, keep, adj):
     b = (n * (t - s)).sum(-1)
     Abar = A @ M.T + b[:, None] * gbar
     bbar = A @ gbar + 2.0 * ebar * b
-    g_tgt = torch.zeros_like(tgt).index_add_(0, j, bbar[:, None] * n)
-    g_n = torch.zeros_like(tgt_n).index_add_(0, j, bbar[:, None] * (t - s) + Abar[:, :3] + torch.cross(Abar[:, 3:], s, dim=-1))
+    rows_t, rows_n = bbar[:, None] * n, bbar[:, None] * (t - s) + Abar[:, :3] + torch.cross(Abar[:, 3:], s, dim=-1)
+    g_tgt = torch.zeros_like(tgt).index_add_(0, j, rows_t)
+    g_n = torch.zeros_like(tgt_n).index_add_(0, j, rows_n)
+    if with_scale:
+        return g_tgt, g_n, torch.zeros_like(tgt).index_add_(0, j, rows_t.abs()), torch.zeros_like(tgt_n).index_add_(0, j, rows_n.abs())
     return g_tgt, g_n
 
 

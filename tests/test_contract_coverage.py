@@ -3,7 +3,9 @@ called by one of the two contract modules (tests/test_gpu_depth_aux_contracts.py
 csrc/icp.hip and tests/test_gpu_icp_contracts.py, for csrc/warp_photo.hip and tests/test_gpu_warp_photo_contracts.py, for
 csrc/warp_photo_fused.hip and tests/test_gpu_lossgrad_contracts.py, for the forward
 entry points of csrc/conv.hip and tests/test_gpu_conv_fwd_contracts.py, and for the map side -- csrc/pointfusion.hip (but
-e2e_pf_active_subsample_dev, which the ICP gate owns) and csrc/knn.hip -- and tests/test_gpu_map_contracts.py."""
+e2e_pf_active_subsample_dev, which the ICP gate owns) and csrc/knn.hip -- and tests/test_gpu_map_contracts.py.  The adjoint side of
+the SLAM chain has the same gates: csrc/pose_grad.hip and tests/test_gpu_pose_grad_contracts.py, csrc/pointfusion_grad.hip with
+csrc/normal_maps_grad.hip and tests/test_gpu_map_grad_contracts.py."""
 import os
 import re
 
@@ -112,3 +114,30 @@ def test_every_entry_point_of_the_knn_file_has_a_contract_case():
     assert implemented <= declared, sorted(implemented - declared)
     called = set(re.findall(r"[\"'.](e2e_\w+)[\"'(]", _read(ROOT, "tests", "test_gpu_map_contracts.py")))
     assert not names - called, f"no contract case calls {sorted(names - called)}"
+
+
+def test_every_entry_point_of_the_pose_grad_file_has_a_contract_case():
+    """csrc/pose_grad.hip's entry points (the adjoint of the ICP normal equations with respect to the sources and to the targets, the
+    pose gradients of transform_points and Project3D, the three workspace queries) are all called by
+    tests/test_gpu_pose_grad_contracts.py."""
+    declared = set(re.findall(r"^(?:int|int64_t|long long)\s+(e2e_\w+)\s*\(", _read(ROOT, "include", "e2eslam.h"), re.M))
+    implemented = set(re.findall(r"^(?:int|int64_t|long long)\s+(e2e_\w+)\s*\(", _read(CSRC, "pose_grad.hip"), re.M))
+    names = declared & implemented
+    assert len(names) >= 7, sorted(names)                                 # 7 at the time of writing: the greps still find them
+    assert implemented <= declared, sorted(implemented - declared)
+    called = set(re.findall(r"[\"'.](e2e_\w+)[\"'(]", _read(ROOT, "tests", "test_gpu_pose_grad_contracts.py")))
+    assert not names - called, f"no contract case calls {sorted(names - called)}"
+
+
+def test_every_entry_point_of_the_map_grad_files_has_a_contract_case():
+    """csrc/pointfusion_grad.hip's entry points (the step's tape and its size, the step's adjoint, the depth gradient of the fusion
+    confidence, the normals' tape, its size and the normals' adjoint) and csrc/normal_maps_grad.hip's one (the adjoint of the normal
+    map) are all called by tests/test_gpu_map_grad_contracts.py."""
+    declared = set(re.findall(r"^(?:int|int64_t|long long)\s+(e2e_\w+)\s*\(", _read(ROOT, "include", "e2eslam.h"), re.M))
+    called = set(re.findall(r"[\"'.](e2e_\w+)[\"'(]", _read(ROOT, "tests", "test_gpu_map_grad_contracts.py")))
+    for name, least in (("pointfusion_grad.hip", 7), ("normal_maps_grad.hip", 1)):
+        implemented = set(re.findall(r"^(?:int|int64_t|long long)\s+(e2e_\w+)\s*\(", _read(CSRC, name), re.M))
+        names = declared & implemented
+        assert len(names) >= least, (name, sorted(names))                 # 7 + 1 at the time of writing: the greps still find them
+        assert implemented <= declared, (name, sorted(implemented - declared))
+        assert not names - called, f"no contract case calls {sorted(names - called)} of {name}"
