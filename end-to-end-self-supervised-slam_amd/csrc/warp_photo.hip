@@ -411,22 +411,33 @@ __global__ void k_reduce_partials(const float* __restrict__ partials, int nblk, 
 // POSE: the same launch also leaves, per workgroup, the 12 float64 sums of gc_r X_j | gc_r over its pixels (Pbar of the tile, row-major
 // 3x4; X = d cam, the back-projected point) in pose.partials[workgroup][12]: the gradient wrt T is their sum over the tiles times K^T
 // (k_warp_photo_bwd_pose_final, warp_photo_pose.hip).  No thread leaves before that reduction; pixels outside the image add zeros.
+// SUMS = WP_SUMS_INTRINSICS: a pass of its own that leaves ONLY, in pose.q_partials[workgroup][9], the float64 sums Q[r][j] of gc_r d pix_j,
+// pix = (x, y, 1): the gradient wrt inv_K[:3,:3] is P[:, :3]^T Q, the one wrt K is Pbar T^T with the pose pass's Pbar
+// (k_warp_photo_bwd_intrinsics_final, warp_photo_intrinsics.hip).  It stores no depth gradient and no pose sums: with 21 sums in ONE
+// instantiation hipcc vectorised the fp32 chain differently and g_depth_tgt came out a few ulps off e2e_warp_photo_bwd's on a fifth of the
+// pixels (measured on the MI355X; the twelve pose sums kept their bits), so the depth gradients and Pbar stay with the pose instantiation,
+// which is untouched, and the entry points launch both (warp_photo_bwd_intrinsics_launch).
 // ---------------------------------------------------------------------------------------------
-template <bool POSE>
+template <int SUMS>
 struct PoseOut {};                       // the last kernel argument: empty without the pose gradient, so that launch is the one it was
 template <>
-struct PoseOut<true> {
+struct PoseOut<WP_SUMS_POSE> {
     double* partials;
 };
+template <>
+struct PoseOut<WP_SUMS_INTRINSICS> {
+    double* q_partials;
+};
 
-template <int PAD, bool POSE>
+template <int PAD, int SUMS>
 __global__ __launch_bounds__(NTHREADS) void k_warp_photo_bwd(
     const float* __restrict__ depth, const float* __restrict__ src, e2e_strides ss,
     const float* __restrict__ tgt, e2e_strides ts, const float* __restrict__ K,
     const float* __restrict__ invK, const float* __restrict__ T, const float* __restrict__ synth,
     const float* __restrict__ valid, int use_mask, int reg_kind, const float* __restrict__ ri_t,
     const float* __restrict__ ri_s, const float* __restrict__ d_s, const float* __restrict__ g_loss,
-    float* __restrict__ g_dt, float* __restrict__ g_ds, int B, int H, int W, PoseOut<POSE> pose) {
+    float* __restrict__ g_dt, float* __restrict__ g_ds, int B, int H, int W, PoseOut<SUMS> pose) {
+    constexpr bool POSE = SUMS != WP_SUMS_NONE, INTR = SUMS == WP_SUMS_INTRINSICS;
     __shared__ float lx[3][(TH + 4) * BP_LD], ly[3][(TH + 4) * BP_LD];
     __shared__ float lg[9][(TH + 2) * BG_LD];
     const int b = blockIdx.z, tx0 = blockIdx.x * TW, ty0 = blockIdx.y * TH;
@@ -546,13 +557,13 @@ __global__ __launch_bounds__(NTHREADS) void k_warp_photo_bwd(
             const float e0 = ri_t[o] - d, e1 = ri_s[o] - d_s[o];
             if (reg_kind == 2) {
                 gd += gl1 * (-2.f * e0);
-                g_ds[o] = gl1 * (-2.f * e1);
+                if constexpr (!INTR) g_ds[o] = gl1 * (-2.f * e1);
             } else {
                 gd += gl1 * ((e0 > 0.f) ? -1.f : ((e0 < 0.f) ? 1.f : 0.f));
-                g_ds[o] = gl1 * ((e1 > 0.f) ? -1.f : ((e1 < 0.f) ? 1.f : 0.f));
+                if constexpr (!INTR) g_ds[o] = gl1 * ((e1 > 0.f) ? -1.f : ((e1 < 0.f) ? 1.f : 0.f));
             }
         }
-        g_dt[o] = gd;
+        if constexpr (!INTR) g_dt[o] = gd;
         if constexpr (POSE) {
             const float gc[3] = {gc0, gc1, gc2};
 #pragma unroll
@@ -563,7 +574,7 @@ __global__ __launch_bounds__(NTHREADS) void k_warp_photo_bwd(
             }
         }
     }
-    if constexpr (POSE) {  // every thread of the workgroup is here: wave shuffle, then the four waves in order through LDS
+    if constexpr (POSE && !INTR) {  // every thread of the workgroup is here: wave shuffle, then the four waves in order through LDS
         __shared__ double sh[12][NTHREADS / 64];
 #pragma unroll
         for (int k = 0; k < 12; ++k) {
@@ -575,6 +586,23 @@ __global__ __launch_bounds__(NTHREADS) void k_warp_photo_bwd(
             double* out = pose.partials + (((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 12;
 #pragma unroll
             for (int k = 0; k < 12; ++k) out[k] = ((sh[k][0] + sh[k][1]) + sh[k][2]) + sh[k][3];
+        }
+    }
+    if constexpr (INTR) {  // the same reduction for Q[r][j] = sum gc_r d pix_j, element by element: three live doubles, not nine
+        __shared__ double shq[WP_NQ][NTHREADS / 64];
+        const double dd = live ? (double)depth[b * N + (int64_t)py * W + px] : 0.0;
+        const double gcd[3] = {acc[3] * dd, acc[7] * dd, acc[11] * dd};      // acc[r][3] = (double)gc_r; a pixel outside the image has 0
+        const double pix[3] = {(double)px, (double)py, 1.0};                // exact
+#pragma unroll
+        for (int k = 0; k < WP_NQ; ++k) {
+            const double v = wave_sum_d(gcd[k / 3] * pix[k % 3]);
+            if ((tid & 63) == 0) shq[k][tid >> 6] = v;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            double* q = pose.q_partials + (((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * WP_NQ;
+#pragma unroll
+            for (int k = 0; k < WP_NQ; ++k) q[k] = ((shq[k][0] + shq[k][1]) + shq[k][2]) + shq[k][3];
         }
     }
 }
@@ -591,20 +619,21 @@ static inline dim3 flat_grid(int B, int64_t N) {
     E2E_REQUIRE(B > 0 && H > 1 && W > 1 && (int64_t)B * H * W < (1ll << 31), E2E_ERR_ARG,     \
                 name ": bad dims B=%d H=%d W=%d", B, H, W)
 
-// the one launch of k_warp_photo_bwd: e2e_warp_photo_bwd (POSE = false) and warp_photo_bwd_pose_launch.  Arguments are not checked here.
-template <bool POSE>
+// the one launch of k_warp_photo_bwd: e2e_warp_photo_bwd (WP_SUMS_NONE), warp_photo_bwd_pose_launch and warp_photo_bwd_intrinsics_launch.
+// Arguments are not checked here.
+template <int SUMS>
 static void warp_photo_bwd_launch(const float* depth_tgt, const float* src, e2e_strides ss, const float* tgt, e2e_strides ts, const float* K,
                                   const float* inv_K, const float* T, const float* synth, const float* valid, int use_mask, int padding_mode,
                                   int reg_kind, const float* reg_init_tgt, const float* reg_init_src, const float* depth_src,
-                                  const float* g_loss, float* g_depth_tgt, float* g_depth_src, int B, int H, int W, PoseOut<POSE> pose,
+                                  const float* g_loss, float* g_depth_tgt, float* g_depth_src, int B, int H, int W, PoseOut<SUMS> pose,
                                   hipStream_t stream) {
     const dim3 g = tile_grid(B, H, W);
     if (padding_mode == E2E_PADDING_BORDER)
-        hipLaunchKernelGGL((k_warp_photo_bwd<E2E_PAD_BORDER, POSE>), g, dim3(TW, TH), 0, stream, depth_tgt, src, ss, tgt, ts, K, inv_K, T,
+        hipLaunchKernelGGL((k_warp_photo_bwd<E2E_PAD_BORDER, SUMS>), g, dim3(TW, TH), 0, stream, depth_tgt, src, ss, tgt, ts, K, inv_K, T,
                            synth, valid, use_mask, reg_kind, reg_init_tgt, reg_init_src, depth_src, g_loss, g_depth_tgt, g_depth_src, B, H,
                            W, pose);
     else
-        hipLaunchKernelGGL((k_warp_photo_bwd<E2E_PAD_ZEROS, POSE>), g, dim3(TW, TH), 0, stream, depth_tgt, src, ss, tgt, ts, K, inv_K, T,
+        hipLaunchKernelGGL((k_warp_photo_bwd<E2E_PAD_ZEROS, SUMS>), g, dim3(TW, TH), 0, stream, depth_tgt, src, ss, tgt, ts, K, inv_K, T,
                            synth, valid, use_mask, reg_kind, reg_init_tgt, reg_init_src, depth_src, g_loss, g_depth_tgt, g_depth_src, B, H,
                            W, pose);
 }
@@ -765,8 +794,8 @@ int e2e_warp_photo_bwd(const float* depth_tgt, const float* src, e2e_strides ss,
                                              depth_tgt && src && tgt && K && inv_K && T && synth && valid && g_loss && g_depth_tgt,
                                              padding_mode, reg_kind, reg_init_tgt && reg_init_src && depth_src && g_depth_src))
         return rc;
-    warp_photo_bwd_launch<false>(depth_tgt, src, ss, tgt, ts, K, inv_K, T, synth, valid, use_mask, padding_mode, reg_kind, reg_init_tgt,
-                                 reg_init_src, depth_src, g_loss, g_depth_tgt, g_depth_src, B, H, W, PoseOut<false>{}, (hipStream_t)stream);
+    warp_photo_bwd_launch<WP_SUMS_NONE>(depth_tgt, src, ss, tgt, ts, K, inv_K, T, synth, valid, use_mask, padding_mode, reg_kind, reg_init_tgt,
+                                 reg_init_src, depth_src, g_loss, g_depth_tgt, g_depth_src, B, H, W, PoseOut<WP_SUMS_NONE>{}, (hipStream_t)stream);
     E2E_LAUNCH_CHECK("e2e_warp_photo_bwd");
     return E2E_OK;
 }
@@ -785,6 +814,19 @@ void warp_photo_bwd_pose_launch(const float* depth_tgt, const float* src, e2e_st
                                 const float* inv_K, const float* T, const float* synth, const float* valid, int use_mask, int padding_mode,
                                 int reg_kind, const float* reg_init_tgt, const float* reg_init_src, const float* depth_src, const float* g_loss,
                                 float* g_depth_tgt, float* g_depth_src, double* partials, int B, int H, int W, hipStream_t stream) {
-    warp_photo_bwd_launch<true>(depth_tgt, src, ss, tgt, ts, K, inv_K, T, synth, valid, use_mask, padding_mode, reg_kind, reg_init_tgt,
-                                reg_init_src, depth_src, g_loss, g_depth_tgt, g_depth_src, B, H, W, PoseOut<true>{partials}, stream);
+    warp_photo_bwd_launch<WP_SUMS_POSE>(depth_tgt, src, ss, tgt, ts, K, inv_K, T, synth, valid, use_mask, padding_mode, reg_kind, reg_init_tgt,
+                                reg_init_src, depth_src, g_loss, g_depth_tgt, g_depth_src, B, H, W, PoseOut<WP_SUMS_POSE>{partials}, stream);
+}
+
+void warp_photo_bwd_intrinsics_launch(const float* depth_tgt, const float* src, e2e_strides ss, const float* tgt, e2e_strides ts, const float* K,
+                                      const float* inv_K, const float* T, const float* synth, const float* valid, int use_mask, int padding_mode,
+                                      int reg_kind, const float* reg_init_tgt, const float* reg_init_src, const float* depth_src,
+                                      const float* g_loss, float* g_depth_tgt, float* g_depth_src, double* partials, double* q_partials, int B,
+                                      int H, int W, hipStream_t stream) {
+    // the pose pass: the depth gradients and Pbar, bit for bit e2e_warp_photo_bwd_pose's; then the Q pass, which stores the 9 sums only
+    warp_photo_bwd_launch<WP_SUMS_POSE>(depth_tgt, src, ss, tgt, ts, K, inv_K, T, synth, valid, use_mask, padding_mode, reg_kind, reg_init_tgt,
+                                        reg_init_src, depth_src, g_loss, g_depth_tgt, g_depth_src, B, H, W, PoseOut<WP_SUMS_POSE>{partials}, stream);
+    warp_photo_bwd_launch<WP_SUMS_INTRINSICS>(depth_tgt, src, ss, tgt, ts, K, inv_K, T, synth, valid, use_mask, padding_mode, reg_kind,
+                                              reg_init_tgt, reg_init_src, depth_src, g_loss, g_depth_tgt, g_depth_src, B, H, W,
+                                              PoseOut<WP_SUMS_INTRINSICS>{q_partials}, stream);
 }

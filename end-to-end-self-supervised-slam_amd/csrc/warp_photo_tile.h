@@ -14,7 +14,11 @@ constexpr int FP_LD = TW + 2;                          // forward planes: tile +
 constexpr int BP_LD = TW + 4;                          // backward image planes: tile + 2-px halo
 constexpr int BG_LD = TW + 2;                          // backward statistics planes: tile + 1-px halo
 constexpr int WP_NSUM = 12;                            // a 3x4 block: sum gc X^T (3x3) | sum gc (3x1), row-major
+constexpr int WP_NQ = 9;                               // a 3x3 block: sum gc (d pix)^T, row-major (the intrinsics mode only)
 constexpr float SSIM_C1 = 1e-4f, SSIM_C2 = 9e-4f;      // 0.01**2, 0.03**2  losses.py:20-21
+
+// what a launch of the backward tile kernels leaves: the depth gradient, the depth gradient and the 12 pose sums, or ONLY the 9 sums Q for inv_K
+enum { WP_SUMS_NONE = 0, WP_SUMS_POSE = 1, WP_SUMS_INTRINSICS = 2 };
 
 // ---------------------------------------------------------------------------------------------
 // SSIM statistics on an LDS plane.  xs/ys point at the window's top-left element, `ld` = row pitch.
@@ -103,12 +107,26 @@ static int warp_photo_check_args(const char* name, int B, int H, int W, bool poi
 // k_reduce_partials (warp_photo.hip): out[s] = scale * the fixed-order float64 sum of partials[s * nblk .. (s + 1) * nblk), s < nsets
 void warp_photo_reduce_launch(const float* partials, int nblk, int nsets, float scale, float* out, hipStream_t stream);
 
-// k_warp_photo_bwd<pad, POSE = true> (warp_photo.hip): the launch of e2e_warp_photo_bwd plus 12 float64 sums per workgroup in
+// k_warp_photo_bwd<pad, WP_SUMS_POSE> (warp_photo.hip): the launch of e2e_warp_photo_bwd plus 12 float64 sums per workgroup in
 // partials[(b * tiles + tile) * 12 + r * 4 + j].  Arguments are not checked here.
 void warp_photo_bwd_pose_launch(const float* depth_tgt, const float* src, e2e_strides ss, const float* tgt, e2e_strides ts, const float* K,
                                 const float* inv_K, const float* T, const float* synth, const float* valid, int use_mask, int padding_mode,
                                 int reg_kind, const float* reg_init_tgt, const float* reg_init_src, const float* depth_src, const float* g_loss,
                                 float* g_depth_tgt, float* g_depth_src, double* partials, int B, int H, int W, hipStream_t stream);
+
+// warp_photo_bwd_pose_launch, then k_warp_photo_bwd<pad, WP_SUMS_INTRINSICS> (warp_photo.hip): a second pass over the tiles that stores
+// only 9 float64 sums per workgroup, q_partials[(b * tiles + tile) * 9 + r * 3 + j] = sum gc_r d pix_j.  Arguments are not checked here.
+void warp_photo_bwd_intrinsics_launch(const float* depth_tgt, const float* src, e2e_strides ss, const float* tgt, e2e_strides ts, const float* K,
+                                      const float* inv_K, const float* T, const float* synth, const float* valid, int use_mask, int padding_mode,
+                                      int reg_kind, const float* reg_init_tgt, const float* reg_init_src, const float* depth_src,
+                                      const float* g_loss, float* g_depth_tgt, float* g_depth_src, double* partials, double* q_partials, int B,
+                                      int H, int W, hipStream_t stream);
+
+// k_warp_photo_bwd_intrinsics_final (warp_photo_intrinsics.hip): g_K[b] and g_inv_K[b] from the fixed-order sums over the tiles of
+// partials[((s * B + b) * tiles + tile) * 12 ..] and q_partials[((s * B + b) * tiles + tile) * 9 ..], the sources added in the order 0, 1;
+// T is (S,B,4,4), K (B,4,4); S = 1 for the pair
+void warp_photo_intrinsics_final_launch(const double* partials, const double* q_partials, int tiles, const float* K, const float* T, float* g_K,
+                                        float* g_inv_K, int S, int B, hipStream_t stream);
 
 // k_warp_photo_bwd_pose_final (warp_photo_pose.hip): g_T[(s * B + b) * 16 ..] = K_b^T times the fixed-order sum over the tiles of
 // partials[((s * B + b) * tiles + tile) * 12 ..]; S = 1 for the pair

@@ -1,7 +1,7 @@
 // warp_photo_window.hip -- the fused warp-photometric pair over a window of S = 1 or 2 source frames (DATA.frames: [0,-1,1], [0,-1], [0,1]) with
 // the candidate / minimum logic of the reference's train_depth.py:621-662 (LOSS.auto_masking, LOSS.min_reprojection), and the same window WITH
 // the geometric-consistency term of the reference's LOSS.geometric branch (train_depth.py:558-576, view_synthesis.py:54-78, losses.py:84-95).
-// ONE forward template <PAD, GEO> and ONE backward template <PAD, POSE, GEO> serve e2e_warp_photo_window_* (GEO = false) and
+// ONE forward template <PAD, GEO> and ONE backward template <PAD, SUMS, GEO> (SUMS: no sums, the pose sums, those and the intrinsics') serve e2e_warp_photo_window_* (GEO = false) and
 // e2e_warp_photo_geo_* (GEO = true): the text is the geometric kernel's, and the compile-time constant GEO deletes the geometric pieces
 // from the window's instantiation (profiles/warp_window_geo_merge.txt).  One tile launch forward (+ the fixed-order reduction of the workgroups'
 // partial sums), one tile launch backward (+ a final kernel per source and batch element when the gradient with respect to the poses is
@@ -268,6 +268,8 @@ __global__ __launch_bounds__(64) void k_geo_final(const float* __restrict__ gpar
 // backward: per source the photometric adjoint (3x3 box + reflect pad fold-back) with the per-pixel weight of that source's reprojection map,
 // then the warp adjoint; g_depth_tgt accumulates in a register over the sources and is stored once.  POSE: per source the workgroup's 12
 // float64 sums of gc_r X_j | gc_r in partials[((s B + b) tiles + tile) * 12 + r * 4 + j]; every thread takes part, dead pixels add zeros.
+// SUMS = WP_SUMS_INTRINSICS: a pass of its own (see k_warp_photo_bwd, warp_photo.hip, for why) that stores ONLY the 9 sums of gc_r d pix_j,
+// in a second region behind the pose sums, [((s B + b) tiles + tile) * 9 + r * 3 + j]: no depth gradient, no depth scatter, no pose sums.
 // GEO: the image index is align_corners=True, and per source the geometric adjoint of the own pixel is added.  Without GEO dsrc0 / dsrc1 /
 // geo_count / geo_min_valid / fx and g_loss[1..] are not read (the window passes NULL and 0).
 // ---------------------------------------------------------------------------------------------
@@ -283,7 +285,7 @@ __device__ __forceinline__ void scatter_tap(unsigned long long* dst, unsigned lo
     else atomicOr(poison, 1ull);
 }
 
-template <int PAD, bool POSE, bool GEO>
+template <int PAD, int SUMS, bool GEO>
 __global__ __launch_bounds__(NTHREADS) void k_warp_photo_window_bwd(
     const float* __restrict__ depth, const float* __restrict__ dsrc0, const float* __restrict__ dsrc1, const float* __restrict__ src0,
     const float* __restrict__ src1, e2e_strides ss, const float* __restrict__ tgt, e2e_strides ts, const float* __restrict__ K,
@@ -291,9 +293,10 @@ __global__ __launch_bounds__(NTHREADS) void k_warp_photo_window_bwd(
     const int* __restrict__ select, const int* __restrict__ geo_count, int use_mask, int terms, int geo_min_valid,
     const float* __restrict__ g_loss, float* __restrict__ g_dt, unsigned long long* __restrict__ fx, double* __restrict__ partials, int S,
     int B, int H, int W) {
+    constexpr bool POSE = SUMS != WP_SUMS_NONE, INTR = SUMS == WP_SUMS_INTRINSICS;
     __shared__ float lx[3][BP_N], ly[3][BP_N];
     __shared__ float lg[9][BG_N];
-    __shared__ double sh[POSE ? WP_NSUM : 1][NTHREADS / 64];
+    __shared__ double sh[POSE ? (INTR ? WP_NQ : WP_NSUM) : 1][NTHREADS / 64];
     const int b = blockIdx.z, tx0 = blockIdx.x * TW, ty0 = blockIdx.y * TH;
     const int tid = threadIdx.y * TW + threadIdx.x;
     const int64_t N = (int64_t)H * W;
@@ -438,10 +441,12 @@ __global__ __launch_bounds__(NTHREADS) void k_warp_photo_window_bwd(
                 if (c2 >= 1e-3f) gwd = k * id;
                 unsigned long long* dst = fx + sbi * N + (int64_t)bd.y0 * W + bd.x0;
                 unsigned long long* poison = fx + (int64_t)S * B * N + s;
-                if (bd.in_y0 & bd.in_x0) scatter_tap(dst, poison, gid * bd.wnw);
-                if (bd.in_y0 & bd.in_x1) scatter_tap(dst + 1, poison, gid * bd.wne);
-                if (bd.in_y1 & bd.in_x0) scatter_tap(dst + W, poison, gid * bd.wsw);
-                if (bd.in_y1 & bd.in_x1) scatter_tap(dst + W + 1, poison, gid * bd.wse);
+                if constexpr (!INTR) {                  // the Q pass adds nothing to the depth scatter: the pose pass has done it
+                    if (bd.in_y0 & bd.in_x0) scatter_tap(dst, poison, gid * bd.wnw);
+                    if (bd.in_y0 & bd.in_x1) scatter_tap(dst + 1, poison, gid * bd.wne);
+                    if (bd.in_y1 & bd.in_x0) scatter_tap(dst + W, poison, gid * bd.wsw);
+                    if (bd.in_y1 & bd.in_x1) scatter_tap(dst + W + 1, poison, gid * bd.wse);
+                }
                 const float gdx = gid * ((t.ne - t.nw) * (1.f - bd.ty) + (t.se - t.sw) * bd.ty);
                 const float gdy = gid * ((t.sw - t.nw) * (1.f - bd.tx) + (t.se - t.ne) * bd.tx);
                 gu += (mdx * gdx) * 2.f / (float)(W - 1);
@@ -461,7 +466,7 @@ __global__ __launch_bounds__(NTHREADS) void k_warp_photo_window_bwd(
                 }
             }
         }
-        if constexpr (POSE) {  // every thread of the workgroup is here: wave shuffle, then the four waves in order through LDS
+        if constexpr (POSE && !INTR) {  // every thread of the workgroup is here: wave shuffle, then the four waves in order through LDS
 #pragma unroll
             for (int k = 0; k < WP_NSUM; ++k) {
                 const double v = wave_sum_d(acc[k]);
@@ -475,7 +480,25 @@ __global__ __launch_bounds__(NTHREADS) void k_warp_photo_window_bwd(
                 for (int k = 0; k < WP_NSUM; ++k) out[k] = ((sh[k][0] + sh[k][1]) + sh[k][2]) + sh[k][3];
             }
         }
+        if constexpr (INTR) {  // the Q pass: the same reduction for Q[r][j] = sum gc_r d pix_j, element by element (three live doubles)
+            const double dd = (double)d;
+            const double gcd[3] = {acc[3] * dd, acc[7] * dd, acc[11] * dd};     // acc[r][3] = (double)gc_r; a pixel outside the image has 0
+            const double pixd[3] = {(double)px, (double)py, 1.0};               // exact
+#pragma unroll
+            for (int k = 0; k < WP_NQ; ++k) {
+                const double v = wave_sum_d(gcd[k / 3] * pixd[k % 3]);
+                if ((tid & 63) == 0) sh[k][tid >> 6] = v;
+            }
+            __syncthreads();
+            if (tid == 0) {  // the second region, [S][B][tiles][9], behind the pose sums
+                const int64_t tiles = (int64_t)gridDim.x * gridDim.y;
+                double* q = partials + (int64_t)S * B * tiles * WP_NSUM + (sbi * tiles + (int64_t)blockIdx.y * gridDim.x + blockIdx.x) * WP_NQ;
+#pragma unroll
+                for (int k = 0; k < WP_NQ; ++k) q[k] = ((sh[k][0] + sh[k][1]) + sh[k][2]) + sh[k][3];
+            }
+        }
     }
+    if constexpr (INTR) return;                          // the Q pass stores no depth gradient: the pose pass has written it
     if (live) g_dt[b * N + pix] = gd;
 }
 
@@ -513,13 +536,15 @@ void launch_fwd(int padding_mode, dim3 g, hipStream_t st, A... a) {
 }
 
 template <bool GEO, class... A>
-void launch_bwd(int padding_mode, bool pose, dim3 g, hipStream_t st, A... a) {
+void launch_bwd(int padding_mode, int sums, dim3 g, hipStream_t st, A... a) {
     if (padding_mode == E2E_PADDING_BORDER) {
-        if (pose) hipLaunchKernelGGL((k_warp_photo_window_bwd<E2E_PAD_BORDER, true, GEO>), g, dim3(TW, TH), 0, st, a...);
-        else hipLaunchKernelGGL((k_warp_photo_window_bwd<E2E_PAD_BORDER, false, GEO>), g, dim3(TW, TH), 0, st, a...);
+        if (sums == WP_SUMS_INTRINSICS) hipLaunchKernelGGL((k_warp_photo_window_bwd<E2E_PAD_BORDER, WP_SUMS_INTRINSICS, GEO>), g, dim3(TW, TH), 0, st, a...);
+        else if (sums == WP_SUMS_POSE) hipLaunchKernelGGL((k_warp_photo_window_bwd<E2E_PAD_BORDER, WP_SUMS_POSE, GEO>), g, dim3(TW, TH), 0, st, a...);
+        else hipLaunchKernelGGL((k_warp_photo_window_bwd<E2E_PAD_BORDER, WP_SUMS_NONE, GEO>), g, dim3(TW, TH), 0, st, a...);
     } else {
-        if (pose) hipLaunchKernelGGL((k_warp_photo_window_bwd<E2E_PAD_ZEROS, true, GEO>), g, dim3(TW, TH), 0, st, a...);
-        else hipLaunchKernelGGL((k_warp_photo_window_bwd<E2E_PAD_ZEROS, false, GEO>), g, dim3(TW, TH), 0, st, a...);
+        if (sums == WP_SUMS_INTRINSICS) hipLaunchKernelGGL((k_warp_photo_window_bwd<E2E_PAD_ZEROS, WP_SUMS_INTRINSICS, GEO>), g, dim3(TW, TH), 0, st, a...);
+        else if (sums == WP_SUMS_POSE) hipLaunchKernelGGL((k_warp_photo_window_bwd<E2E_PAD_ZEROS, WP_SUMS_POSE, GEO>), g, dim3(TW, TH), 0, st, a...);
+        else hipLaunchKernelGGL((k_warp_photo_window_bwd<E2E_PAD_ZEROS, WP_SUMS_NONE, GEO>), g, dim3(TW, TH), 0, st, a...);
     }
 }
 
@@ -566,7 +591,7 @@ int e2e_warp_photo_window_bwd(const float* depth_tgt, const float* src0, const f
                 "e2e_warp_photo_window_bwd: null pointer");
     E2E_REQUIRE(!g_T || workspace, E2E_ERR_ARG, "e2e_warp_photo_window_bwd: g_T without workspace");
     hipStream_t st = (hipStream_t)stream;
-    launch_bwd<false>(padding_mode, g_T != nullptr, tile_grid(B, H, W), st, depth_tgt, (const float*)nullptr, (const float*)nullptr, src0, src1,
+    launch_bwd<false>(padding_mode, g_T ? WP_SUMS_POSE : WP_SUMS_NONE, tile_grid(B, H, W), st, depth_tgt, (const float*)nullptr, (const float*)nullptr, src0, src1,
                       src_strides, tgt, tgt_strides, K, inv_K, T, synth, valid, select, (const int*)nullptr, use_mask, terms, 0, g_loss,
                       g_depth_tgt, (unsigned long long*)nullptr, (double*)workspace, S, B, H, W);
     E2E_LAUNCH_CHECK("e2e_warp_photo_window_bwd");
@@ -629,7 +654,7 @@ int e2e_warp_photo_geo_bwd(const float* depth_tgt, const float* depth_src0, cons
     double* partials = (double*)workspace + words;       // written only when g_T is asked for
     E2E_REQUIRE(hipMemsetAsync(fx, 0, (size_t)words * 8, st) == hipSuccess, E2E_ERR_LAUNCH,
                 "e2e_warp_photo_geo_bwd: hipMemsetAsync of the fixed-point scratch failed");
-    launch_bwd<true>(padding_mode, g_T != nullptr, tile_grid(B, H, W), st, depth_tgt, depth_src0, depth_src1, src0, src1, src_strides, tgt,
+    launch_bwd<true>(padding_mode, g_T ? WP_SUMS_POSE : WP_SUMS_NONE, tile_grid(B, H, W), st, depth_tgt, depth_src0, depth_src1, src0, src1, src_strides, tgt,
                      tgt_strides, K, inv_K, T, synth, valid, select, geo_count, use_mask, terms, geo_min_valid, g_loss, g_depth_tgt, fx, partials,
                      S, B, H, W);
     E2E_LAUNCH_CHECK("e2e_warp_photo_geo_bwd");
@@ -641,6 +666,81 @@ int e2e_warp_photo_geo_bwd(const float* depth_tgt, const float* depth_src0, cons
         warp_photo_pose_final_launch(partials, (int)tile_count(H, W), K, g_T, S, B, st);
         E2E_LAUNCH_CHECK("e2e_warp_photo_geo_bwd(final)");
     }
+    return E2E_OK;
+}
+
+// ---- the same two backwards with the gradient with respect to the intrinsics: the tile launch with the pose sums (the existing instantiation:
+// the depth gradients and Pbar keep their bits), the tile launch in its third mode (the Q pass: 9 sums per workgroup and source into the second
+// region), then k_warp_photo_bwd_intrinsics_final; k_warp_photo_bwd_pose_final runs unchanged on the first region when g_T is asked for.
+int64_t e2e_warp_photo_window_bwd_intrinsics_workspace_bytes(int S, int B, int H, int W) {
+    if (S < 1 || S > MAX_S || B <= 0 || H <= 0 || W <= 0) return 0;
+    return (int64_t)S * B * tile_count(H, W) * (WP_NSUM + WP_NQ) * 8;
+}
+
+int e2e_warp_photo_window_bwd_intrinsics(const float* depth_tgt, const float* src0, const float* src1, e2e_strides src_strides, const float* tgt,
+                                         e2e_strides tgt_strides, const float* K, const float* inv_K, const float* T, const float* synth,
+                                         const float* valid, const int* select, int use_mask, int padding_mode, int terms, const float* g_loss,
+                                         float* g_depth_tgt, float* g_T, float* g_K, float* g_inv_K, void* workspace, int S, int B, int H, int W,
+                                         void* stream) {
+    const int rc = check_window("e2e_warp_photo_window_bwd_intrinsics", false, S, B, H, W, padding_mode, terms, 0);
+    if (rc != E2E_OK) return rc;
+    E2E_REQUIRE(depth_tgt && src0 && (src1 || S == 1) && tgt && K && inv_K && T && synth && valid && select && g_loss && g_depth_tgt && g_K &&
+                    g_inv_K && workspace,
+                E2E_ERR_ARG, "e2e_warp_photo_window_bwd_intrinsics: null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    const int tiles = (int)tile_count(H, W);
+    double* partials = (double*)workspace;
+    for (const int sums : {WP_SUMS_POSE, WP_SUMS_INTRINSICS})      // the pose pass (g_depth_tgt, Pbar: e2e_warp_photo_window_bwd's bits), then the Q pass
+        launch_bwd<false>(padding_mode, sums, tile_grid(B, H, W), st, depth_tgt, (const float*)nullptr, (const float*)nullptr, src0, src1,
+                          src_strides, tgt, tgt_strides, K, inv_K, T, synth, valid, select, (const int*)nullptr, use_mask, terms, 0, g_loss,
+                          g_depth_tgt, (unsigned long long*)nullptr, partials, S, B, H, W);
+    E2E_LAUNCH_CHECK("e2e_warp_photo_window_bwd_intrinsics");
+    if (g_T) {
+        warp_photo_pose_final_launch(partials, tiles, K, g_T, S, B, st);
+        E2E_LAUNCH_CHECK("e2e_warp_photo_window_bwd_intrinsics(pose)");
+    }
+    warp_photo_intrinsics_final_launch(partials, partials + (int64_t)S * B * tiles * WP_NSUM, tiles, K, T, g_K, g_inv_K, S, B, st);
+    E2E_LAUNCH_CHECK("e2e_warp_photo_window_bwd_intrinsics(final)");
+    return E2E_OK;
+}
+
+int64_t e2e_warp_photo_geo_bwd_intrinsics_workspace_bytes(int S, int B, int H, int W) {
+    if (S < 1 || S > MAX_S || B <= 0 || H <= 0 || W <= 0) return 0;
+    return (fixed_words(S, B, H, W) + (int64_t)S * B * tile_count(H, W) * (WP_NSUM + WP_NQ)) * 8;
+}
+
+int e2e_warp_photo_geo_bwd_intrinsics(const float* depth_tgt, const float* depth_src0, const float* depth_src1, const float* src0,
+                                      const float* src1, e2e_strides src_strides, const float* tgt, e2e_strides tgt_strides, const float* K,
+                                      const float* inv_K, const float* T, const float* synth, const float* valid, const int* select,
+                                      const int* geo_count, int use_mask, int padding_mode, int terms, int geo_min_valid, const float* g_loss,
+                                      float* g_depth_tgt, float* g_depth_src, float* g_T, float* g_K, float* g_inv_K, void* workspace, int S,
+                                      int B, int H, int W, void* stream) {
+    const int rc = check_window("e2e_warp_photo_geo_bwd_intrinsics", true, S, B, H, W, padding_mode, terms, geo_min_valid);
+    if (rc != E2E_OK) return rc;
+    E2E_REQUIRE(depth_tgt && depth_src0 && (depth_src1 || S == 1) && src0 && (src1 || S == 1) && tgt && K && inv_K && T && synth && valid &&
+                    select && geo_count && g_loss && g_depth_tgt && g_depth_src && g_K && g_inv_K && workspace,
+                E2E_ERR_ARG, "e2e_warp_photo_geo_bwd_intrinsics: null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t words = fixed_words(S, B, H, W);
+    const int tiles = (int)tile_count(H, W);
+    unsigned long long* fx = (unsigned long long*)workspace;
+    double* partials = (double*)workspace + words;
+    E2E_REQUIRE(hipMemsetAsync(fx, 0, (size_t)words * 8, st) == hipSuccess, E2E_ERR_LAUNCH,
+                "e2e_warp_photo_geo_bwd_intrinsics: hipMemsetAsync of the fixed-point scratch failed");
+    for (const int sums : {WP_SUMS_POSE, WP_SUMS_INTRINSICS})      // the pose pass (both depth gradients, Pbar: e2e_warp_photo_geo_bwd's bits), then the Q pass
+        launch_bwd<true>(padding_mode, sums, tile_grid(B, H, W), st, depth_tgt, depth_src0, depth_src1, src0, src1, src_strides, tgt, tgt_strides, K,
+                         inv_K, T, synth, valid, select, geo_count, use_mask, terms, geo_min_valid, g_loss, g_depth_tgt, fx, partials, S, B, H, W);
+    E2E_LAUNCH_CHECK("e2e_warp_photo_geo_bwd_intrinsics");
+    const int64_t per_source = (int64_t)B * H * W, n = per_source * S;
+    hipLaunchKernelGGL(k_geo_fixed48_to_float, dim3((unsigned)((n + 255) / 256 > 4096 ? 4096 : (n + 255) / 256)), dim3(256), 0, st,
+                       (const long long*)fx, g_depth_src, per_source, S);
+    E2E_LAUNCH_CHECK("e2e_warp_photo_geo_bwd_intrinsics(depth_src)");
+    if (g_T) {
+        warp_photo_pose_final_launch(partials, tiles, K, g_T, S, B, st);
+        E2E_LAUNCH_CHECK("e2e_warp_photo_geo_bwd_intrinsics(pose)");
+    }
+    warp_photo_intrinsics_final_launch(partials, partials + (int64_t)S * B * tiles * WP_NSUM, tiles, K, T, g_K, g_inv_K, S, B, st);
+    E2E_LAUNCH_CHECK("e2e_warp_photo_geo_bwd_intrinsics(final)");
     return E2E_OK;
 }
 

@@ -2,7 +2,8 @@
 
 `WarpPhotoPlan` owns every intermediate buffer of the image-space part of one refinement step, so a
 step is exactly: e2e_warp_photo_fwd (+ its 1-block reduction) and e2e_warp_photo_bwd (or
-e2e_warp_photo_bwd_pose, which also returns the gradient with respect to T) -- no
+e2e_warp_photo_bwd_pose, which also returns the gradient with respect to T, or e2e_warp_photo_bwd_intrinsics,
+which returns the gradients with respect to K and inv_K as well) -- no
 allocator traffic, no host synchronisation.  The build's driver and bench.py use it; the autograd
 form for ad-hoc use is ops.warp_photometric."""
 import ctypes
@@ -28,6 +29,7 @@ class WarpPhotoPlan:
         self.g_depth_src = torch.empty(B, 1, H, W, **f)
         self.ws = torch.empty(L.load().e2e_warp_photo_workspace_floats(B, H, W), **f)
         self.g_T = self.ws_pose = None             # backward(pose=True): the gradient wrt T and its float64 partial sums
+        self.g_K = self.g_inv_K = self.ws_intrinsics = None        # backward(intrinsics=True): the gradients wrt K, inv_K and their sums
 
     def bind(self, depth_tgt, depth_src, init_tgt, init_src, src, tgt, K, inv_K, T):
         """Fix the input tensors (they may be rewritten in place between steps)."""
@@ -67,12 +69,27 @@ class WarpPhotoPlan:
             self.g_T = torch.empty(self.B, 4, 4, device=dev, dtype=torch.float32)
             self.ws_pose = torch.empty(L.load().e2e_warp_photo_bwd_pose_workspace_bytes(self.B, self.H, self.W), device=dev, dtype=torch.uint8)
 
-    def backward(self, pose=False):
+    def _intrinsics_buffers(self):
+        if self.g_K is None:
+            dev = self.synth.device
+            self.g_K, self.g_inv_K = (torch.empty(self.B, 4, 4, device=dev, dtype=torch.float32) for _ in range(2))
+            self.ws_intrinsics = torch.empty(L.query("e2e_warp_photo_bwd_intrinsics_workspace_bytes", self.B, self.H, self.W), device=dev, dtype=torch.uint8)
+
+    def backward(self, pose=False, intrinsics=False):
         """-> (g_depth_tgt, g_depth_src); with pose=True (e2e_warp_photo_bwd_pose) -> (g_depth_tgt, g_depth_src, g_T), g_T (B,4,4) the
-        gradient of g_loss[0] * photometric with respect to the bound T.  g_T and its workspace are allocated once, by the first such
-        call -- make that call before capturing a graph."""
+        gradient of g_loss[0] * photometric with respect to the bound T.  With intrinsics=True (e2e_warp_photo_bwd_intrinsics) the tuple
+        ends with g_K, g_inv_K (B,4,4), the gradients with respect to the bound K and inv_K: (g_depth_tgt, g_depth_src[, g_T], g_K,
+        g_inv_K).  Each output and its workspace are allocated once, by the first call that asks for it -- make that call before
+        capturing a graph."""
         outputs = dict(synth=L.ptr(self.synth), valid=L.ptr(self.valid), g_loss=L.ptr(self.g_loss), g_depth_tgt=L.ptr(self.g_depth_tgt),
                        g_depth_src=L.ptr(self.g_depth_src) if self.reg else None)
+        if intrinsics:
+            self._intrinsics_buffers()
+            if pose:
+                self._pose_buffers()
+            L.call("e2e_warp_photo_bwd_intrinsics", geom=self._operands(), g_T=L.ptr(self.g_T) if pose else None, g_K=L.ptr(self.g_K),
+                   g_inv_K=L.ptr(self.g_inv_K), workspace=L.ptr(self.ws_intrinsics), **outputs)
+            return (self.g_depth_tgt, self.g_depth_src) + ((self.g_T,) if pose else ()) + (self.g_K, self.g_inv_K)
         if not pose:
             L.call("e2e_warp_photo_bwd", geom=self._operands(), **outputs)
             return self.g_depth_tgt, self.g_depth_src

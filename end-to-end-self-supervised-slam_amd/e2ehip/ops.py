@@ -30,19 +30,25 @@ class _Backproject(torch.autograd.Function):
         ik = _mat(inv_K, "inv_K", B)
         out = torch.empty(B, 4, H * W, device=d.device, dtype=torch.float32)
         L.call("e2e_backproject_fwd", L.ptr(d), L.ptr(ik), L.ptr(out), B, H, W, L.stream())
-        ctx.save_for_backward(ik)
+        ctx.save_for_backward(ik, d if ctx.needs_input_grad[1] else None)       # the depth only for the gradient wrt inv_K
         ctx.dims = (B, H, W)
         return out
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g):
-        ik, = ctx.saved_tensors
+        ik, d = ctx.saved_tensors
         B, H, W = ctx.dims
         g = g.contiguous()
-        gd = torch.empty(B, 1, H, W, device=g.device, dtype=torch.float32)
-        L.call("e2e_backproject_bwd", L.ptr(g), L.ptr(ik), L.ptr(gd), B, H, W, L.stream())
-        return gd, None
+        gd = gik = None
+        if ctx.needs_input_grad[0]:
+            gd = torch.empty(B, 1, H, W, device=g.device, dtype=torch.float32)
+            L.call("e2e_backproject_bwd", L.ptr(g), L.ptr(ik), L.ptr(gd), B, H, W, L.stream())
+        if ctx.needs_input_grad[1]:          # inv_K is a parameter (self-calibration): sum g_cam[r] depth pix_j
+            gik = torch.empty(B, 4, 4, device=g.device, dtype=torch.float32)
+            ws = torch.empty(L.query("e2e_backproject_bwd_invk_workspace_bytes", B), device=g.device, dtype=torch.uint8)
+            L.call("e2e_backproject_bwd_invk", g_cam=L.ptr(g), depth=L.ptr(d), g_inv_K=L.ptr(gik), workspace=L.ptr(ws), B=B, H=H, W=W, stream=L.stream())
+        return gd, gik
 
 
 def backproject(depth, inv_K):
@@ -77,7 +83,7 @@ class _Project3D(torch.autograd.Function):
         g_z = rest[0] if len(rest) == 2 else None
         g_grid = (g_grid if g_grid is not None else torch.zeros(B, H, W, 2, device=p.device)).contiguous()
         g_z = g_z.contiguous() if g_z is not None else None
-        gp = gT = None
+        gp = gK = gT = None
         if ctx.needs_input_grad[0]:
             gp = torch.empty_like(p)
             L.call("e2e_project3d_bwd", L.ptr(p), L.ptr(K), L.ptr(T), L.ptr(g_grid), L.ptr(g_z), L.ptr(gp), B, H, W, L.stream())
@@ -86,7 +92,12 @@ class _Project3D(torch.autograd.Function):
             ws = torch.empty(L.load().e2e_project3d_bwd_t_workspace_bytes(B), device=p.device, dtype=torch.uint8)
             L.call("e2e_project3d_bwd_t", points=L.ptr(p), K=L.ptr(K), T=L.ptr(T), g_grid=L.ptr(g_grid), g_z=L.ptr(g_z), g_T=L.ptr(gT),
                    workspace=L.ptr(ws), B=B, H=H, W=W, stream=L.stream())
-        return gp, None, gT, None, None, None
+        if ctx.needs_input_grad[1]:          # K is a parameter (self-calibration): d/dK through the same P, g_K[:3] = Pbar T^T
+            gK = torch.empty_like(K)
+            ws = torch.empty(L.query("e2e_project3d_bwd_k_workspace_bytes", B), device=p.device, dtype=torch.uint8)
+            L.call("e2e_project3d_bwd_k", points=L.ptr(p), K=L.ptr(K), T=L.ptr(T), g_grid=L.ptr(g_grid), g_z=L.ptr(g_z), g_K=L.ptr(gK),
+                   workspace=L.ptr(ws), B=B, H=H, W=W, stream=L.stream())
+        return gp, gK, gT, None, None, None
 
 
 def project3d(points, K, T, height, width, geometric=False):
@@ -192,10 +203,11 @@ def photometric(prediction, target):
 
 
 # ---------------------------------------------------------------------------------------------
-def _check_warp_inputs(fn, depth_tgt, srcs, tgt, K, inv_K, n_poses=None):
-    """What warp_photometric and warp_photometric_window (`fn`) refuse alike: intrinsics that require grad, a depth_tgt that is not (B,1,H,W),
-    for the window (n_poses given) anything but 1 or 2 sources and as many poses, frames that are not (B,3,H,W).  Returns (B, H, W)."""
-    if torch.is_grad_enabled():
+def _check_warp_inputs(fn, depth_tgt, srcs, tgt, K, inv_K, n_poses=None, intrinsics_grad=False):
+    """What warp_photometric and warp_photometric_window (`fn`) refuse alike: intrinsics that require grad without intrinsics_grad=True, a
+    depth_tgt that is not (B,1,H,W), for the window (n_poses given) anything but 1 or 2 sources and as many poses, frames that are not
+    (B,3,H,W).  Returns (B, H, W)."""
+    if torch.is_grad_enabled() and not intrinsics_grad:
         for n, t in (("K", K), ("inv_K", inv_K)):
             if torch.is_tensor(t) and t.requires_grad:
                 raise NotImplementedError(f"{fn}: {n} requires grad, and the fused kernels have no gradient with respect to the intrinsics")
@@ -251,18 +263,23 @@ class _WarpPhotometric(torch.autograd.Function):
                       inv_K=L.ptr(inv_K), T=L.ptr(T), synth=L.ptr(synth), valid=L.ptr(valid), use_mask=use_mask, padding_mode=pad, reg_kind=reg_kind,
                       reg_init_tgt=L.ptr(it), reg_init_src=L.ptr(is_), depth_src=L.ptr(ds), g_loss=L.ptr(gl), g_depth_tgt=L.ptr(gdt),
                       g_depth_src=L.ptr(gds), B=B, H=H, W=W, stream=L.stream())
-        gT = None
+        gT = gK = giK = None
         if ctx.needs_input_grad[8]:          # the pose carries a graph (differentiable odometry, e2ehip.icp): the same kernel also sums d/dT
             gT = torch.empty(B, 4, 4, device=dt.device, dtype=torch.float32)
+        if ctx.needs_input_grad[6] or ctx.needs_input_grad[7]:      # an intrinsic is a parameter (intrinsics_grad=True): 9 sums more, both gradients
+            gK, giK = (torch.empty(B, 4, 4, device=dt.device, dtype=torch.float32) for _ in range(2))
+            ws = torch.empty(L.query("e2e_warp_photo_bwd_intrinsics_workspace_bytes", B, H, W), device=dt.device, dtype=torch.uint8)
+            L.call("e2e_warp_photo_bwd_intrinsics", g_T=L.ptr(gT), g_K=L.ptr(gK), g_inv_K=L.ptr(giK), workspace=L.ptr(ws), **common)
+        elif gT is not None:
             ws = torch.empty(L.load().e2e_warp_photo_bwd_pose_workspace_bytes(B, H, W), device=dt.device, dtype=torch.uint8)
             L.call("e2e_warp_photo_bwd_pose", g_T=L.ptr(gT), workspace=L.ptr(ws), **common)
         else:
             L.call("e2e_warp_photo_bwd", **common)
-        return (gdt, gds) + (None,) * 6 + (gT,) + (None,) * 4
+        return (gdt, gds) + (None,) * 4 + (gK if ctx.needs_input_grad[6] else None, giK if ctx.needs_input_grad[7] else None, gT) + (None,) * 4
 
 
 def warp_photometric(depth_tgt, src, tgt, K, inv_K, T, padding_mode="border", use_mask=True,
-                     depth_src=None, init_tgt=None, init_src=None, reg_kind=None, want_pmap=False):
+                     depth_src=None, init_tgt=None, init_src=None, reg_kind=None, want_pmap=False, intrinsics_grad=False):
     """Fused image-space part of one refinement step (2 launches forward, 1 backward; 2 backward when T requires grad).
 
     depth_tgt (B,1,H,W); src/tgt (B,3,H,W) views (NHWC memory welcome); K, inv_K, T (B,4,4).
@@ -271,9 +288,13 @@ def warp_photometric(depth_tgt, src, tgt, K, inv_K, T, padding_mode="border", us
 
     Differentiated: depth_tgt, depth_src (through the regulariser only) and T (e2e_warp_photo_bwd_pose; the gradient has the shape of
     the T that was passed, so a pose expanded over the batch gets the sum).  The frames, init_tgt / init_src and the outputs synth, valid
-    and pmap are constants.  K and inv_K are constants too: one that requires grad raises NotImplementedError.
+    and pmap are constants.  K and inv_K are constants too: one that requires grad raises NotImplementedError -- unless
+    intrinsics_grad=True (self-calibration): then the backward is e2e_warp_photo_bwd_intrinsics whenever K or inv_K requires grad, and
+    K.grad / inv_K.grad have the shape of what was passed (a (4,4) matrix expanded over the batch gets the sum).  K and inv_K are
+    independent inputs: the gradient of each is taken with the other held fixed.  With neither requiring grad the launches are the same
+    as without the keyword.
     reference: online_adaption.py:412-455, :544-564, :482-511, :612-623."""
-    B, H, W = _check_warp_inputs("warp_photometric", depth_tgt, [src], tgt, K, inv_K)
+    B, H, W = _check_warp_inputs("warp_photometric", depth_tgt, [src], tgt, K, inv_K, intrinsics_grad=bool(intrinsics_grad))
     rk = {None: 0, "l1": 1, "l2": 2}.get(reg_kind, -1)
     if rk < 0:
         raise ValueError("please specify a correct norm")          # losses.py:146
@@ -344,24 +365,31 @@ class _WarpPhotometricWindow(torch.autograd.Function):
         gl = gl.contiguous()
         gdt = torch.empty(B, 1, H, W, device=dev, dtype=torch.float32)
         gds = torch.empty(S, B, 1, H, W, device=dev, dtype=torch.float32) if geo else None
-        gT = ws = None
+        gT = gK = giK = ws = None
         if ctx.needs_input_grad[8] or (S == 2 and ctx.needs_input_grad[9]):      # a pose carries a graph: the same launch also sums d/dT
             gT = torch.empty(S, B, 4, 4, device=dev, dtype=torch.float32)
-        if geo or gT is not None:                              # the pose sums; the geometric form's depth scatter always needs its scratch
-            ws = torch.empty(L.query(name + "_bwd_workspace_bytes", S, B, H, W), device=dev, dtype=torch.uint8)
         more = dict(depth_src0=L.ptr(ds0), depth_src1=L.ptr(ds1), geo_count=L.ptr(count), geo_min_valid=geo_min_valid,
                     g_depth_src=L.ptr(gds)) if geo else {}
-        L.call(name + "_bwd", depth_tgt=L.ptr(dt), src0=L.ptr(src0), src1=L.ptr(src1), src_strides=L.strides4(src0), tgt=L.ptr(tgt),
+        entry = name + "_bwd"
+        if ctx.needs_input_grad[6] or ctx.needs_input_grad[7]:  # an intrinsic is a parameter (intrinsics_grad=True): both gradients, summed over the sources
+            entry = name + "_bwd_intrinsics"
+            gK, giK = (torch.empty(B, 4, 4, device=dev, dtype=torch.float32) for _ in range(2))
+            more.update(g_K=L.ptr(gK), g_inv_K=L.ptr(giK))
+        if geo or gT is not None or gK is not None:            # the float64 sums; the geometric form's depth scatter always needs its scratch
+            ws = torch.empty(L.query(entry + "_workspace_bytes", S, B, H, W), device=dev, dtype=torch.uint8)
+        L.call(entry, depth_tgt=L.ptr(dt), src0=L.ptr(src0), src1=L.ptr(src1), src_strides=L.strides4(src0), tgt=L.ptr(tgt),
                tgt_strides=L.strides4(tgt), K=L.ptr(K), inv_K=L.ptr(inv_K), T=L.ptr(T), synth=L.ptr(synth), valid=L.ptr(valid), select=L.ptr(select),
                use_mask=use_mask, padding_mode=pad, terms=terms, g_loss=L.ptr(gl), g_depth_tgt=L.ptr(gdt), g_T=L.ptr(gT), workspace=L.ptr(ws),
                S=S, B=B, H=H, W=W, stream=L.stream(), **more)
         g_T0 = gT[0] if gT is not None and ctx.needs_input_grad[8] else None
         g_T1 = gT[1] if gT is not None and S == 2 and ctx.needs_input_grad[9] else None
-        return (gdt, gds[0] if geo else None, gds[1] if geo and S == 2 else None) + (None,) * 5 + (g_T0, g_T1) + (None,) * 6
+        return (gdt, gds[0] if geo else None, gds[1] if geo and S == 2 else None) + (None,) * 3 + \
+            (gK if ctx.needs_input_grad[6] else None, giK if ctx.needs_input_grad[7] else None, g_T0, g_T1) + (None,) * 6
 
 
 def warp_photometric_window(depth_tgt, srcs, tgt, K, inv_K, Ts, padding_mode="border", use_mask=True, min_reprojection=False,
-                            auto_masking=False, tie_noise=None, want_pmap=False, geometric=False, depth_srcs=None, geo_min_valid=10000):
+                            auto_masking=False, tie_noise=None, want_pmap=False, geometric=False, depth_srcs=None, geo_min_valid=10000,
+                            intrinsics_grad=False):
     """The fused pair over a window of one or two source frames with the candidate / minimum logic of train_depth.py:621-662
     (e2e_warp_photo_window_fwd / _bwd: 2 launches forward, 1 backward; 2 backward when a pose requires grad).
 
@@ -377,10 +405,12 @@ def warp_photometric_window(depth_tgt, srcs, tgt, K, inv_K, Ts, padding_mode="bo
     the index of the first minimal candidate, pmap (B,1,H,W): the minimum, when asked for).
 
     Differentiated: depth_tgt and every T (the gradient has the shape of the T that was passed, so a pose expanded over the batch gets the
-    sum).  Frames, masks, tie_noise and the other outputs are constants; K or inv_K requiring grad raises NotImplementedError."""
+    sum).  Frames, masks, tie_noise and the other outputs are constants; K or inv_K requiring grad raises NotImplementedError unless
+    intrinsics_grad=True: then the backward is e2e_warp_photo_window_bwd_intrinsics / e2e_warp_photo_geo_bwd_intrinsics whenever one of them
+    requires grad, and K.grad / inv_K.grad (the sum over the sources) have the shape of what was passed."""
     srcs, Ts = list(srcs), list(Ts)
     S = len(srcs)
-    B, H, W = _check_warp_inputs("warp_photometric_window", depth_tgt, srcs, tgt, K, inv_K, n_poses=len(Ts))
+    B, H, W = _check_warp_inputs("warp_photometric_window", depth_tgt, srcs, tgt, K, inv_K, n_poses=len(Ts), intrinsics_grad=bool(intrinsics_grad))
     if tie_noise is not None and tuple(tie_noise.shape) != (B, S, H, W):
         raise ValueError(f"tie_noise: expected ({B},{S},{H},{W}), got {tuple(tie_noise.shape)}")
     terms = (TERM_AUTO_MASKING if auto_masking else 0) | (TERM_MIN_REPROJECTION if min_reprojection else 0)

@@ -5,10 +5,15 @@
 * `learn_depth_scale`   -- absolute_scale.py:207-240: a `ScaleLayer` (one scalar) or `Conv1x1(1, 1, bias=True)` (scale +
   offset) on top of a fixed depth prediction, trained through the same loss.
 
-Both run one `e2e_warp_photo_lossgrad` launch + one fused Adam launch per step; nothing else touches the GPU."""
+* `learn_intrinsics`    -- self-calibration: four factors on fx, fy, cx, cy of K, trained through the same loss with depth and pose fixed
+  (the reference's scale_by_f / normalize_intrinsics / utils/pretrained_focal.py exist because the focal length may not match the data).
+
+The first two run one `e2e_warp_photo_lossgrad` launch + one fused Adam launch per step; nothing else touches the GPU.  The third runs
+the fused forward / backward pair with the gradient with respect to the intrinsics, torch's autograd on the 4x4 matrices, and fused Adam."""
 import torch
 
 from . import _lib as L
+from . import ops
 from .fused import LossGradPlan
 from .optim import FusedAdam
 
@@ -86,6 +91,59 @@ def learn_depth_scale(depth_pred, src, tgt, K, T, steps=50, lr=1e-2, init_value=
                 prm.grad.copy_(gr)
         opt.step()
     return float(w.data), float(b.data), [float(v[0]) for v in torch.stack(trace).cpu()]
+
+
+def intrinsics_from_factors(K, factors):
+    """K (B,4,4), a zero-skew pinhole matrix; factors (4,) on fx, fy, cx, cy -> (K_eff, inv_K_eff), both (B,4,4): the scaled matrix and its
+    closed-form inverse, built with torch on the 4x4 so that autograd carries d/d factors (any device)."""
+    fx, fy, cx, cy = factors[0] * K[:, 0, 0], factors[1] * K[:, 1, 1], factors[2] * K[:, 0, 2], factors[3] * K[:, 1, 2]
+    z, o = torch.zeros_like(fx), torch.ones_like(fx)
+    K_eff = torch.stack([fx, z, cx, z, z, fy, cy, z, z, z, o, z, z, z, z, o], -1).view(-1, 4, 4)
+    inv = torch.stack([1 / fx, z, -cx / fx, z, z, 1 / fy, -cy / fy, z, z, z, o, z, z, z, z, o], -1).view(-1, 4, 4)
+    return K_eff, inv
+
+
+def _require_pinhole(K):
+    if K.dim() != 3 or tuple(K.shape[1:]) != (4, 4):
+        raise ValueError(f"K: expected (B,4,4), got {tuple(K.shape)}")
+    Kc = K.detach().cpu()
+    rest = Kc.clone()
+    rest[:, 0, 0] = rest[:, 1, 1] = rest[:, 0, 2] = rest[:, 1, 2] = 0
+    rest[:, 2, 2] -= 1
+    rest[:, 3, 3] -= 1
+    if bool(rest.ne(0).any()) or bool((Kc[:, 0, 0] == 0).any()) or bool((Kc[:, 1, 1] == 0).any()) or not bool(torch.isfinite(Kc).all()):
+        raise ValueError("learn_intrinsics: K must be a zero-skew pinhole matrix [[fx,0,cx,0],[0,fy,cy,0],[0,0,1,0],[0,0,0,1]] with fx, fy != 0")
+
+
+def learn_intrinsics(depth_tgt, src, tgt, K, T, steps, lr, padding_mode="border", use_mask=True, init=(1, 1, 1, 1)):
+    """Self-calibration through the photometric loss: four factors on fx, fy, cx, cy of the zero-skew pinhole K (B,4,4; anything else raises
+    ValueError) are trained by FusedAdam through ops.warp_photometric(intrinsics_grad=True) -- K_eff and its closed-form inverse are
+    rebuilt from the factors every step (intrinsics_from_factors), the fused backward returns dL/dK_eff and dL/d inv_K_eff, and torch
+    carries both onto the factors.  Depth (B,1,H,W) and pose (B,4,4) are fixed.  Returns (factors (4,) on the CPU, K_eff (B,4,4) at those
+    factors, [loss per step])."""
+    if len(init) != 4:
+        raise ValueError("init: four factors, on fx, fy, cx, cy")
+    d = L.dev(depth_tgt, "depth_tgt").detach().contiguous()
+    K = L.dev(K, "K").detach()
+    _require_pinhole(K)
+    T = L.dev(T, "T").detach().contiguous()
+    f = torch.nn.Parameter(torch.tensor([float(v) for v in init], device=d.device))
+    opt = FusedAdam([f], lr=lr)
+    trace = []
+    for _ in range(steps):
+        K_eff, inv_eff = intrinsics_from_factors(K, f)
+        loss = ops.warp_photometric(d, src, tgt, K_eff, inv_eff, T, padding_mode=padding_mode, use_mask=use_mask, intrinsics_grad=True)["photometric"]
+        g, = torch.autograd.grad(loss, f)
+        trace.append(loss.detach().clone())
+        opt.zero_grad()
+        if f.grad is None:
+            f.grad = g.clone()
+        else:
+            f.grad.copy_(g)
+        opt.step()
+    with torch.no_grad():
+        K_eff = intrinsics_from_factors(K, f.data)[0].clone()
+    return f.data.detach().cpu().clone(), K_eff, ([float(v) for v in torch.stack(trace).cpu()] if trace else [])
 
 
 def scale_grid_search(depth_pred, src, tgt, K, T, grid, steps=3, lr=1e-2, affine=True, padding_mode="border", use_mask=True, init_bias=0.0):

@@ -78,6 +78,18 @@ int e2e_project3d_bwd(const float* points, const float* K, const float* T, const
 int64_t e2e_project3d_bwd_t_workspace_bytes(int B);
 int e2e_project3d_bwd_t(const float* points, const float* K, const float* T, const float* g_grid,
                         const float* g_z, float* g_T, void* workspace, int B, int H, int W, void* stream);
+/* ... and with respect to K, by the same convention: g_K (B,4,4) = d/dK of sum(g_grid . grid) + sum(g_z . z_out).  K enters through rows
+ * 0..2 of K T only: with Pbar = sum cbar p^T (3x4; cbar the fp32 expressions of e2e_project3d_bwd, its clamp(1e-3) rule for g_z included;
+ * float64 sums in a fixed order, no atomics), g_K[:3,:] = Pbar T^T and row 3 is 0.  workspace: e2e_project3d_bwd_k_workspace_bytes(B) bytes. */
+int64_t e2e_project3d_bwd_k_workspace_bytes(int B);
+int e2e_project3d_bwd_k(const float* points, const float* K, const float* T, const float* g_grid, const float* g_z,
+                        float* g_K, void* workspace, int B, int H, int W, void* stream);
+/* the adjoint of e2e_backproject_fwd with respect to inv_K: depth (B,H*W), g_cam (B,4,H*W) -> g_inv_K (B,4,4) with
+ * g_inv_K[r][j] = sum g_cam[r] depth pix_j for r, j < 3, pix = (x, y, 1); row 3 and column 3 are 0 (the forward reads inv_K[:3,:3] only).
+ * float64 sums in a fixed order, no atomics.  workspace: e2e_backproject_bwd_invk_workspace_bytes(B) bytes. */
+int64_t e2e_backproject_bwd_invk_workspace_bytes(int B);
+int e2e_backproject_bwd_invk(const float* g_cam, const float* depth, float* g_inv_K, void* workspace, int B, int H, int W,
+                             void* stream);
 
 /* F.grid_sample(input, grid, mode="bilinear", padding_mode, align_corners) as called at
  * online_adaption.py:431-439,450-453.  input (B,C,Hi,Wi) via strides, grid (B,Ho,Wo,2) contiguous,
@@ -182,6 +194,40 @@ int e2e_warp_photo_bwd_pose(const float* depth_tgt, const float* src, e2e_stride
                             const float* reg_init_src, const float* depth_src, const float* g_loss,
                             float* g_depth_tgt, float* g_depth_src, float* g_T, void* workspace, int B,
                             int H, int W, void* stream);
+
+/* The same backward with the gradient with respect to the camera intrinsics as well (self-calibration through the photometric loss; the
+ * reference carries scale_by_f, normalize_intrinsics and utils/pretrained_focal.py because the focal length may not match the data).
+ * Four launches (three without g_T): the kernel of e2e_warp_photo_bwd_pose itself (depth gradients and pose sums: its bits), a second
+ * pass of the same tile kernel that stores only the nine sums Q below, the final kernel of e2e_warp_photo_bwd_pose when g_T is asked for,
+ * and a final kernel of one workgroup per batch element for the intrinsics.
+ *   RULE.  The conventions are those of e2e_warp_photo_bwd_pose: z = c2 + 1e-7, /(W-1) and /(H-1), the validity mask a constant, zero slope
+ *     under an active border clamp.  Per batch element and source s:  P_s = (K T_s)[:3,:],  pix = (x, y, 1),  cam = inv_K[:3,:3] pix,
+ *     X = d cam,  c = P_s [X;1].  K enters through rows 0..2 of K T only and inv_K through its upper-left 3x3 only.  With (gc0, gc1, gc2)
+ *     the very fp32 adjoint of c that reaches g_depth_tgt, in float64:
+ *       Pbar_s[i][j] = sum gc_i X_j (j < 3),  Pbar_s[i][3] = sum gc_i      the pose sums, in the place and layout they have there;
+ *       Q_s[i][j]    = sum gc_i d pix_j  (i, j < 3)                        from the same fp32 gc and d, pix exact; pixels outside add 0;
+ *       g_K[i][k]     = sum_s sum_{j<4} Pbar_s[i][j] T_s[k][j]   for i < 3, k < 4;   row 3 is 0;
+ *       g_inv_K[r][j] = sum_s sum_{i<3} P_s[i][r] Q_s[i][j]      for r, j < 3;       row 3 and column 3 are 0;
+ *     P_s is formed in float64 from the fp32 K and T_s, the sources are added in the order s = 0, 1, and all 16 entries of both outputs
+ *     are written.  (The pair has the one source s = 0.)  Under the geometric term gc2 carries that term's adjoint, so the same formulas
+ *     hold for e2e_warp_photo_geo_bwd_intrinsics.
+ *   g_K, g_inv_K (B,4,4)       both required;
+ *   g_T (B,4,4) or NULL        NULL: the pose final stage is not launched; otherwise bit-identical to e2e_warp_photo_bwd_pose's;
+ *   g_depth_tgt, g_depth_src   bit-identical to what e2e_warp_photo_bwd writes for the same arguments.
+ *   The sums are float64 in the fixed order of e2e_warp_photo_bwd_pose (wave shuffle, the four waves through LDS, per workgroup 12 doubles
+ *     in [B][tiles][12] and 9 in a second region [B][tiles][9] behind them); the final kernel folds the tiles per sum (lane l adds
+ *     l, l + 64, ... in order, then a shuffle tree).  No atomics: two runs give the same bits.
+ *   workspace: e2e_warp_photo_bwd_intrinsics_workspace_bytes(B,H,W) bytes = 8 x 21 B ceil(H/8) ceil(W/32) (0 for a non-positive size).
+ *   A refused call (NULL g_K, g_inv_K or workspace or any pointer e2e_warp_photo_bwd needs, bad dimensions, padding_mode or reg_kind)
+ *     returns E2E_ERR_ARG before any launch and writes nothing. */
+int64_t e2e_warp_photo_bwd_intrinsics_workspace_bytes(int B, int H, int W);
+int e2e_warp_photo_bwd_intrinsics(const float* depth_tgt, const float* src, e2e_strides src_strides,
+                                  const float* tgt, e2e_strides tgt_strides, const float* K, const float* inv_K,
+                                  const float* T, const float* synth, const float* valid, int use_mask,
+                                  int padding_mode, int reg_kind, const float* reg_init_tgt,
+                                  const float* reg_init_src, const float* depth_src, const float* g_loss,
+                                  float* g_depth_tgt, float* g_depth_src, float* g_T, float* g_K, float* g_inv_K,
+                                  void* workspace, int B, int H, int W, void* stream);
 
 /* The step the build's driver actually launches: loss AND gradient in ONE pass (the gradient of a
  * mean does not depend on its value, so forward and backward of the image-space part collapse;
@@ -358,6 +404,29 @@ int e2e_warp_photo_geo_bwd(const float* depth_tgt, const float* depth_src0, cons
                            const int* select, const int* geo_count, int use_mask, int padding_mode, int terms,
                            int geo_min_valid, const float* g_loss, float* g_depth_tgt, float* g_depth_src, float* g_T,
                            void* workspace, int S, int B, int H, int W, void* stream);
+
+/* e2e_warp_photo_window_bwd and e2e_warp_photo_geo_bwd with the gradient with respect to the intrinsics: the rule of
+ * e2e_warp_photo_bwd_intrinsics with one (Pbar_s, Q_s) per source, added in the order s = 0, 1.
+ *   g_K, g_inv_K (B,4,4)   both required;   g_T (S,B,4,4) or NULL: NULL skips the pose final stage, otherwise the bits of the form above;
+ *   g_depth_tgt (and the geometric form's g_depth_src): bit-identical to what the form above writes for the same arguments.
+ *   workspace (required): e2e_warp_photo_window_bwd_intrinsics_workspace_bytes = 8 x 21 S B ceil(H/8) ceil(W/32) bytes -- the pose sums
+ *     [S][B][tiles][12] where e2e_warp_photo_window_bwd has them, then [S][B][tiles][9];  e2e_warp_photo_geo_bwd_intrinsics_workspace_bytes =
+ *     8 (S B H W + S) + 8 x 21 S B ceil(H/8) ceil(W/32): the fixed-point sums first.  0 for a non-positive size or an S outside 1..2.
+ *   A refused call (what the form above refuses, or a NULL g_K, g_inv_K or workspace) returns E2E_ERR_ARG before any launch and writes
+ *     nothing.  Bitwise reproducible run to run. */
+int64_t e2e_warp_photo_window_bwd_intrinsics_workspace_bytes(int S, int B, int H, int W);
+int e2e_warp_photo_window_bwd_intrinsics(const float* depth_tgt, const float* src0, const float* src1, e2e_strides src_strides,
+                                         const float* tgt, e2e_strides tgt_strides, const float* K, const float* inv_K,
+                                         const float* T, const float* synth, const float* valid, const int* select, int use_mask,
+                                         int padding_mode, int terms, const float* g_loss, float* g_depth_tgt, float* g_T,
+                                         float* g_K, float* g_inv_K, void* workspace, int S, int B, int H, int W, void* stream);
+int64_t e2e_warp_photo_geo_bwd_intrinsics_workspace_bytes(int S, int B, int H, int W);
+int e2e_warp_photo_geo_bwd_intrinsics(const float* depth_tgt, const float* depth_src0, const float* depth_src1, const float* src0,
+                                      const float* src1, e2e_strides src_strides, const float* tgt, e2e_strides tgt_strides,
+                                      const float* K, const float* inv_K, const float* T, const float* synth, const float* valid,
+                                      const int* select, const int* geo_count, int use_mask, int padding_mode, int terms,
+                                      int geo_min_valid, const float* g_loss, float* g_depth_tgt, float* g_depth_src, float* g_T,
+                                      float* g_K, float* g_inv_K, void* workspace, int S, int B, int H, int W, void* stream);
 
 /* online_adaption.py:600-610 + losses.py:119-132 for ONE frame: edge-aware first-order smoothness of
  * disp / (mean(disp) + 1e-7) with the edges of img (3,H,W through strides; the batch stride is not used), fused
