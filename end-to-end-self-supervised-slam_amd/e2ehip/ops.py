@@ -788,6 +788,97 @@ def depth_from_disp_range(disp, min_depth, max_depth, scale=1.0):
     return _RangeDepth.apply(disp, min_depth, max_depth, scale)
 
 
+PYRAMID_SCALES = 4                    # disp0 .. disp3 of e2e_disp_pyramid_depth_fwd / _bwd
+
+
+def _pyramid_args(ds):
+    """disp0 .. disp3 and h0, w0 .. h3, w3 of the pyramid entry points: the given scales in the first slots, the rest absent"""
+    pad = PYRAMID_SCALES - len(ds)
+    sizes = [n for d in ds for n in d.shape[2:]] + [0] * (2 * pad)
+    return [L.ptr(d) for d in ds] + [None] * pad + sizes
+
+
+class _DispPyramidDepth(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, size, min_depth, max_depth, scale, *disps):
+        ds = [L.dev(d, "disp").contiguous() for d in disps]
+        B, (H, W) = ds[0].shape[0], size
+        ctx.cfg = (B, H, W, float(min_depth), float(max_depth), float(scale))
+        depth = torch.empty(len(ds), B, 1, H, W, device=ds[0].device, dtype=torch.float32)
+        L.call("e2e_disp_pyramid_depth_fwd", *_pyramid_args(ds), *ctx.cfg, L.ptr(depth), L.stream())
+        ctx.save_for_backward(*ds)
+        return depth
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        ds = ctx.saved_tensors
+        gds = [torch.empty_like(d) for d in ds]
+        L.call("e2e_disp_pyramid_depth_bwd", L.ptr(g.contiguous()), *_pyramid_args(ds), *ctx.cfg,
+               *([L.ptr(t) for t in gds] + [None] * (PYRAMID_SCALES - len(gds))), L.stream())
+        return (None,) * 4 + tuple(gds)
+
+
+def disp_pyramid_depth(disps, size, min_depth, max_depth, scale=1.0):
+    """The monodepth2 disparity pyramid at full resolution: every (B,1,h_s,w_s) disparity of `disps` (1 to 4 scales, finest first)
+    upsampled bilinearly to size = (H, W) as F.interpolate(align_corners=False) does and converted to depth as depth_from_disp_range
+    does -> (S,B,1,H,W).  One launch forward (e2e_disp_pyramid_depth_fwd), one backward (e2e_disp_pyramid_depth_bwd: a gather, no
+    atomics), a gradient to every disparity; a scale that already has the full size comes out bit-equal to depth_from_disp_range."""
+    disps = list(disps)
+    if not 1 <= len(disps) <= PYRAMID_SCALES:
+        raise ValueError(f"disps: expected 1 to {PYRAMID_SCALES} scales, got {len(disps)}")
+    H, W = (int(n) for n in size)
+    for s, d in enumerate(disps):
+        if not torch.is_tensor(d) or d.dim() != 4 or d.shape[1] != 1:
+            raise ValueError(f"disps[{s}]: expected (B,1,h,w), got {tuple(d.shape) if torch.is_tensor(d) else type(d).__name__}")
+        if d.shape[0] != disps[0].shape[0]:
+            raise ValueError(f"disps[{s}]: expected ({disps[0].shape[0]},1,h,w), got {tuple(d.shape)}")
+        if not (1 <= d.shape[2] <= H and 1 <= d.shape[3] <= W):
+            raise ValueError(f"disps[{s}]: {d.shape[2]} x {d.shape[3]} does not fit the full size {H} x {W} (the pyramid only upsamples)")
+    if not 0 < float(min_depth) < float(max_depth):
+        raise ValueError(f"expected 0 < min_depth < max_depth, got {min_depth} and {max_depth}")
+    return _DispPyramidDepth.apply((H, W), min_depth, max_depth, scale, *disps)
+
+
+def warp_photometric_multiscale(disps, srcs, tgt, K, inv_K, Ts, min_depth, max_depth, scale=1.0, padding_mode="border", use_mask=True,
+                                min_reprojection=False, auto_masking=False, tie_noise=None):
+    """monodepth2's multi-scale image-space loss: every scale's disparity is brought to the size of the frames and converted to depth
+    (disp_pyramid_depth), the S scales are stacked along the batch, and ONE fused pair warps and compares them all at full resolution:
+    warp_photometric for one source and no flags, warp_photometric_window otherwise.  The pair's mean over the stacked batch is
+    sum_s loss_s / S.
+
+    disps: 1 to 4 (B,1,h_s,w_s) disparities; srcs: 1 or 2 (B,3,H,W) views and tgt likewise; K, inv_K (B,4,4); Ts: one (B,4,4) pose per
+    source; tie_noise (B,len(srcs),H,W) or None, the same draw for every scale.  With B = 1 the frames are read in place by every scale
+    (a batch stride of 0); with a larger batch they are copied once per scale, as the kernels address the batch by one stride.
+    Returns dict(photometric, photometric_per_scale (S,) detached, depth (S,B,1,H,W)).  Differentiated: every disparity and every T
+    (stacked S times, so a pose with a graph gets the sum over the scales through e2e_warp_photo_bwd_pose / the window's backward)."""
+    srcs, Ts = list(srcs), list(Ts)
+    B, _, H, W = tgt.shape if torch.is_tensor(tgt) and tgt.dim() == 4 else (0, 0, 0, 0)
+    if B == 0 or tgt.shape[1] != 3:
+        raise ValueError(f"target_frame: expected (B,3,H,W), got {tuple(tgt.shape) if torch.is_tensor(tgt) else type(tgt).__name__}")
+    if len(srcs) not in (1, 2) or len(Ts) != len(srcs):
+        raise ValueError(f"warp_photometric_multiscale: expected 1 or 2 source frames and as many poses, got {len(srcs)} and {len(Ts)}")
+    depth = disp_pyramid_depth(disps, (H, W), min_depth, max_depth, scale)
+    S = depth.shape[0]
+    if depth.shape[1] != B:
+        raise ValueError(f"disps: batch {depth.shape[1]} against frames of batch {B}")
+    if B == 1:
+        frames = lambda t: t.expand(S, -1, -1, -1)
+    else:
+        frames = lambda t: t.repeat(S, 1, 1, 1)
+    mats = lambda t: t.unsqueeze(0).expand(S, -1, -1, -1).reshape(S * B, 4, 4)
+    stacked = depth.view(S * B, 1, H, W)
+    if len(srcs) == 1 and not (min_reprojection or auto_masking):
+        out = warp_photometric(stacked, frames(srcs[0]), frames(tgt), mats(K), mats(inv_K), mats(Ts[0]), padding_mode=padding_mode,
+                               use_mask=use_mask, want_pmap=True)
+    else:
+        noise = tie_noise.repeat(S, 1, 1, 1) if tie_noise is not None else None
+        out = warp_photometric_window(stacked, [frames(s) for s in srcs], frames(tgt), mats(K), mats(inv_K), [mats(T) for T in Ts],
+                                      padding_mode=padding_mode, use_mask=use_mask, min_reprojection=min_reprojection,
+                                      auto_masking=auto_masking, tie_noise=noise, want_pmap=True)
+    return {"photometric": out["photometric"], "photometric_per_scale": out["pmap"].view(S, -1).mean(1), "depth": depth}
+
+
 class _MeanDiff(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, b, kind):

@@ -25,6 +25,9 @@ target depth, every source depth and every pose; the `mask.sum() > 10000` gate o
 `MODEL.depth_network` selects the depth network as in the reference (train_depth.py:124-179): `indoor` is DispResNet_Indoor, `monodepth2`
 is ResnetEncoder + DepthDecoder with a sigmoid disparity at every scale of `DATA.scales`, turned into depth by convert_disp_to_depth
 (DATA.min_depth / max_depth) and loaded by load_model() from `<name>.pth` files.
+`LOSS.multiscale: True` (absent = False; monodepth2 only, not in the reference, which took monodepth2's decoder without its loss) takes the
+image-space term on every scale of `DATA.scales` -- each disparity upsampled to the input resolution, e2e_disp_pyramid_depth_fwd / _bwd --
+and averages, on the same fused pair with the scales stacked along the batch; everything else of a step stays on scale 0.
 
     python train_depth.py --config_path configs/config_train_depth.yaml
 """
@@ -69,6 +72,18 @@ class Depth_Estimation:
         if getattr(self.args.VIZ, "tensorboard", False):
             raise NotImplementedError("out of scope: SURVEY.md section 5.5 -- TensorBoard gradient hooks (VIZ.tensorboard)")
         self._sequence, self._state_dict, self.fused_losses = sequence, state_dict, fused_losses
+        # LOSS.multiscale (absent = False): monodepth2's loss -- the image-space term is taken on every scale of DATA.scales, each
+        # disparity upsampled to the input resolution, and averaged (ops.warp_photometric_multiscale), which is what trains the heads of
+        # the coarse scales.  It exists on the fused route only.
+        self.multiscale = bool(getattr(self.args.LOSS, "multiscale", False))
+        if self.multiscale:
+            if self.args.MODEL.depth_network != "monodepth2":
+                raise ValueError("LOSS.multiscale needs MODEL.depth_network: monodepth2 (the indoor network predicts scale 0 only)")
+            if self.args.LOSS.geometric:
+                raise NotImplementedError("LOSS.multiscale with LOSS.geometric: the geometric-consistency term has no multi-scale form")
+            if not fused_losses or self.args.LOSS.photometric_mask is None:
+                raise NotImplementedError("LOSS.multiscale with fused_losses=False (or LOSS.photometric_mask: None): the multi-scale loss "
+                                          "runs on the fused warp-photometric pair only")
         # DATA.use_gt_pose: False -- the estimated poses carry the gradient of the loss through the odometry into the predicted depth, as
         # the reference's do (train_depth.py:381-382, :395).  E2E_POSE_GRAD=0 (or pose_gradient = False): the poses are constants.
         self.pose_gradient = os.environ.get("E2E_POSE_GRAD", "1") != "0"
@@ -261,6 +276,7 @@ class Depth_Estimation:
                         k *= float(intrinsics[0, 0, 0, 0]) / a.ABLATION.focal_pretrain                  # scale_by_f (training_utils.py:142-152)
                     if a.ABLATION.scaled_depth:
                         k *= a.ABLATION.scaling_depth                                                    # fixed "median" scale (:343-345)
+                    self._depth_scale = k
                     if monodepth2:                                                                       # convert_disp_to_depth * k (:297-312)
                         inputs[("depth", index, scale)] = ops.depth_from_disp_range(inputs[("disp", index, scale)], a.DATA.min_depth, a.DATA.max_depth, k)
                     else:
@@ -391,7 +407,20 @@ class Depth_Estimation:
         a = self.args
         frames = a.DATA.frames[1:]
         self.optimizer.zero_grad()
-        if len(frames) == 2 or a.LOSS.min_reprojection or a.LOSS.auto_masking or a.LOSS.geometric:
+        if self.multiscale:
+            # every scale of DATA.scales at full resolution, the scales stacked along the batch of the same fused pair; the SLAM
+            # reconstruction and every other term stay on scale 0
+            noise = None
+            if a.LOSS.min_reprojection and a.LOSS.auto_masking:
+                B, _, H, W = inputs["target_depth"].shape
+                noise = torch.randn((B, len(frames), H, W), device=inputs["target_depth"].device) * 0.00001     # "Break tie's" (:650)
+            out = ops.warp_photometric_multiscale([inputs["disp", self._tgt_index, s] for s in sorted(a.DATA.scales)],
+                                                  [inputs["source_frame", f] for f in frames], inputs["target_frame"], inputs["K"],
+                                                  inputs["Inverse_K"], [inputs["T", f] for f in frames], a.DATA.min_depth, a.DATA.max_depth,
+                                                  self._depth_scale, padding_mode=a.MODEL.padding_mode, use_mask=bool(a.LOSS.photometric_mask),
+                                                  min_reprojection=bool(a.LOSS.min_reprojection), auto_masking=bool(a.LOSS.auto_masking),
+                                                  tie_noise=noise)
+        elif len(frames) == 2 or a.LOSS.min_reprojection or a.LOSS.auto_masking or a.LOSS.geometric:
             noise = None
             if a.LOSS.min_reprojection and a.LOSS.auto_masking:
                 B, _, H, W = inputs["target_depth"].shape

@@ -1129,6 +1129,35 @@ int e2e_disp_range_depth_fwd(const float* disp, float min_depth, float max_depth
 int e2e_disp_range_depth_bwd(const float* g_depth, const float* disp, float min_depth, float max_depth, float scale, float* g_disp,
                              int64_t n, void* stream);
 
+/* The multi-scale photometric loss of monodepth2 (csrc/disp_pyramid.hip; LOSS.multiscale): every scale's disparity is upsampled
+ * bilinearly to the input resolution and converted to depth, so that each scale is warped and compared at full resolution.  For a scale
+ * with disparity d (B,1,h,w) and the full size (H,W), h <= H and w <= W -- F.interpolate(d, size=(H,W), mode="bilinear",
+ * align_corners=False) followed by e2e_disp_range_depth_fwd:
+ *     sy = max((y + 0.5) * h / H - 0.5, 0),  y0 = floor(sy),  y1 = min(y0 + 1, h - 1),  wy = sy - y0        (the same in x)
+ *     u(y,x)     = (1-wy)(1-wx) d[y0,x0] + (1-wy) wx d[y0,x1] + wy (1-wx) d[y1,x0] + wy wx d[y1,x1]
+ *     depth(y,x) = scale / (lo + (hi - lo) u),   lo = 1 / max_depth, hi = 1 / min_depth
+ * and the adjoint, with u recomputed from d (nothing is saved between the two calls):
+ *     g_u = -g_depth * scale * (hi - lo) / (lo + (hi - lo) u)^2
+ *     g_d[j,i] = sum over every fine pixel (y,x) whose stencil touches (j,i) of its weight on (j,i) times g_u(y,x)
+ * (row 0 also receives the fine rows whose sy was clamped to 0, row h-1 both weights of the fine rows whose y1 was clamped onto y0;
+ * columns likewise).  The adjoint is a gather: the lanes that own a coarse pixel walk its footprint in a fixed order and are added by a
+ * fixed tree; no atomics and no workspace, two calls give the same bits.  Both directions take one stencil function, so the adjoint's
+ * weights are the forward's.
+ *
+ * Up to four scales in ONE launch each way: disp0 .. disp3 with their sizes h0,w0 .. h3,w3; a NULL disparity is an absent scale, and
+ * its sizes (and g_disp) are not read.  depth and g_depth are (S,B,1,H,W) over the S present scales in ascending order; the grid's z
+ * index is (scale, batch element).  Where h == H and w == W every weight is exactly 0 or 1, and that scale's depth and g_disp are
+ * bit-equal to e2e_disp_range_depth_fwd / _bwd on the same input.
+ * Refused with E2E_ERR_ARG before any launch, nothing written: a NULL depth / g_depth; no scale present; a present scale with h > H,
+ * w > W or a non-positive size, or (backward) a NULL g_disp; B < 1, H < 1 or W < 1; not 0 < min_depth < max_depth; and the limits of
+ * the launch geometry: H or W above 262140, S * B above 65535, a coarse pixel whose footprint exceeds 2^31 - 1 fine pixels. */
+int e2e_disp_pyramid_depth_fwd(const float* disp0, const float* disp1, const float* disp2, const float* disp3, int h0, int w0, int h1, int w1,
+                               int h2, int w2, int h3, int w3, int B, int H, int W, float min_depth, float max_depth, float scale,
+                               float* depth, void* stream);
+int e2e_disp_pyramid_depth_bwd(const float* g_depth, const float* disp0, const float* disp1, const float* disp2, const float* disp3, int h0,
+                               int w0, int h1, int w1, int h2, int w2, int h3, int w3, int B, int H, int W, float min_depth, float max_depth,
+                               float scale, float* g_disp0, float* g_disp1, float* g_disp2, float* g_disp3, void* stream);
+
 /* ------------------------------------------------------------------------------------------ */
 /* Frame-to-model ICP odometry (gradslam odometry providers; MODEL.odom: icp | gradicp)          */
 /* ------------------------------------------------------------------------------------------ */
