@@ -416,7 +416,7 @@ __global__ void k_reduce_partials(const float* __restrict__ partials, int nblk, 
 // (k_warp_photo_bwd_intrinsics_final, warp_photo_intrinsics.hip).  It stores no depth gradient and no pose sums: with 21 sums in ONE
 // instantiation hipcc vectorised the fp32 chain differently and g_depth_tgt came out a few ulps off e2e_warp_photo_bwd's on a fifth of the
 // pixels (measured on the MI355X; the twelve pose sums kept their bits), so the depth gradients and Pbar stay with the pose instantiation,
-// which is untouched, and the entry points launch both (warp_photo_bwd_intrinsics_launch).
+// which is untouched, and the intrinsics mode launches both (warp_photo_bwd_run).
 // ---------------------------------------------------------------------------------------------
 template <int SUMS>
 struct PoseOut {};                       // the last kernel argument: empty without the pose gradient, so that launch is the one it was
@@ -619,23 +619,13 @@ static inline dim3 flat_grid(int B, int64_t N) {
     E2E_REQUIRE(B > 0 && H > 1 && W > 1 && (int64_t)B * H * W < (1ll << 31), E2E_ERR_ARG,     \
                 name ": bad dims B=%d H=%d W=%d", B, H, W)
 
-// the one launch of k_warp_photo_bwd: e2e_warp_photo_bwd (WP_SUMS_NONE), warp_photo_bwd_pose_launch and warp_photo_bwd_intrinsics_launch.
-// Arguments are not checked here.
+// the one launch of k_warp_photo_bwd, and the one place where the operand struct is unpacked.  Arguments are not checked here.
 template <int SUMS>
-static void warp_photo_bwd_launch(const float* depth_tgt, const float* src, e2e_strides ss, const float* tgt, e2e_strides ts, const float* K,
-                                  const float* inv_K, const float* T, const float* synth, const float* valid, int use_mask, int padding_mode,
-                                  int reg_kind, const float* reg_init_tgt, const float* reg_init_src, const float* depth_src,
-                                  const float* g_loss, float* g_depth_tgt, float* g_depth_src, int B, int H, int W, PoseOut<SUMS> pose,
-                                  hipStream_t stream) {
-    const dim3 g = tile_grid(B, H, W);
-    if (padding_mode == E2E_PADDING_BORDER)
-        hipLaunchKernelGGL((k_warp_photo_bwd<E2E_PAD_BORDER, SUMS>), g, dim3(TW, TH), 0, stream, depth_tgt, src, ss, tgt, ts, K, inv_K, T,
-                           synth, valid, use_mask, reg_kind, reg_init_tgt, reg_init_src, depth_src, g_loss, g_depth_tgt, g_depth_src, B, H,
-                           W, pose);
-    else
-        hipLaunchKernelGGL((k_warp_photo_bwd<E2E_PAD_ZEROS, SUMS>), g, dim3(TW, TH), 0, stream, depth_tgt, src, ss, tgt, ts, K, inv_K, T,
-                           synth, valid, use_mask, reg_kind, reg_init_tgt, reg_init_src, depth_src, g_loss, g_depth_tgt, g_depth_src, B, H,
-                           W, pose);
+static void warp_photo_bwd_launch(const WarpPhotoBwdArgs& a, PoseOut<SUMS> pose, hipStream_t stream) {
+    const auto kernel = a.padding_mode == E2E_PADDING_BORDER ? k_warp_photo_bwd<E2E_PAD_BORDER, SUMS> : k_warp_photo_bwd<E2E_PAD_ZEROS, SUMS>;
+    hipLaunchKernelGGL(kernel, tile_grid(a.B, a.H, a.W), dim3(TW, TH), 0, stream, a.depth_tgt, a.src, a.src_strides, a.tgt, a.tgt_strides, a.K,
+                       a.inv_K, a.T, a.synth, a.valid, a.use_mask, a.reg_kind, a.reg_init_tgt, a.reg_init_src, a.depth_src, a.g_loss,
+                       a.g_depth_tgt, a.g_depth_src, a.B, a.H, a.W, pose);
 }
 
 extern "C" {
@@ -790,14 +780,9 @@ int e2e_warp_photo_bwd(const float* depth_tgt, const float* src, e2e_strides ss,
                        int use_mask, int padding_mode, int reg_kind, const float* reg_init_tgt,
                        const float* reg_init_src, const float* depth_src, const float* g_loss, float* g_depth_tgt,
                        float* g_depth_src, int B, int H, int W, void* stream) {
-    if (const int rc = warp_photo_check_args("e2e_warp_photo_bwd", B, H, W,
-                                             depth_tgt && src && tgt && K && inv_K && T && synth && valid && g_loss && g_depth_tgt,
-                                             padding_mode, reg_kind, reg_init_tgt && reg_init_src && depth_src && g_depth_src))
-        return rc;
-    warp_photo_bwd_launch<WP_SUMS_NONE>(depth_tgt, src, ss, tgt, ts, K, inv_K, T, synth, valid, use_mask, padding_mode, reg_kind, reg_init_tgt,
-                                 reg_init_src, depth_src, g_loss, g_depth_tgt, g_depth_src, B, H, W, PoseOut<WP_SUMS_NONE>{}, (hipStream_t)stream);
-    E2E_LAUNCH_CHECK("e2e_warp_photo_bwd");
-    return E2E_OK;
+    const WarpPhotoBwdArgs a{depth_tgt, src, ss, tgt, ts, K, inv_K, T, synth, valid, use_mask, padding_mode, reg_kind, reg_init_tgt, reg_init_src,
+                             depth_src, g_loss, g_depth_tgt, g_depth_src, B, H, W};
+    return warp_photo_bwd_run("e2e_warp_photo_bwd", WP_SUMS_NONE, a, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream);
 }
 
 }  // extern "C"
@@ -810,23 +795,34 @@ void warp_photo_reduce_launch(const float* partials, int nblk, int nsets, float 
     hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(256), 0, stream, partials, nblk, nsets, scale, out);
 }
 
-void warp_photo_bwd_pose_launch(const float* depth_tgt, const float* src, e2e_strides ss, const float* tgt, e2e_strides ts, const float* K,
-                                const float* inv_K, const float* T, const float* synth, const float* valid, int use_mask, int padding_mode,
-                                int reg_kind, const float* reg_init_tgt, const float* reg_init_src, const float* depth_src, const float* g_loss,
-                                float* g_depth_tgt, float* g_depth_src, double* partials, int B, int H, int W, hipStream_t stream) {
-    warp_photo_bwd_launch<WP_SUMS_POSE>(depth_tgt, src, ss, tgt, ts, K, inv_K, T, synth, valid, use_mask, padding_mode, reg_kind, reg_init_tgt,
-                                reg_init_src, depth_src, g_loss, g_depth_tgt, g_depth_src, B, H, W, PoseOut<WP_SUMS_POSE>{partials}, stream);
-}
-
-void warp_photo_bwd_intrinsics_launch(const float* depth_tgt, const float* src, e2e_strides ss, const float* tgt, e2e_strides ts, const float* K,
-                                      const float* inv_K, const float* T, const float* synth, const float* valid, int use_mask, int padding_mode,
-                                      int reg_kind, const float* reg_init_tgt, const float* reg_init_src, const float* depth_src,
-                                      const float* g_loss, float* g_depth_tgt, float* g_depth_src, double* partials, double* q_partials, int B,
-                                      int H, int W, hipStream_t stream) {
-    // the pose pass: the depth gradients and Pbar, bit for bit e2e_warp_photo_bwd_pose's; then the Q pass, which stores the 9 sums only
-    warp_photo_bwd_launch<WP_SUMS_POSE>(depth_tgt, src, ss, tgt, ts, K, inv_K, T, synth, valid, use_mask, padding_mode, reg_kind, reg_init_tgt,
-                                        reg_init_src, depth_src, g_loss, g_depth_tgt, g_depth_src, B, H, W, PoseOut<WP_SUMS_POSE>{partials}, stream);
-    warp_photo_bwd_launch<WP_SUMS_INTRINSICS>(depth_tgt, src, ss, tgt, ts, K, inv_K, T, synth, valid, use_mask, padding_mode, reg_kind,
-                                              reg_init_tgt, reg_init_src, depth_src, g_loss, g_depth_tgt, g_depth_src, B, H, W,
-                                              PoseOut<WP_SUMS_INTRINSICS>{q_partials}, stream);
+// the pair's backward in its three modes (warp_photo_tile.h).  Why the intrinsics mode is two passes: the comment of k_warp_photo_bwd.
+int warp_photo_bwd_run(const char* name, int sums, const WarpPhotoBwdArgs& a, float* g_T, float* g_K, float* g_inv_K, void* workspace,
+                       hipStream_t stream) {
+    const bool intr = sums == WP_SUMS_INTRINSICS;
+    const bool outputs = sums == WP_SUMS_NONE || (workspace && (intr ? g_K && g_inv_K : g_T != nullptr));
+    if (const int rc = warp_photo_check_args(name, a.B, a.H, a.W,
+                                             a.depth_tgt && a.src && a.tgt && a.K && a.inv_K && a.T && a.synth && a.valid && a.g_loss &&
+                                                 a.g_depth_tgt && outputs,
+                                             a.padding_mode, a.reg_kind, a.reg_init_tgt && a.reg_init_src && a.depth_src && a.g_depth_src))
+        return rc;
+    if (sums == WP_SUMS_NONE) {
+        warp_photo_bwd_launch(a, PoseOut<WP_SUMS_NONE>{}, stream);
+        return warp_photo_launch_status(name, "");
+    }
+    E2E_REQUIRE(a.B <= 65535, E2E_ERR_ARG, "%s: B=%d exceeds the grid", name, a.B);
+    const WarpPhotoBwdWorkspace ws = warp_photo_bwd_workspace(0, sums, 1, a.B, a.H, a.W);
+    const int tiles = (int)tile_count(a.H, a.W);
+    double *partials = (double*)workspace + ws.partials, *q_partials = (double*)workspace + ws.q_partials;
+    warp_photo_bwd_launch(a, PoseOut<WP_SUMS_POSE>{partials}, stream);
+    if (intr) warp_photo_bwd_launch(a, PoseOut<WP_SUMS_INTRINSICS>{q_partials}, stream);
+    if (const int rc = warp_photo_launch_status(name, "")) return rc;
+    if (g_T) {
+        warp_photo_pose_final_launch(partials, tiles, a.K, g_T, 1, a.B, stream);
+        if (const int rc = warp_photo_launch_status(name, intr ? "(pose)" : "(final)")) return rc;
+    }
+    if (intr) {
+        warp_photo_intrinsics_final_launch(partials, q_partials, tiles, a.K, a.T, g_K, g_inv_K, 1, a.B, stream);
+        if (const int rc = warp_photo_launch_status(name, "(final)")) return rc;
+    }
+    return E2E_OK;
 }

@@ -11,7 +11,8 @@
 //     g_inv_K[r][j] = sum_s sum_{i<3} P_s[i][r] Q_s[i][j]        r, j < 3; row 3 and column 3 are 0
 // with P_s formed in float64 from the fp32 K and T_s and the sources added in the order 0, 1.  Pbar comes from the pose instantiation's own
 // launch, Q from a second pass of the tile kernel that stores nothing else (why two passes: the comment of k_warp_photo_bwd).  Here: the
-// second stage that folds the workgroups' sums in a fixed order and applies the two formulas, and the pair's entry point.
+// second stage that folds the workgroups' sums in a fixed order and applies the two formulas, and the pair's entry point, which fills the
+// operand struct and calls the pair's one backward path (warp_photo_bwd_run, warp_photo.hip).
 // k_warp_photo_bwd_pose_final runs unchanged on the first region, so g_T has the bits of e2e_warp_photo_bwd_pose.
 //
 // The operator forms.  e2e_project3d_bwd_k (the K half of Project3D's adjoint, next to e2e_project3d_bwd_t) and e2e_backproject_bwd_invk
@@ -198,7 +199,7 @@ extern "C" {
 
 int64_t e2e_warp_photo_bwd_intrinsics_workspace_bytes(int B, int H, int W) {
     if (B <= 0 || H <= 0 || W <= 0) return 0;
-    return (int64_t)B * tile_count(H, W) * IN_NALL * 8;
+    return warp_photo_bwd_workspace(0, WP_SUMS_INTRINSICS, 1, B, H, W).words * 8;
 }
 
 int e2e_warp_photo_bwd_intrinsics(const float* depth_tgt, const float* src, e2e_strides src_strides, const float* tgt, e2e_strides tgt_strides,
@@ -206,26 +207,9 @@ int e2e_warp_photo_bwd_intrinsics(const float* depth_tgt, const float* src, e2e_
                                   int padding_mode, int reg_kind, const float* reg_init_tgt, const float* reg_init_src, const float* depth_src,
                                   const float* g_loss, float* g_depth_tgt, float* g_depth_src, float* g_T, float* g_K, float* g_inv_K,
                                   void* workspace, int B, int H, int W, void* stream) {
-    if (const int rc = warp_photo_check_args("e2e_warp_photo_bwd_intrinsics", B, H, W,
-                                             depth_tgt && src && tgt && K && inv_K && T && synth && valid && g_loss && g_depth_tgt && g_K &&
-                                                 g_inv_K && workspace,
-                                             padding_mode, reg_kind, reg_init_tgt && reg_init_src && depth_src && g_depth_src))
-        return rc;
-    E2E_REQUIRE(B <= 65535, E2E_ERR_ARG, "e2e_warp_photo_bwd_intrinsics: B=%d exceeds the grid", B);
-    hipStream_t st = (hipStream_t)stream;
-    const int tiles = (int)tile_count(H, W);
-    double* partials = (double*)workspace;
-    double* q_partials = partials + (int64_t)B * tiles * WP_NSUM;
-    warp_photo_bwd_intrinsics_launch(depth_tgt, src, src_strides, tgt, tgt_strides, K, inv_K, T, synth, valid, use_mask, padding_mode, reg_kind,
-                                     reg_init_tgt, reg_init_src, depth_src, g_loss, g_depth_tgt, g_depth_src, partials, q_partials, B, H, W, st);
-    E2E_LAUNCH_CHECK("e2e_warp_photo_bwd_intrinsics");
-    if (g_T) {
-        warp_photo_pose_final_launch(partials, tiles, K, g_T, 1, B, st);
-        E2E_LAUNCH_CHECK("e2e_warp_photo_bwd_intrinsics(pose)");
-    }
-    warp_photo_intrinsics_final_launch(partials, q_partials, tiles, K, T, g_K, g_inv_K, 1, B, st);
-    E2E_LAUNCH_CHECK("e2e_warp_photo_bwd_intrinsics(final)");
-    return E2E_OK;
+    const WarpPhotoBwdArgs a{depth_tgt, src, src_strides, tgt, tgt_strides, K, inv_K, T, synth, valid, use_mask, padding_mode, reg_kind,
+                             reg_init_tgt, reg_init_src, depth_src, g_loss, g_depth_tgt, g_depth_src, B, H, W};
+    return warp_photo_bwd_run("e2e_warp_photo_bwd_intrinsics", WP_SUMS_INTRINSICS, a, g_T, g_K, g_inv_K, workspace, (hipStream_t)stream);
 }
 
 int64_t e2e_project3d_bwd_k_workspace_bytes(int B) { return B > 0 ? (int64_t)B * OP_MAX_PARTS * WP_NSUM * 8 : 0; }

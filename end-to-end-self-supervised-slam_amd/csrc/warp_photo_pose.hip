@@ -1,8 +1,9 @@
 // warp_photo_pose.hip -- the fused warp-photometric backward with the gradient with respect to the relative pose T (DATA.use_gt_pose: False:
 // the photometric loss is differentiated through the pose, train_depth.py:381-382, :395).  The per-pixel work is k_warp_photo_bwd<pad, POSE>
 // of warp_photo.hip, which already forms the adjoint (gc0, gc1, gc2) of the projected point on its way to g_depth_tgt; with POSE it also
-// leaves Pbar = sum gc X^T | sum gc per workgroup as 12 float64 sums.  Here: the entry points, and the second stage that folds the
-// workgroups' sums per batch element in a fixed order and applies K^T, as k_project3d_bwd_T_final (pose_grad.hip) does for the operator.
+// leaves Pbar = sum gc X^T | sum gc per workgroup as 12 float64 sums.  Here: the entry point, which fills the operand struct and calls the
+// pair's one backward path (warp_photo_bwd_run, warp_photo.hip), and the second stage that folds the workgroups' sums per batch element in
+// a fixed order and applies K^T, as k_project3d_bwd_T_final (pose_grad.hip) does for the operator.
 // The three-frame window, with or without the geometric-consistency term (k_warp_photo_window_bwd<pad, POSE, GEO> of warp_photo_window.hip),
 // runs the same second stage with one grid row per source.
 // No atomics anywhere: bitwise reproducible run to run.
@@ -36,7 +37,7 @@ extern "C" {
 
 int64_t e2e_warp_photo_bwd_pose_workspace_bytes(int B, int H, int W) {
     if (B <= 0 || H <= 0 || W <= 0) return 0;
-    return (int64_t)B * tile_count(H, W) * WP_NSUM * 8;
+    return warp_photo_bwd_workspace(0, WP_SUMS_POSE, 1, B, H, W).words * 8;
 }
 
 int e2e_warp_photo_bwd_pose(const float* depth_tgt, const float* src, e2e_strides src_strides, const float* tgt, e2e_strides tgt_strides,
@@ -44,18 +45,9 @@ int e2e_warp_photo_bwd_pose(const float* depth_tgt, const float* src, e2e_stride
                             int padding_mode, int reg_kind, const float* reg_init_tgt, const float* reg_init_src, const float* depth_src,
                             const float* g_loss, float* g_depth_tgt, float* g_depth_src, float* g_T, void* workspace, int B, int H, int W,
                             void* stream) {
-    if (const int rc = warp_photo_check_args("e2e_warp_photo_bwd_pose", B, H, W,
-                                             depth_tgt && src && tgt && K && inv_K && T && synth && valid && g_loss && g_depth_tgt && g_T && workspace,
-                                             padding_mode, reg_kind, reg_init_tgt && reg_init_src && depth_src && g_depth_src))
-        return rc;
-    E2E_REQUIRE(B <= 65535, E2E_ERR_ARG, "e2e_warp_photo_bwd_pose: B=%d exceeds the grid", B);
-    hipStream_t st = (hipStream_t)stream;
-    warp_photo_bwd_pose_launch(depth_tgt, src, src_strides, tgt, tgt_strides, K, inv_K, T, synth, valid, use_mask, padding_mode, reg_kind,
-                               reg_init_tgt, reg_init_src, depth_src, g_loss, g_depth_tgt, g_depth_src, (double*)workspace, B, H, W, st);
-    E2E_LAUNCH_CHECK("e2e_warp_photo_bwd_pose");
-    warp_photo_pose_final_launch((const double*)workspace, (int)tile_count(H, W), K, g_T, 1, B, st);
-    E2E_LAUNCH_CHECK("e2e_warp_photo_bwd_pose(final)");
-    return E2E_OK;
+    const WarpPhotoBwdArgs a{depth_tgt, src, src_strides, tgt, tgt_strides, K, inv_K, T, synth, valid, use_mask, padding_mode, reg_kind,
+                             reg_init_tgt, reg_init_src, depth_src, g_loss, g_depth_tgt, g_depth_src, B, H, W};
+    return warp_photo_bwd_run("e2e_warp_photo_bwd_pose", WP_SUMS_POSE, a, g_T, nullptr, nullptr, workspace, (hipStream_t)stream);
 }
 
 }  // extern "C"

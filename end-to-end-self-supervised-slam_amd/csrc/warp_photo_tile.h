@@ -1,6 +1,7 @@
 // warp_photo_tile.h -- what the 32x8 warp-photometric family shares: the pair (warp_photo.hip), its pose gradient (warp_photo_pose.hip) and
 // the three-frame window with and without the geometric-consistency term (warp_photo_window.hip: one kernel template pair for both).  Tile
-// constants, the SSIM device functions, the three-channel sample, the pair's host argument checks, and the host launchers of the two second
+// constants, the SSIM device functions, the three-channel sample, the pair's host argument checks, the layout of the backward workspaces,
+// the one host path of the pair's three backwards (warp_photo_bwd_run) with its operand struct, and the host launchers of the second
 // stages, each of which lives in one file and serves the others.
 // The device functions were MOVED here as they stood: a function that already exists compiles to the same instructions wherever it is
 // defined (profiles/warp_family_refactor.txt: 0 differing lines in every tile kernel).  Arithmetic that is written out in a kernel is not
@@ -93,7 +94,7 @@ __device__ __forceinline__ void sample3(const float* __restrict__ base, const e2
 static inline dim3 tile_grid(int B, int H, int W) { return dim3(e2e_ceil_div(W, TW), e2e_ceil_div(H, TH), B); }
 static inline int64_t tile_count(int H, int W) { return (int64_t)e2e_ceil_div(W, TW) * e2e_ceil_div(H, TH); }     // tiles per batch element
 
-// the argument checks of e2e_warp_photo_fwd / _bwd / _bwd_pose (`name` = the entry point; the messages are part of the interface)
+// the argument checks of e2e_warp_photo_fwd and of the three backwards (`name` = the entry point; the messages are part of the interface)
 static int warp_photo_check_args(const char* name, int B, int H, int W, bool pointers, int padding_mode, int reg_kind, bool reg_buffers) {
     E2E_REQUIRE(B > 0 && H > 1 && W > 1 && (int64_t)B * H * W < (1ll << 31), E2E_ERR_ARG, "%s: bad dims B=%d H=%d W=%d", name, B, H, W);
     E2E_REQUIRE(pointers, E2E_ERR_ARG, "%s: null pointer", name);
@@ -104,23 +105,47 @@ static int warp_photo_check_args(const char* name, int B, int H, int W, bool poi
     return E2E_OK;
 }
 
+// E2E_LAUNCH_CHECK for a host path that serves several entry points: `stage` = "" or the "(stage)" that follows the entry point's name
+static inline int warp_photo_launch_status(const char* name, const char* stage) {
+    char what[96];                                     // the longest entry-point name with its stage has 49 characters
+    snprintf(what, sizeof what, "%s%s", name, stage);
+    E2E_LAUNCH_CHECK(what);
+    return E2E_OK;
+}
+
+// The backward workspace of the whole family, for the *_workspace_bytes queries and the host paths alike, in 8-byte words: `fixed` words of
+// fixed-point scratch (the geometric forms; 0 elsewhere), then the float64 pose sums [S][B][tiles][12], then, with WP_SUMS_INTRINSICS only,
+// the float64 sums Q [S][B][tiles][9] (k_warp_photo_window_bwd finds this region by the same expression).  S = 1 for the pair.
+struct WarpPhotoBwdWorkspace {
+    int64_t partials, q_partials, words;               // where the two regions of sums begin, and the size
+};
+static inline WarpPhotoBwdWorkspace warp_photo_bwd_workspace(int64_t fixed, int sums, int S, int B, int H, int W) {
+    const int64_t n = (int64_t)S * B * tile_count(H, W);
+    return {fixed, fixed + n * WP_NSUM, fixed + n * WP_NSUM + (sums == WP_SUMS_INTRINSICS ? n * WP_NQ : 0)};
+}
+
+// what e2e_warp_photo_bwd, _bwd_pose and _bwd_intrinsics share, under the parameter names of include/e2eslam.h (host only: never a kernel
+// argument -- that would change every kernarg layout, profiles/lossgrad_tile_refactor.txt)
+struct WarpPhotoBwdArgs {
+    const float *depth_tgt, *src;
+    e2e_strides src_strides;
+    const float* tgt;
+    e2e_strides tgt_strides;
+    const float *K, *inv_K, *T, *synth, *valid;
+    int use_mask, padding_mode, reg_kind;
+    const float *reg_init_tgt, *reg_init_src, *depth_src, *g_loss;
+    float *g_depth_tgt, *g_depth_src;
+    int B, H, W;
+};
+
+// The pair's backward, whole (warp_photo.hip, where k_warp_photo_bwd lives): the checks of the mode under the entry point's `name`, then the
+// tile launch; WP_SUMS_POSE (g_T, workspace required) leaves partials[(b * tiles + tile) * 12 + r * 4 + j] and runs the pose final;
+// WP_SUMS_INTRINSICS (g_K, g_inv_K, workspace required) adds a pass that stores only q_partials[(b * tiles + tile) * 9 + r * 3 + j] = sum gc_r d pix_j.
+int warp_photo_bwd_run(const char* name, int sums, const WarpPhotoBwdArgs& a, float* g_T, float* g_K, float* g_inv_K, void* workspace,
+                       hipStream_t stream);
+
 // k_reduce_partials (warp_photo.hip): out[s] = scale * the fixed-order float64 sum of partials[s * nblk .. (s + 1) * nblk), s < nsets
 void warp_photo_reduce_launch(const float* partials, int nblk, int nsets, float scale, float* out, hipStream_t stream);
-
-// k_warp_photo_bwd<pad, WP_SUMS_POSE> (warp_photo.hip): the launch of e2e_warp_photo_bwd plus 12 float64 sums per workgroup in
-// partials[(b * tiles + tile) * 12 + r * 4 + j].  Arguments are not checked here.
-void warp_photo_bwd_pose_launch(const float* depth_tgt, const float* src, e2e_strides ss, const float* tgt, e2e_strides ts, const float* K,
-                                const float* inv_K, const float* T, const float* synth, const float* valid, int use_mask, int padding_mode,
-                                int reg_kind, const float* reg_init_tgt, const float* reg_init_src, const float* depth_src, const float* g_loss,
-                                float* g_depth_tgt, float* g_depth_src, double* partials, int B, int H, int W, hipStream_t stream);
-
-// warp_photo_bwd_pose_launch, then k_warp_photo_bwd<pad, WP_SUMS_INTRINSICS> (warp_photo.hip): a second pass over the tiles that stores
-// only 9 float64 sums per workgroup, q_partials[(b * tiles + tile) * 9 + r * 3 + j] = sum gc_r d pix_j.  Arguments are not checked here.
-void warp_photo_bwd_intrinsics_launch(const float* depth_tgt, const float* src, e2e_strides ss, const float* tgt, e2e_strides ts, const float* K,
-                                      const float* inv_K, const float* T, const float* synth, const float* valid, int use_mask, int padding_mode,
-                                      int reg_kind, const float* reg_init_tgt, const float* reg_init_src, const float* depth_src,
-                                      const float* g_loss, float* g_depth_tgt, float* g_depth_src, double* partials, double* q_partials, int B,
-                                      int H, int W, hipStream_t stream);
 
 // k_warp_photo_bwd_intrinsics_final (warp_photo_intrinsics.hip): g_K[b] and g_inv_K[b] from the fixed-order sums over the tiles of
 // partials[((s * B + b) * tiles + tile) * 12 ..] and q_partials[((s * B + b) * tiles + tile) * 9 ..], the sources added in the order 0, 1;

@@ -5,7 +5,8 @@
 // e2e_warp_photo_geo_* (GEO = true): the text is the geometric kernel's, and the compile-time constant GEO deletes the geometric pieces
 // from the window's instantiation (profiles/warp_window_geo_merge.txt).  One tile launch forward (+ the fixed-order reduction of the workgroups'
 // partial sums), one tile launch backward (+ a final kernel per source and batch element when the gradient with respect to the poses is
-// asked for).
+// asked for).  On the host the six entry points fill one operand struct and share ONE forward path (window_fwd<GEO>) and ONE backward path
+// (window_bwd<GEO>, without or with the intrinsics); the workspace layouts are stated once, for the size queries and the paths alike.
 //
 // Semantics of the window.  For source s with its validity mask m_s (1 everywhere when use_mask == 0):
 //     R_s = photometric(synth_s m_s, tgt m_s)                    the reprojection map
@@ -511,41 +512,144 @@ __global__ void k_geo_fixed48_to_float(const long long* __restrict__ fx, float* 
     }
 }
 
-// what the four entry points refuse before they look at their own pointers (`name` = the entry point, geo = its geometric form; the
-// messages are part of the interface)
-int check_window(const char* name, bool geo, int S, int B, int H, int W, int padding_mode, int terms, int geo_min_valid) {
-    E2E_REQUIRE(S >= 1 && S <= MAX_S, E2E_ERR_ARG, "%s: S=%d source frames (1 or 2)", name, S);
-    E2E_REQUIRE(B > 0 && B <= 65535 && H > 1 && W > 1 && (int64_t)B * H * W < (1ll << 31), E2E_ERR_ARG, "%s: bad dims B=%d H=%d W=%d", name,
-                B, H, W);
-    E2E_REQUIRE(padding_mode == E2E_PADDING_BORDER || padding_mode == E2E_PADDING_ZEROS, E2E_ERR_ARG,
-                "%s: padding_mode %d not supported (zeros|border)", name, padding_mode);
-    E2E_REQUIRE((terms & ~(E2E_TERM_AUTO_MASKING | E2E_TERM_MIN_REPROJECTION)) == 0, E2E_ERR_ARG,
-                "%s: terms %d (E2E_TERM_AUTO_MASKING | E2E_TERM_MIN_REPROJECTION; the geometric term %s)", name, terms,
+// ---- host: what the six entry points share, under the parameter names of include/e2eslam.h; the plain window leaves the geometric operands
+// NULL / 0.  Never a kernel argument (that would change every kernarg layout, profiles/lossgrad_tile_refactor.txt).
+struct WindowArgs {
+    const float *depth_tgt, *depth_src0, *depth_src1, *src0, *src1;
+    e2e_strides src_strides;
+    const float* tgt;
+    e2e_strides tgt_strides;
+    const float *K, *inv_K, *T;
+    int use_mask, padding_mode, terms, geo_min_valid;
+    int S, B, H, W;
+};
+// the rest of each direction's list; an entry point sets by name what it has, the others stay NULL (the forward writes what the backward reads)
+struct WindowFwdArgs : WindowArgs {
+    const float* tie_noise;
+    float *synth, *valid, *pmap, *loss_out, *workspace;
+    int *select, *geo_count;
+};
+struct WindowBwdArgs : WindowArgs {
+    const float *synth, *valid, *g_loss;
+    const int *select, *geo_count;
+    float *g_depth_tgt, *g_depth_src, *g_T, *g_K, *g_inv_K;
+    void* workspace;
+};
+
+// what every entry point refuses before it looks at its own pointers (`name` = the entry point, geo = its geometric form; the messages are
+// part of the interface)
+int check_window(const char* name, bool geo, const WindowArgs& a) {
+    E2E_REQUIRE(a.S >= 1 && a.S <= MAX_S, E2E_ERR_ARG, "%s: S=%d source frames (1 or 2)", name, a.S);
+    E2E_REQUIRE(a.B > 0 && a.B <= 65535 && a.H > 1 && a.W > 1 && (int64_t)a.B * a.H * a.W < (1ll << 31), E2E_ERR_ARG,
+                "%s: bad dims B=%d H=%d W=%d", name, a.B, a.H, a.W);
+    E2E_REQUIRE(a.padding_mode == E2E_PADDING_BORDER || a.padding_mode == E2E_PADDING_ZEROS, E2E_ERR_ARG,
+                "%s: padding_mode %d not supported (zeros|border)", name, a.padding_mode);
+    E2E_REQUIRE((a.terms & ~(E2E_TERM_AUTO_MASKING | E2E_TERM_MIN_REPROJECTION)) == 0, E2E_ERR_ARG,
+                "%s: terms %d (E2E_TERM_AUTO_MASKING | E2E_TERM_MIN_REPROJECTION; the geometric term %s)", name, a.terms,
                 geo ? "is always on here" : "stays on the operators");
-    E2E_REQUIRE(!geo || geo_min_valid >= 0, E2E_ERR_ARG, "%s: geo_min_valid %d is negative", name, geo_min_valid);
+    E2E_REQUIRE(!geo || a.geo_min_valid >= 0, E2E_ERR_ARG, "%s: geo_min_valid %d is negative", name, a.geo_min_valid);
     return E2E_OK;
 }
 
-int64_t fixed_words(int S, int B, int H, int W) { return (int64_t)S * B * H * W + S; }          // the sums and one poison word per source
+bool bad_query(int S, int B, int H, int W) { return S < 1 || S > MAX_S || B <= 0 || H <= 0 || W <= 0; }     // every size query answers 0
 
-// the PAD and the PAD x POSE selection of the tile launches, once per direction; `a` is the kernel's argument list
-template <bool GEO, class... A>
-void launch_fwd(int padding_mode, dim3 g, hipStream_t st, A... a) {
-    if (padding_mode == E2E_PADDING_BORDER) hipLaunchKernelGGL((k_warp_photo_window_fwd<E2E_PAD_BORDER, GEO>), g, dim3(TW, TH), 0, st, a...);
-    else hipLaunchKernelGGL((k_warp_photo_window_fwd<E2E_PAD_ZEROS, GEO>), g, dim3(TW, TH), 0, st, a...);
+// The forward workspace, for the two queries and the forward path alike, in floats: the loss partials [nblk], then with the geometric term the
+// diff sums [S][nblk] (floats) and the validity counts [S][nblk] (ints)
+struct FwdWorkspace {
+    int64_t nblk, gpart, cpart, floats;
+};
+FwdWorkspace fwd_workspace(bool geo, int S, int B, int H, int W) {
+    const int64_t nblk = (int64_t)B * tile_count(H, W);
+    return {nblk, nblk, nblk * (1 + S), geo ? nblk * (1 + 2 * S) : nblk};
 }
 
-template <bool GEO, class... A>
-void launch_bwd(int padding_mode, int sums, dim3 g, hipStream_t st, A... a) {
-    if (padding_mode == E2E_PADDING_BORDER) {
-        if (sums == WP_SUMS_INTRINSICS) hipLaunchKernelGGL((k_warp_photo_window_bwd<E2E_PAD_BORDER, WP_SUMS_INTRINSICS, GEO>), g, dim3(TW, TH), 0, st, a...);
-        else if (sums == WP_SUMS_POSE) hipLaunchKernelGGL((k_warp_photo_window_bwd<E2E_PAD_BORDER, WP_SUMS_POSE, GEO>), g, dim3(TW, TH), 0, st, a...);
-        else hipLaunchKernelGGL((k_warp_photo_window_bwd<E2E_PAD_BORDER, WP_SUMS_NONE, GEO>), g, dim3(TW, TH), 0, st, a...);
-    } else {
-        if (sums == WP_SUMS_INTRINSICS) hipLaunchKernelGGL((k_warp_photo_window_bwd<E2E_PAD_ZEROS, WP_SUMS_INTRINSICS, GEO>), g, dim3(TW, TH), 0, st, a...);
-        else if (sums == WP_SUMS_POSE) hipLaunchKernelGGL((k_warp_photo_window_bwd<E2E_PAD_ZEROS, WP_SUMS_POSE, GEO>), g, dim3(TW, TH), 0, st, a...);
-        else hipLaunchKernelGGL((k_warp_photo_window_bwd<E2E_PAD_ZEROS, WP_SUMS_NONE, GEO>), g, dim3(TW, TH), 0, st, a...);
+// the backward workspace: with the geometric term the fixed-point sums and one poison word per source come first, zeroed by the call
+WarpPhotoBwdWorkspace bwd_workspace(bool geo, bool intrinsics, int S, int B, int H, int W) {
+    return warp_photo_bwd_workspace(geo ? (int64_t)S * B * H * W + S : 0, intrinsics ? WP_SUMS_INTRINSICS : WP_SUMS_POSE, S, B, H, W);
+}
+
+// the PAD x SUMS instantiation of the backward tile kernel
+template <bool GEO>
+auto bwd_kernel(bool border, int sums) {
+    if (border) {
+        if (sums == WP_SUMS_INTRINSICS) return k_warp_photo_window_bwd<E2E_PAD_BORDER, WP_SUMS_INTRINSICS, GEO>;
+        if (sums == WP_SUMS_POSE) return k_warp_photo_window_bwd<E2E_PAD_BORDER, WP_SUMS_POSE, GEO>;
+        return k_warp_photo_window_bwd<E2E_PAD_BORDER, WP_SUMS_NONE, GEO>;
     }
+    if (sums == WP_SUMS_INTRINSICS) return k_warp_photo_window_bwd<E2E_PAD_ZEROS, WP_SUMS_INTRINSICS, GEO>;
+    if (sums == WP_SUMS_POSE) return k_warp_photo_window_bwd<E2E_PAD_ZEROS, WP_SUMS_POSE, GEO>;
+    return k_warp_photo_window_bwd<E2E_PAD_ZEROS, WP_SUMS_NONE, GEO>;
+}
+
+// the forward of the window and of its geometric form: the tile launch, the reduction of the loss partials, with GEO the geometric term's final
+template <bool GEO>
+int window_fwd(const char* name, const WindowFwdArgs& a, hipStream_t st) {
+    if (const int rc = check_window(name, GEO, a)) return rc;
+    E2E_REQUIRE(a.depth_tgt && a.src0 && (a.src1 || a.S == 1) && a.tgt && a.K && a.inv_K && a.T && a.synth && a.valid && a.select && a.loss_out &&
+                    a.workspace && (!GEO || (a.depth_src0 && (a.depth_src1 || a.S == 1) && a.geo_count)),
+                E2E_ERR_ARG, "%s: null pointer", name);
+    const FwdWorkspace ws = fwd_workspace(GEO, a.S, a.B, a.H, a.W);
+    float* gpart = GEO ? a.workspace + ws.gpart : nullptr;
+    int* cpart = GEO ? (int*)(a.workspace + ws.cpart) : nullptr;
+    const auto kernel = a.padding_mode == E2E_PADDING_BORDER ? k_warp_photo_window_fwd<E2E_PAD_BORDER, GEO> : k_warp_photo_window_fwd<E2E_PAD_ZEROS, GEO>;
+    hipLaunchKernelGGL(kernel, tile_grid(a.B, a.H, a.W), dim3(TW, TH), 0, st, a.depth_tgt, a.depth_src0, a.depth_src1, a.src0, a.src1, a.src_strides,
+                       a.tgt, a.tgt_strides, a.K, a.inv_K, a.T, a.tie_noise, a.synth, a.valid, a.select, a.pmap, a.use_mask, a.terms, a.workspace,
+                       gpart, cpart, a.S, a.B, a.H, a.W);
+    if (const int rc = warp_photo_launch_status(name, "")) return rc;
+    const float scale = (float)(1.0 / ((double)a.B * a.H * a.W));
+    warp_photo_reduce_launch(a.workspace, (int)ws.nblk, 1, scale, a.loss_out, st);
+    if (const int rc = warp_photo_launch_status(name, "(reduce)")) return rc;
+    if constexpr (GEO) {
+        hipLaunchKernelGGL(k_geo_final, dim3(a.S), dim3(64), 0, st, gpart, cpart, (int)ws.nblk, a.geo_min_valid, a.geo_count, a.loss_out);
+        if (const int rc = warp_photo_launch_status(name, "(geometric)")) return rc;
+    }
+    return E2E_OK;
+}
+
+// The backward of the window and of its geometric form, without or with the gradient with respect to the intrinsics.  With it: the tile launch
+// with the pose sums (the existing instantiation: the depth gradients and Pbar keep their bits), the tile launch in its third mode (the Q pass:
+// 9 sums per workgroup and source into the region behind), then k_warp_photo_bwd_intrinsics_final; k_warp_photo_bwd_pose_final runs unchanged
+// on the pose sums whenever g_T is asked for.
+template <bool GEO>
+int window_bwd(const char* name, bool intrinsics, const WindowBwdArgs& a, hipStream_t st) {
+    if (const int rc = check_window(name, GEO, a)) return rc;
+    // line 1: what all four need; line 2: the two geometric forms; line 3: the two intrinsics forms.  Those three always require workspace, so
+    // only e2e_warp_photo_window_bwd can reach the second message.
+    E2E_REQUIRE(a.depth_tgt && a.src0 && (a.src1 || a.S == 1) && a.tgt && a.K && a.inv_K && a.T && a.synth && a.valid && a.select && a.g_loss && a.g_depth_tgt &&
+                    (!GEO || (a.depth_src0 && (a.depth_src1 || a.S == 1) && a.geo_count && a.g_depth_src && a.workspace)) &&
+                    (!intrinsics || (a.g_K && a.g_inv_K && a.workspace)),
+                E2E_ERR_ARG, "%s: null pointer", name);
+    E2E_REQUIRE(!a.g_T || a.workspace, E2E_ERR_ARG, "%s: g_T without workspace", name);
+    const WarpPhotoBwdWorkspace ws = bwd_workspace(GEO, intrinsics, a.S, a.B, a.H, a.W);
+    const int tiles = (int)tile_count(a.H, a.W);
+    unsigned long long* fx = GEO ? (unsigned long long*)a.workspace : nullptr;
+    double* partials = (double*)a.workspace + ws.partials;       // written only with the pose sums
+    if constexpr (GEO)
+        E2E_REQUIRE(hipMemsetAsync(fx, 0, (size_t)ws.partials * 8, st) == hipSuccess, E2E_ERR_LAUNCH,
+                    "%s: hipMemsetAsync of the fixed-point scratch failed", name);
+    const auto tile_pass = [&](int sums) {
+        hipLaunchKernelGGL(bwd_kernel<GEO>(a.padding_mode == E2E_PADDING_BORDER, sums), tile_grid(a.B, a.H, a.W), dim3(TW, TH), 0, st, a.depth_tgt,
+                           a.depth_src0, a.depth_src1, a.src0, a.src1, a.src_strides, a.tgt, a.tgt_strides, a.K, a.inv_K, a.T, a.synth, a.valid,
+                           a.select, a.geo_count, a.use_mask, a.terms, a.geo_min_valid, a.g_loss, a.g_depth_tgt, fx, partials, a.S, a.B, a.H, a.W);
+    };
+    tile_pass(a.g_T || intrinsics ? WP_SUMS_POSE : WP_SUMS_NONE);
+    if (intrinsics) tile_pass(WP_SUMS_INTRINSICS);                  // the Q pass, always second
+    if (const int rc = warp_photo_launch_status(name, "")) return rc;
+    if constexpr (GEO) {
+        const int64_t per_source = (int64_t)a.B * a.H * a.W, n = per_source * a.S;
+        hipLaunchKernelGGL(k_geo_fixed48_to_float, dim3((unsigned)((n + 255) / 256 > 4096 ? 4096 : (n + 255) / 256)), dim3(256), 0, st,
+                           (const long long*)fx, a.g_depth_src, per_source, a.S);
+        if (const int rc = warp_photo_launch_status(name, "(depth_src)")) return rc;
+    }
+    if (a.g_T) {
+        warp_photo_pose_final_launch(partials, tiles, a.K, a.g_T, a.S, a.B, st);
+        if (const int rc = warp_photo_launch_status(name, intrinsics ? "(pose)" : "(final)")) return rc;
+    }
+    if (intrinsics) {
+        warp_photo_intrinsics_final_launch(partials, (double*)a.workspace + ws.q_partials, tiles, a.K, a.T, a.g_K, a.g_inv_K, a.S, a.B, st);
+        if (const int rc = warp_photo_launch_status(name, "(final)")) return rc;
+    }
+    return E2E_OK;
 }
 
 }  // namespace
@@ -553,58 +657,33 @@ void launch_bwd(int padding_mode, int sums, dim3 g, hipStream_t st, A... a) {
 extern "C" {
 
 int64_t e2e_warp_photo_window_workspace_floats(int S, int B, int H, int W) {
-    if (S < 1 || S > MAX_S || B <= 0 || H <= 0 || W <= 0) return 0;
-    return (int64_t)B * tile_count(H, W);
+    return bad_query(S, B, H, W) ? 0 : fwd_workspace(false, S, B, H, W).floats;
 }
 
 int e2e_warp_photo_window_fwd(const float* depth_tgt, const float* src0, const float* src1, e2e_strides src_strides, const float* tgt,
                               e2e_strides tgt_strides, const float* K, const float* inv_K, const float* T, const float* tie_noise, float* synth,
                               float* valid, int* select, float* pmap, int use_mask, int padding_mode, int terms, float* loss_out,
                               float* workspace, int S, int B, int H, int W, void* stream) {
-    const int rc = check_window("e2e_warp_photo_window_fwd", false, S, B, H, W, padding_mode, terms, 0);
-    if (rc != E2E_OK) return rc;
-    E2E_REQUIRE(depth_tgt && src0 && (src1 || S == 1) && tgt && K && inv_K && T && synth && valid && select && loss_out && workspace, E2E_ERR_ARG,
-                "e2e_warp_photo_window_fwd: null pointer");
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 g = tile_grid(B, H, W);
-    launch_fwd<false>(padding_mode, g, st, depth_tgt, (const float*)nullptr, (const float*)nullptr, src0, src1, src_strides, tgt, tgt_strides, K,
-                      inv_K, T, tie_noise, synth, valid, select, pmap, use_mask, terms, workspace, (float*)nullptr, (int*)nullptr, S, B, H, W);
-    E2E_LAUNCH_CHECK("e2e_warp_photo_window_fwd");
-    const float scale = (float)(1.0 / ((double)B * H * W));
-    warp_photo_reduce_launch(workspace, (int)(g.x * g.y * g.z), 1, scale, loss_out, st);
-    E2E_LAUNCH_CHECK("e2e_warp_photo_window_fwd(reduce)");
-    return E2E_OK;
+    WindowFwdArgs a{{depth_tgt, nullptr, nullptr, src0, src1, src_strides, tgt, tgt_strides, K, inv_K, T, use_mask, padding_mode, terms, 0, S, B, H, W}};
+    a.tie_noise = tie_noise; a.synth = synth; a.valid = valid; a.select = select; a.pmap = pmap; a.loss_out = loss_out; a.workspace = workspace;
+    return window_fwd<false>("e2e_warp_photo_window_fwd", a, (hipStream_t)stream);
 }
 
 int64_t e2e_warp_photo_window_bwd_workspace_bytes(int S, int B, int H, int W) {
-    if (S < 1 || S > MAX_S || B <= 0 || H <= 0 || W <= 0) return 0;
-    return (int64_t)S * B * tile_count(H, W) * WP_NSUM * 8;
+    return bad_query(S, B, H, W) ? 0 : bwd_workspace(false, false, S, B, H, W).words * 8;
 }
 
 int e2e_warp_photo_window_bwd(const float* depth_tgt, const float* src0, const float* src1, e2e_strides src_strides, const float* tgt,
                               e2e_strides tgt_strides, const float* K, const float* inv_K, const float* T, const float* synth,
                               const float* valid, const int* select, int use_mask, int padding_mode, int terms, const float* g_loss,
                               float* g_depth_tgt, float* g_T, void* workspace, int S, int B, int H, int W, void* stream) {
-    const int rc = check_window("e2e_warp_photo_window_bwd", false, S, B, H, W, padding_mode, terms, 0);
-    if (rc != E2E_OK) return rc;
-    E2E_REQUIRE(depth_tgt && src0 && (src1 || S == 1) && tgt && K && inv_K && T && synth && valid && select && g_loss && g_depth_tgt, E2E_ERR_ARG,
-                "e2e_warp_photo_window_bwd: null pointer");
-    E2E_REQUIRE(!g_T || workspace, E2E_ERR_ARG, "e2e_warp_photo_window_bwd: g_T without workspace");
-    hipStream_t st = (hipStream_t)stream;
-    launch_bwd<false>(padding_mode, g_T ? WP_SUMS_POSE : WP_SUMS_NONE, tile_grid(B, H, W), st, depth_tgt, (const float*)nullptr, (const float*)nullptr, src0, src1,
-                      src_strides, tgt, tgt_strides, K, inv_K, T, synth, valid, select, (const int*)nullptr, use_mask, terms, 0, g_loss,
-                      g_depth_tgt, (unsigned long long*)nullptr, (double*)workspace, S, B, H, W);
-    E2E_LAUNCH_CHECK("e2e_warp_photo_window_bwd");
-    if (g_T) {
-        warp_photo_pose_final_launch((const double*)workspace, (int)tile_count(H, W), K, g_T, S, B, st);
-        E2E_LAUNCH_CHECK("e2e_warp_photo_window_bwd(final)");
-    }
-    return E2E_OK;
+    WindowBwdArgs a{{depth_tgt, nullptr, nullptr, src0, src1, src_strides, tgt, tgt_strides, K, inv_K, T, use_mask, padding_mode, terms, 0, S, B, H, W}};
+    a.synth = synth; a.valid = valid; a.select = select; a.g_loss = g_loss; a.g_depth_tgt = g_depth_tgt; a.g_T = g_T; a.workspace = workspace;
+    return window_bwd<false>("e2e_warp_photo_window_bwd", false, a, (hipStream_t)stream);
 }
 
 int64_t e2e_warp_photo_geo_workspace_floats(int S, int B, int H, int W) {
-    if (S < 1 || S > MAX_S || B <= 0 || H <= 0 || W <= 0) return 0;
-    return (int64_t)B * tile_count(H, W) * (1 + 2 * S);
+    return bad_query(S, B, H, W) ? 0 : fwd_workspace(true, S, B, H, W).floats;
 }
 
 int e2e_warp_photo_geo_fwd(const float* depth_tgt, const float* depth_src0, const float* depth_src1, const float* src0, const float* src1,
@@ -612,30 +691,15 @@ int e2e_warp_photo_geo_fwd(const float* depth_tgt, const float* depth_src0, cons
                            const float* tie_noise, float* synth, float* valid, int* select, float* pmap, int* geo_count, int use_mask,
                            int padding_mode, int terms, int geo_min_valid, float* loss_out, float* workspace, int S, int B, int H, int W,
                            void* stream) {
-    const int rc = check_window("e2e_warp_photo_geo_fwd", true, S, B, H, W, padding_mode, terms, geo_min_valid);
-    if (rc != E2E_OK) return rc;
-    E2E_REQUIRE(depth_tgt && depth_src0 && (depth_src1 || S == 1) && src0 && (src1 || S == 1) && tgt && K && inv_K && T && synth && valid &&
-                    select && geo_count && loss_out && workspace,
-                E2E_ERR_ARG, "e2e_warp_photo_geo_fwd: null pointer");
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 g = tile_grid(B, H, W);
-    const int nblk = (int)(g.x * g.y * g.z);
-    float* gpart = workspace + nblk;                     // [S][nblk] floats, then [S][nblk] ints
-    int* cpart = (int*)(workspace + (int64_t)nblk * (1 + S));
-    launch_fwd<true>(padding_mode, g, st, depth_tgt, depth_src0, depth_src1, src0, src1, src_strides, tgt, tgt_strides, K, inv_K, T, tie_noise,
-                     synth, valid, select, pmap, use_mask, terms, workspace, gpart, cpart, S, B, H, W);
-    E2E_LAUNCH_CHECK("e2e_warp_photo_geo_fwd");
-    const float scale = (float)(1.0 / ((double)B * H * W));
-    warp_photo_reduce_launch(workspace, nblk, 1, scale, loss_out, st);
-    E2E_LAUNCH_CHECK("e2e_warp_photo_geo_fwd(reduce)");
-    hipLaunchKernelGGL(k_geo_final, dim3(S), dim3(64), 0, st, gpart, cpart, nblk, geo_min_valid, geo_count, loss_out);
-    E2E_LAUNCH_CHECK("e2e_warp_photo_geo_fwd(geometric)");
-    return E2E_OK;
+    WindowFwdArgs a{{depth_tgt, depth_src0, depth_src1, src0, src1, src_strides, tgt, tgt_strides, K, inv_K, T, use_mask, padding_mode, terms,
+                      geo_min_valid, S, B, H, W}};
+    a.tie_noise = tie_noise; a.synth = synth; a.valid = valid; a.select = select; a.pmap = pmap; a.loss_out = loss_out; a.workspace = workspace;
+    a.geo_count = geo_count;
+    return window_fwd<true>("e2e_warp_photo_geo_fwd", a, (hipStream_t)stream);
 }
 
 int64_t e2e_warp_photo_geo_bwd_workspace_bytes(int S, int B, int H, int W) {
-    if (S < 1 || S > MAX_S || B <= 0 || H <= 0 || W <= 0) return 0;
-    return (fixed_words(S, B, H, W) + (int64_t)S * B * tile_count(H, W) * WP_NSUM) * 8;
+    return bad_query(S, B, H, W) ? 0 : bwd_workspace(true, false, S, B, H, W).words * 8;
 }
 
 int e2e_warp_photo_geo_bwd(const float* depth_tgt, const float* depth_src0, const float* depth_src1, const float* src0, const float* src1,
@@ -643,38 +707,15 @@ int e2e_warp_photo_geo_bwd(const float* depth_tgt, const float* depth_src0, cons
                            const float* synth, const float* valid, const int* select, const int* geo_count, int use_mask, int padding_mode,
                            int terms, int geo_min_valid, const float* g_loss, float* g_depth_tgt, float* g_depth_src, float* g_T,
                            void* workspace, int S, int B, int H, int W, void* stream) {
-    const int rc = check_window("e2e_warp_photo_geo_bwd", true, S, B, H, W, padding_mode, terms, geo_min_valid);
-    if (rc != E2E_OK) return rc;
-    E2E_REQUIRE(depth_tgt && depth_src0 && (depth_src1 || S == 1) && src0 && (src1 || S == 1) && tgt && K && inv_K && T && synth && valid &&
-                    select && geo_count && g_loss && g_depth_tgt && g_depth_src && workspace,
-                E2E_ERR_ARG, "e2e_warp_photo_geo_bwd: null pointer");
-    hipStream_t st = (hipStream_t)stream;
-    const int64_t words = fixed_words(S, B, H, W);
-    unsigned long long* fx = (unsigned long long*)workspace;
-    double* partials = (double*)workspace + words;       // written only when g_T is asked for
-    E2E_REQUIRE(hipMemsetAsync(fx, 0, (size_t)words * 8, st) == hipSuccess, E2E_ERR_LAUNCH,
-                "e2e_warp_photo_geo_bwd: hipMemsetAsync of the fixed-point scratch failed");
-    launch_bwd<true>(padding_mode, g_T ? WP_SUMS_POSE : WP_SUMS_NONE, tile_grid(B, H, W), st, depth_tgt, depth_src0, depth_src1, src0, src1, src_strides, tgt,
-                     tgt_strides, K, inv_K, T, synth, valid, select, geo_count, use_mask, terms, geo_min_valid, g_loss, g_depth_tgt, fx, partials,
-                     S, B, H, W);
-    E2E_LAUNCH_CHECK("e2e_warp_photo_geo_bwd");
-    const int64_t per_source = (int64_t)B * H * W, n = per_source * S;
-    hipLaunchKernelGGL(k_geo_fixed48_to_float, dim3((unsigned)((n + 255) / 256 > 4096 ? 4096 : (n + 255) / 256)), dim3(256), 0, st,
-                       (const long long*)fx, g_depth_src, per_source, S);
-    E2E_LAUNCH_CHECK("e2e_warp_photo_geo_bwd(depth_src)");
-    if (g_T) {
-        warp_photo_pose_final_launch(partials, (int)tile_count(H, W), K, g_T, S, B, st);
-        E2E_LAUNCH_CHECK("e2e_warp_photo_geo_bwd(final)");
-    }
-    return E2E_OK;
+    WindowBwdArgs a{{depth_tgt, depth_src0, depth_src1, src0, src1, src_strides, tgt, tgt_strides, K, inv_K, T, use_mask, padding_mode, terms,
+                      geo_min_valid, S, B, H, W}};
+    a.synth = synth; a.valid = valid; a.select = select; a.g_loss = g_loss; a.g_depth_tgt = g_depth_tgt; a.g_T = g_T; a.workspace = workspace;
+    a.geo_count = geo_count; a.g_depth_src = g_depth_src;
+    return window_bwd<true>("e2e_warp_photo_geo_bwd", false, a, (hipStream_t)stream);
 }
 
-// ---- the same two backwards with the gradient with respect to the intrinsics: the tile launch with the pose sums (the existing instantiation:
-// the depth gradients and Pbar keep their bits), the tile launch in its third mode (the Q pass: 9 sums per workgroup and source into the second
-// region), then k_warp_photo_bwd_intrinsics_final; k_warp_photo_bwd_pose_final runs unchanged on the first region when g_T is asked for.
 int64_t e2e_warp_photo_window_bwd_intrinsics_workspace_bytes(int S, int B, int H, int W) {
-    if (S < 1 || S > MAX_S || B <= 0 || H <= 0 || W <= 0) return 0;
-    return (int64_t)S * B * tile_count(H, W) * (WP_NSUM + WP_NQ) * 8;
+    return bad_query(S, B, H, W) ? 0 : bwd_workspace(false, true, S, B, H, W).words * 8;
 }
 
 int e2e_warp_photo_window_bwd_intrinsics(const float* depth_tgt, const float* src0, const float* src1, e2e_strides src_strides, const float* tgt,
@@ -682,31 +723,14 @@ int e2e_warp_photo_window_bwd_intrinsics(const float* depth_tgt, const float* sr
                                          const float* valid, const int* select, int use_mask, int padding_mode, int terms, const float* g_loss,
                                          float* g_depth_tgt, float* g_T, float* g_K, float* g_inv_K, void* workspace, int S, int B, int H, int W,
                                          void* stream) {
-    const int rc = check_window("e2e_warp_photo_window_bwd_intrinsics", false, S, B, H, W, padding_mode, terms, 0);
-    if (rc != E2E_OK) return rc;
-    E2E_REQUIRE(depth_tgt && src0 && (src1 || S == 1) && tgt && K && inv_K && T && synth && valid && select && g_loss && g_depth_tgt && g_K &&
-                    g_inv_K && workspace,
-                E2E_ERR_ARG, "e2e_warp_photo_window_bwd_intrinsics: null pointer");
-    hipStream_t st = (hipStream_t)stream;
-    const int tiles = (int)tile_count(H, W);
-    double* partials = (double*)workspace;
-    for (const int sums : {WP_SUMS_POSE, WP_SUMS_INTRINSICS})      // the pose pass (g_depth_tgt, Pbar: e2e_warp_photo_window_bwd's bits), then the Q pass
-        launch_bwd<false>(padding_mode, sums, tile_grid(B, H, W), st, depth_tgt, (const float*)nullptr, (const float*)nullptr, src0, src1,
-                          src_strides, tgt, tgt_strides, K, inv_K, T, synth, valid, select, (const int*)nullptr, use_mask, terms, 0, g_loss,
-                          g_depth_tgt, (unsigned long long*)nullptr, partials, S, B, H, W);
-    E2E_LAUNCH_CHECK("e2e_warp_photo_window_bwd_intrinsics");
-    if (g_T) {
-        warp_photo_pose_final_launch(partials, tiles, K, g_T, S, B, st);
-        E2E_LAUNCH_CHECK("e2e_warp_photo_window_bwd_intrinsics(pose)");
-    }
-    warp_photo_intrinsics_final_launch(partials, partials + (int64_t)S * B * tiles * WP_NSUM, tiles, K, T, g_K, g_inv_K, S, B, st);
-    E2E_LAUNCH_CHECK("e2e_warp_photo_window_bwd_intrinsics(final)");
-    return E2E_OK;
+    WindowBwdArgs a{{depth_tgt, nullptr, nullptr, src0, src1, src_strides, tgt, tgt_strides, K, inv_K, T, use_mask, padding_mode, terms, 0, S, B, H, W}};
+    a.synth = synth; a.valid = valid; a.select = select; a.g_loss = g_loss; a.g_depth_tgt = g_depth_tgt; a.g_T = g_T; a.workspace = workspace;
+    a.g_K = g_K; a.g_inv_K = g_inv_K;
+    return window_bwd<false>("e2e_warp_photo_window_bwd_intrinsics", true, a, (hipStream_t)stream);
 }
 
 int64_t e2e_warp_photo_geo_bwd_intrinsics_workspace_bytes(int S, int B, int H, int W) {
-    if (S < 1 || S > MAX_S || B <= 0 || H <= 0 || W <= 0) return 0;
-    return (fixed_words(S, B, H, W) + (int64_t)S * B * tile_count(H, W) * (WP_NSUM + WP_NQ)) * 8;
+    return bad_query(S, B, H, W) ? 0 : bwd_workspace(true, true, S, B, H, W).words * 8;
 }
 
 int e2e_warp_photo_geo_bwd_intrinsics(const float* depth_tgt, const float* depth_src0, const float* depth_src1, const float* src0,
@@ -715,33 +739,11 @@ int e2e_warp_photo_geo_bwd_intrinsics(const float* depth_tgt, const float* depth
                                       const int* geo_count, int use_mask, int padding_mode, int terms, int geo_min_valid, const float* g_loss,
                                       float* g_depth_tgt, float* g_depth_src, float* g_T, float* g_K, float* g_inv_K, void* workspace, int S,
                                       int B, int H, int W, void* stream) {
-    const int rc = check_window("e2e_warp_photo_geo_bwd_intrinsics", true, S, B, H, W, padding_mode, terms, geo_min_valid);
-    if (rc != E2E_OK) return rc;
-    E2E_REQUIRE(depth_tgt && depth_src0 && (depth_src1 || S == 1) && src0 && (src1 || S == 1) && tgt && K && inv_K && T && synth && valid &&
-                    select && geo_count && g_loss && g_depth_tgt && g_depth_src && g_K && g_inv_K && workspace,
-                E2E_ERR_ARG, "e2e_warp_photo_geo_bwd_intrinsics: null pointer");
-    hipStream_t st = (hipStream_t)stream;
-    const int64_t words = fixed_words(S, B, H, W);
-    const int tiles = (int)tile_count(H, W);
-    unsigned long long* fx = (unsigned long long*)workspace;
-    double* partials = (double*)workspace + words;
-    E2E_REQUIRE(hipMemsetAsync(fx, 0, (size_t)words * 8, st) == hipSuccess, E2E_ERR_LAUNCH,
-                "e2e_warp_photo_geo_bwd_intrinsics: hipMemsetAsync of the fixed-point scratch failed");
-    for (const int sums : {WP_SUMS_POSE, WP_SUMS_INTRINSICS})      // the pose pass (both depth gradients, Pbar: e2e_warp_photo_geo_bwd's bits), then the Q pass
-        launch_bwd<true>(padding_mode, sums, tile_grid(B, H, W), st, depth_tgt, depth_src0, depth_src1, src0, src1, src_strides, tgt, tgt_strides, K,
-                         inv_K, T, synth, valid, select, geo_count, use_mask, terms, geo_min_valid, g_loss, g_depth_tgt, fx, partials, S, B, H, W);
-    E2E_LAUNCH_CHECK("e2e_warp_photo_geo_bwd_intrinsics");
-    const int64_t per_source = (int64_t)B * H * W, n = per_source * S;
-    hipLaunchKernelGGL(k_geo_fixed48_to_float, dim3((unsigned)((n + 255) / 256 > 4096 ? 4096 : (n + 255) / 256)), dim3(256), 0, st,
-                       (const long long*)fx, g_depth_src, per_source, S);
-    E2E_LAUNCH_CHECK("e2e_warp_photo_geo_bwd_intrinsics(depth_src)");
-    if (g_T) {
-        warp_photo_pose_final_launch(partials, tiles, K, g_T, S, B, st);
-        E2E_LAUNCH_CHECK("e2e_warp_photo_geo_bwd_intrinsics(pose)");
-    }
-    warp_photo_intrinsics_final_launch(partials, partials + (int64_t)S * B * tiles * WP_NSUM, tiles, K, T, g_K, g_inv_K, S, B, st);
-    E2E_LAUNCH_CHECK("e2e_warp_photo_geo_bwd_intrinsics(final)");
-    return E2E_OK;
+    WindowBwdArgs a{{depth_tgt, depth_src0, depth_src1, src0, src1, src_strides, tgt, tgt_strides, K, inv_K, T, use_mask, padding_mode, terms,
+                      geo_min_valid, S, B, H, W}};
+    a.synth = synth; a.valid = valid; a.select = select; a.g_loss = g_loss; a.g_depth_tgt = g_depth_tgt; a.g_T = g_T; a.workspace = workspace;
+    a.geo_count = geo_count; a.g_depth_src = g_depth_src; a.g_K = g_K; a.g_inv_K = g_inv_K;
+    return window_bwd<true>("e2e_warp_photo_geo_bwd_intrinsics", true, a, (hipStream_t)stream);
 }
 
 }  // extern "C"
