@@ -958,6 +958,65 @@ def smoothness(disp, img):
     return _Smoothness.apply(disp, img)
 
 
+class _DispPyramidSmoothness(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, img, weights, want_grad, *disps):
+        ds = [L.dev(d, "disp").contiguous() for d in disps]
+        im = L.dev(img, "img")
+        B, _, H, W = im.shape
+        pad = [None] * (PYRAMID_SCALES - len(ds))
+        sizes = _pyramid_args(ds)[PYRAMID_SCALES:]
+        out = torch.empty(PYRAMID_SCALES + 1, device=im.device, dtype=torch.float32)
+        gds = [torch.empty_like(d) for d in ds] if want_grad else []
+        ws = torch.empty(L.query("e2e_disp_pyramid_smoothness_workspace_floats", *sizes, B), device=im.device, dtype=torch.float32)
+        L.call("e2e_disp_pyramid_smoothness_lossgrad", *([L.ptr(d) for d in ds] + pad), *sizes, L.ptr(im), L.strides4(im), B, H, W,
+               *(list(weights) + [0.0] * len(pad)), L.ptr(out), *([L.ptr(g) for g in gds] + [None] * (PYRAMID_SCALES - len(gds))),
+               L.ptr(ws), L.stream())
+        ctx.save_for_backward(*gds)
+        return out                                                  # loss_out[5]: the graph is used through its last element only
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, go):
+        gds, needs = ctx.saved_tensors, ctx.needs_input_grad[3:]
+        if not gds:
+            return (None,) * (3 + len(needs))
+        return (None,) * 3 + tuple(g * go[PYRAMID_SCALES] if need else None for g, need in zip(gds, needs))
+
+
+def disp_pyramid_smoothness(disps, img, weights=None):
+    """monodepth2's edge-aware smoothness on every scale of the disparity pyramid: for each (B,1,h_s,w_s) disparity of `disps` (1 to 4
+    scales, finest first) the smoothness (loss/losses.py:119-132) of its mean-normalised form against img (B,3,H,W, any strides, a
+    constant) box-averaged to that scale's resolution -- F.avg_pool2d(img, (H / h_s, W / w_s)), so h_s must divide H and w_s W, and
+    both be >= 2 -- weighted by weights[s] (default 1 each) and summed.  One entry-point call (two launches whatever the number of
+    scales, e2e_disp_pyramid_smoothness_lossgrad) computes the loss and, where a disparity needs one, every gradient; the backward only
+    scales them.  Returns dict(smoothness = the weighted sum (0-dim, carries the graph), smoothness_per_scale (S,) detached, unweighted)."""
+    disps = list(disps)
+    if not 1 <= len(disps) <= PYRAMID_SCALES:
+        raise ValueError(f"disps: expected 1 to {PYRAMID_SCALES} scales, got {len(disps)}")
+    if not torch.is_tensor(img) or img.dim() != 4 or img.shape[1] != 3:
+        raise ValueError(f"img: expected (B,3,H,W), got {tuple(img.shape) if torch.is_tensor(img) else type(img).__name__}")
+    B, _, H, W = img.shape
+    for s, d in enumerate(disps):
+        if not torch.is_tensor(d) or d.dim() != 4 or d.shape[1] != 1:
+            raise ValueError(f"disps[{s}]: expected (B,1,h,w), got {tuple(d.shape) if torch.is_tensor(d) else type(d).__name__}")
+        if d.shape[0] != B:
+            raise ValueError(f"disps[{s}]: expected ({B},1,h,w) to go with img {tuple(img.shape)}, got {tuple(d.shape)}")
+        h, w = d.shape[2:]
+        if not (1 <= h <= H and 1 <= w <= W):
+            raise ValueError(f"disps[{s}]: {h} x {w} does not fit the image {H} x {W}")
+        if h < 2 or w < 2:
+            raise ValueError(f"disps[{s}]: {h} x {w}: the smoothness needs at least 2 x 2 (an axis of one pixel has no edge)")
+        if H % h or W % w:
+            raise ValueError(f"disps[{s}]: {h} x {w} does not divide the image {H} x {W} (the colour pyramid is a box mean over whole blocks)")
+    weights = [1.0] * len(disps) if weights is None else [float(v) for v in weights]
+    if len(weights) != len(disps):
+        raise ValueError(f"weights: expected one per scale ({len(disps)}), got {len(weights)}")
+    want_grad = torch.is_grad_enabled() and any(d.requires_grad for d in disps)
+    out = _DispPyramidSmoothness.apply(img, weights, want_grad, *disps)
+    return {"smoothness": out[PYRAMID_SCALES], "smoothness_per_scale": out.detach()[:len(disps)]}
+
+
 class _GeomConsistency(torch.autograd.Function):
     @staticmethod
     def forward(ctx, wd, idp, mask):

@@ -28,6 +28,10 @@ is ResnetEncoder + DepthDecoder with a sigmoid disparity at every scale of `DATA
 `LOSS.multiscale: True` (absent = False; monodepth2 only, not in the reference, which took monodepth2's decoder without its loss) takes the
 image-space term on every scale of `DATA.scales` -- each disparity upsampled to the input resolution, e2e_disp_pyramid_depth_fwd / _bwd --
 and averages, on the same fused pair with the scales stacked along the batch; everything else of a step stays on scale 0.
+`LOSS.multiscale_smoothness: True` (absent = False; needs LOSS.multiscale and LOSS.smoothness) takes the smoothness term on every scale of
+`DATA.scales` as monodepth2 does: each scale's mean-normalised disparity of frame 0 against the target image box-averaged to that scale's
+resolution (F.avg_pool2d; monodepth2's dataloader resizes with an antialiasing filter instead), weighted 1 / (2^s S) -- its
+`smooth_loss / 2**scale` followed by `/ num_scales` -- in one call of e2e_disp_pyramid_smoothness_lossgrad (ops.disp_pyramid_smoothness).
 
     python train_depth.py --config_path configs/config_train_depth.yaml
 """
@@ -84,6 +88,10 @@ class Depth_Estimation:
             if not fused_losses or self.args.LOSS.photometric_mask is None:
                 raise NotImplementedError("LOSS.multiscale with fused_losses=False (or LOSS.photometric_mask: None): the multi-scale loss "
                                           "runs on the fused warp-photometric pair only")
+        # LOSS.multiscale_smoothness (absent = False): monodepth2's regulariser on every scale of DATA.scales (compute_smoothness_loss)
+        self.multiscale_smoothness = bool(getattr(self.args.LOSS, "multiscale_smoothness", False))
+        if self.multiscale_smoothness and not (self.multiscale and self.args.LOSS.smoothness):
+            raise ValueError("LOSS.multiscale_smoothness needs LOSS.multiscale: True and LOSS.smoothness: True")
         # DATA.use_gt_pose: False -- the estimated poses carry the gradient of the loss through the odometry into the predicted depth, as
         # the reference's do (train_depth.py:381-382, :395).  E2E_POSE_GRAD=0 (or pose_gradient = False): the poses are constants.
         self.pose_gradient = os.environ.get("E2E_POSE_GRAD", "1") != "0"
@@ -510,7 +518,12 @@ class Depth_Estimation:
         return torch.stack([geometric_consistency_loss(outputs, frame, self.device) for frame in self.args.DATA.frames[1:]], dim=0)
 
     def compute_smoothness_loss(self, inputs):
-        """mean-normalised disparity of frame 0 against the target image (train_depth.py:763-773)."""
+        """mean-normalised disparity of frame 0 against the target image (train_depth.py:763-773); with LOSS.multiscale_smoothness every
+        scale of DATA.scales against the image at that scale's resolution, weighted 1 / (2^s S) as monodepth2 weights them."""
+        if self.multiscale_smoothness:
+            scales = sorted(self.args.DATA.scales)
+            return ops.disp_pyramid_smoothness([inputs["disp", 0, s] for s in scales], inputs["target_frame"],
+                                               weights=[1.0 / (2 ** s * len(scales)) for s in scales])["smoothness"]
         return disparity_smoothness_loss(disp=ops.mean_normalize(inputs[("disp", 0, 0)]), img=inputs["target_frame"])
 
     def compute_depth_regularizer(self, inputs):

@@ -1158,6 +1158,38 @@ int e2e_disp_pyramid_depth_bwd(const float* g_depth, const float* disp0, const f
                                int w0, int h1, int w1, int h2, int w2, int h3, int w3, int B, int H, int W, float min_depth, float max_depth,
                                float scale, float* g_disp0, float* g_disp1, float* g_disp2, float* g_disp3, void* stream);
 
+/* The multi-scale edge-aware smoothness of monodepth2 (csrc/disp_pyramid_smooth.hip; LOSS.multiscale_smoothness): every scale's
+ * mean-normalised disparity held against the colour image at that scale's own resolution, loss and gradient in one call.
+ * Slots: dispK is (B,1,hK,wK) contiguous; a NULL dispK is an absent scale: its sizes, weight and g_dispK are not read and its g_dispK
+ * buffer is not written.
+ * Image: img is (B,3,H,W) read through img_strides (an NCHW view of NHWC memory works).  For slot K, fy = H / hK and fx = W / wK must be
+ * integers >= 1 (they may differ); the image of scale K is the box mean of each fy x fx block per channel, F.avg_pool2d(img, (fy, fx)),
+ * each box summed in a fixed order (the fy rows of a column top down, then the fx column sums left to right).  This box pyramid is
+ * this project's definition: monodepth2's dataloader resizes the colour image with an antialiasing filter instead.
+ * Loss, per present scale (losses.py:119-132 on the mean-normalised disparity of online_adaption.py:600-610):
+ *     n = d / (m + 1e-7), m the mean of d over one image's plane
+ *     loss_K = mean over B h (w-1) x-edges of |n(y,x) - n(y,x+1)| exp(-mean_c |img_K(c,y,x) - img_K(c,y,x+1)|)
+ *            + mean over B (h-1) w y-edges of the same in y
+ * loss_out[5]: loss_out[K] = loss_K, unweighted, 0 for an absent slot; loss_out[4] = sum_K weightK loss_K.  All five are always written.
+ * Gradients: g_dispK = weightK d loss_K / d dispK, the mean's own contribution included; every element is written, nothing is
+ * accumulated.  The subgradient of |.| at 0 is 0: a constant plane gives a loss of exactly 0 and a gradient of exactly 0 everywhere.
+ * The sign of an edge is taken from the raw difference d(p) - d(q).  Either every present scale has its g_disp, or all four are NULL
+ * (the loss alone; loss_out then has the bits of the call with gradients).
+ * Two launches whatever S and B are (the grid's z index is (scale, batch element)); no atomics: per-tile partial sums go into
+ * `workspace` (e2e_disp_pyramid_smoothness_workspace_floats floats: partial sums only, no per-pixel plane) and are added in a fixed
+ * order, the per-pixel gradient is staged in g_dispK and scaled in place.  Two calls give the same bits.
+ * Refused with E2E_ERR_ARG before any launch, nothing written: a NULL img, loss_out or workspace; no scale present; a present scale
+ * with h < 2, w < 2, h > H, w > W, H % h != 0 or W % w != 0; some but not all present scales with a g_disp; B < 1, H < 1 or W < 1;
+ * S * B above 65535; an image whose strided extent (sum over the axes of (n - 1) |stride|) does not fit the int64_t of e2e_strides.
+ * The workspace query takes 0 x 0 for an absent scale and returns 0 for sizes the entry point refuses. */
+int64_t e2e_disp_pyramid_smoothness_workspace_floats(int h0, int w0, int h1, int w1, int h2, int w2, int h3, int w3, int B);
+int e2e_disp_pyramid_smoothness_lossgrad(const float* disp0, const float* disp1, const float* disp2, const float* disp3,
+        int h0, int w0, int h1, int w1, int h2, int w2, int h3, int w3,
+        const float* img, e2e_strides img_strides, int B, int H, int W,
+        float weight0, float weight1, float weight2, float weight3,
+        float* loss_out, float* g_disp0, float* g_disp1, float* g_disp2, float* g_disp3,
+        float* workspace, void* stream);
+
 /* ------------------------------------------------------------------------------------------ */
 /* Frame-to-model ICP odometry (gradslam odometry providers; MODEL.odom: icp | gradicp)          */
 /* ------------------------------------------------------------------------------------------ */
