@@ -5,7 +5,7 @@
 // e2e_warp_photo_geo_* (GEO = true): the text is the geometric kernel's, and the compile-time constant GEO deletes the geometric pieces
 // from the window's instantiation (profiles/warp_window_geo_merge.txt).  One tile launch forward (+ the fixed-order reduction of the workgroups'
 // partial sums), one tile launch backward (+ a final kernel per source and batch element when the gradient with respect to the poses is
-// asked for).  On the host the six entry points fill one operand struct and share ONE forward path (window_fwd<GEO>) and ONE backward path
+// asked for).  On the host the eight entry points fill one operand struct and share ONE forward path (window_fwd<GEO>) and ONE backward path
 // (window_bwd<GEO>, without or with the intrinsics); the workspace layouts are stated once, for the size queries and the paths alike.
 //
 // Semantics of the window.  For source s with its validity mask m_s (1 everywhere when use_mask == 0):
@@ -43,6 +43,12 @@
 // Both add into the gc of the photometric adjoint, so g_depth_tgt = gc . r and the 12 float64 pose sums carry the term.  A closed gate -- or
 // an upstream g_loss[1+s] of exactly 0 -- skips the piece: g_depth_tgt and g_T then have the bits of the photometric part alone and
 // g_depth_src[s] is all zero.
+//
+// Scale groups (e2e_warp_photo_geo_groups_fwd / _bwd: monodepth2's disparity pyramid, the scales stacked along the batch).  The batch is G
+// groups of B / G items, group g the items g B / G ... (g + 1) B / G - 1, and ONLY the term's reduction and gate are per group: n_{s,g}, G_{s,g}
+// and the upstream g_loss[1 + s G + g] live in slot [s G + g].  The forward tile kernel is untouched: its partials are batch-major, so
+// k_geo_final sums a group's run of blocks exactly as it sums a whole call's, and group g comes out with the bits of a call on its slice.
+// The backward tile kernel reads its item's slot.  The other entry points are the G = 1 case of the same two kernels.
 //
 // (i) is a data-dependent scatter.  It is made order-independent as in e2e_grid_sample_bwd_exact: 2^-48 fixed-point int64 atomic adds into
 // workspace zeroed by the call, then a conversion pass that writes all of g_depth_src; a contribution that is not finite or not below 4096
@@ -246,22 +252,26 @@ __global__ __launch_bounds__(NTHREADS) void k_warp_photo_window_fwd(
     }
 }
 
-// one wave per source: lane l adds the workgroups' partials l, l + 64, ... in order, then a fixed shuffle tree; the count is an integer sum
+// one wave per source and scale group (grid (S, G); G = 1: the whole call): lane l adds the group's workgroup partials l, l + 64, ... counted
+// from the group's first block, in order, then a fixed shuffle tree; the count is an integer sum.  The tile kernel numbers its blocks
+// batch-major, so group g owns the nblk / G blocks from g nblk / G on, and its sum is the sum a call on that group's slice would form.
 __global__ __launch_bounds__(64) void k_geo_final(const float* __restrict__ gpart, const int* __restrict__ cpart, int nblk, int geo_min_valid,
                                                   int* __restrict__ geo_count, float* __restrict__ loss_out) {
-    const int s = blockIdx.x, lane = threadIdx.x;
+    const int s = blockIdx.x, g = blockIdx.y, G = gridDim.y, lane = threadIdx.x;
+    const int per_group = nblk / G;
+    const int64_t first = (int64_t)s * nblk + (int64_t)g * per_group;
     double a = 0.0;
     long long n = 0;
-    for (int i = lane; i < nblk; i += 64) {
-        a += (double)gpart[(int64_t)s * nblk + i];
-        n += cpart[(int64_t)s * nblk + i];
+    for (int i = lane; i < per_group; i += 64) {
+        a += (double)gpart[first + i];
+        n += cpart[first + i];
     }
     a = wave_sum_d(a);
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) n += __shfl_down(n, o, 64);
     if (lane == 0) {
-        geo_count[s] = (int)n;
-        loss_out[1 + s] = (n > (long long)geo_min_valid) ? (float)(a / (double)n) : 0.f;
+        geo_count[s * G + g] = (int)n;
+        loss_out[1 + s * G + g] = (n > (long long)geo_min_valid) ? (float)(a / (double)n) : 0.f;
     }
 }
 
@@ -273,6 +283,8 @@ __global__ __launch_bounds__(64) void k_geo_final(const float* __restrict__ gpar
 // in a second region behind the pose sums, [((s B + b) tiles + tile) * 9 + r * 3 + j]: no depth gradient, no depth scatter, no pose sums.
 // GEO: the image index is align_corners=True, and per source the geometric adjoint of the own pixel is added.  Without GEO dsrc0 / dsrc1 /
 // geo_count / geo_min_valid / fx and g_loss[1..] are not read (the window passes NULL and 0).
+// group_items = B / G, the batch items per scale group: item b reads the count and the upstream of slot s G + b / group_items.  Every entry
+// point but the grouped pair passes B (one group, slot s).
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ float source_weight(int sel, int s, int nI, bool minrep, float gl, float gl_mean) {
     if (sel < nI) return 0.f;                            // an identity candidate won: constants only
@@ -293,7 +305,7 @@ __global__ __launch_bounds__(NTHREADS) void k_warp_photo_window_bwd(
     const float* __restrict__ invK, const float* __restrict__ T, const float* __restrict__ synth, const float* __restrict__ valid,
     const int* __restrict__ select, const int* __restrict__ geo_count, int use_mask, int terms, int geo_min_valid,
     const float* __restrict__ g_loss, float* __restrict__ g_dt, unsigned long long* __restrict__ fx, double* __restrict__ partials, int S,
-    int B, int H, int W) {
+    int B, int H, int W, int group_items) {
     constexpr bool POSE = SUMS != WP_SUMS_NONE, INTR = SUMS == WP_SUMS_INTRINSICS;
     __shared__ float lx[3][BP_N], ly[3][BP_N];
     __shared__ float lg[9][BG_N];
@@ -329,8 +341,9 @@ __global__ __launch_bounds__(NTHREADS) void k_warp_photo_window_bwd(
         const int64_t sbi = (int64_t)s * B + b;
         const float* syn = synth + sbi * 3 * N;
         const float* val = valid + sbi * N;
-        const int ns = GEO ? geo_count[s] : 0;
-        const float e = (GEO && ns > geo_min_valid && ns > 0) ? g_loss[1 + s] / (float)ns : 0.f;      // 0: the gate is closed, the piece is skipped
+        const int slot = GEO ? s * (B / group_items) + b / group_items : 0;      // [s G + g] of this item's scale group; group_items = B: s
+        const int ns = GEO ? geo_count[slot] : 0;
+        const float e = (GEO && ns > geo_min_valid && ns > 0) ? g_loss[1 + slot] / (float)ns : 0.f;   // 0: the gate is closed, the piece is skipped
         if (s) __syncthreads();                          // source s-1's planes (and its pose sums) have been read
         for (int i = tid; i < BP_N; i += NTHREADS) {
             const int l_y = i / BP_LD, l_x = i % BP_LD;
@@ -522,6 +535,7 @@ struct WindowArgs {
     const float *K, *inv_K, *T;
     int use_mask, padding_mode, terms, geo_min_valid;
     int S, B, H, W;
+    int groups = 1;                                      // scale groups of the batch (the grouped geo pair sets it; see check_groups)
 };
 // the rest of each direction's list; an entry point sets by name what it has, the others stay NULL (the forward writes what the backward reads)
 struct WindowFwdArgs : WindowArgs {
@@ -548,6 +562,15 @@ int check_window(const char* name, bool geo, const WindowArgs& a) {
                 "%s: terms %d (E2E_TERM_AUTO_MASKING | E2E_TERM_MIN_REPROJECTION; the geometric term %s)", name, a.terms,
                 geo ? "is always on here" : "stays on the operators");
     E2E_REQUIRE(!geo || a.geo_min_valid >= 0, E2E_ERR_ARG, "%s: geo_min_valid %d is negative", name, a.geo_min_valid);
+    return E2E_OK;
+}
+
+// the grouped geo pair's own refusals, after everything the geo pair refuses: the batch is `groups` scale groups of B / groups items each,
+// group g the items g B / groups ... (g + 1) B / groups - 1.  The other entry points have one group and pass.
+constexpr int MAX_GROUPS = 4;                            // PYRAMID_SCALES of e2e_disp_pyramid_depth_fwd
+int check_groups(const char* name, const WindowArgs& a) {
+    E2E_REQUIRE(a.groups >= 1 && a.groups <= MAX_GROUPS, E2E_ERR_ARG, "%s: groups=%d scale groups (1 to %d)", name, a.groups, MAX_GROUPS);
+    E2E_REQUIRE(a.B % a.groups == 0, E2E_ERR_ARG, "%s: B=%d is not a multiple of groups=%d", name, a.B, a.groups);
     return E2E_OK;
 }
 
@@ -588,6 +611,7 @@ int window_fwd(const char* name, const WindowFwdArgs& a, hipStream_t st) {
     E2E_REQUIRE(a.depth_tgt && a.src0 && (a.src1 || a.S == 1) && a.tgt && a.K && a.inv_K && a.T && a.synth && a.valid && a.select && a.loss_out &&
                     a.workspace && (!GEO || (a.depth_src0 && (a.depth_src1 || a.S == 1) && a.geo_count)),
                 E2E_ERR_ARG, "%s: null pointer", name);
+    if (const int rc = check_groups(name, a)) return rc;
     const FwdWorkspace ws = fwd_workspace(GEO, a.S, a.B, a.H, a.W);
     float* gpart = GEO ? a.workspace + ws.gpart : nullptr;
     int* cpart = GEO ? (int*)(a.workspace + ws.cpart) : nullptr;
@@ -600,7 +624,7 @@ int window_fwd(const char* name, const WindowFwdArgs& a, hipStream_t st) {
     warp_photo_reduce_launch(a.workspace, (int)ws.nblk, 1, scale, a.loss_out, st);
     if (const int rc = warp_photo_launch_status(name, "(reduce)")) return rc;
     if constexpr (GEO) {
-        hipLaunchKernelGGL(k_geo_final, dim3(a.S), dim3(64), 0, st, gpart, cpart, (int)ws.nblk, a.geo_min_valid, a.geo_count, a.loss_out);
+        hipLaunchKernelGGL(k_geo_final, dim3(a.S, a.groups), dim3(64), 0, st, gpart, cpart, (int)ws.nblk, a.geo_min_valid, a.geo_count, a.loss_out);
         if (const int rc = warp_photo_launch_status(name, "(geometric)")) return rc;
     }
     return E2E_OK;
@@ -620,6 +644,7 @@ int window_bwd(const char* name, bool intrinsics, const WindowBwdArgs& a, hipStr
                     (!intrinsics || (a.g_K && a.g_inv_K && a.workspace)),
                 E2E_ERR_ARG, "%s: null pointer", name);
     E2E_REQUIRE(!a.g_T || a.workspace, E2E_ERR_ARG, "%s: g_T without workspace", name);
+    if (const int rc = check_groups(name, a)) return rc;
     const WarpPhotoBwdWorkspace ws = bwd_workspace(GEO, intrinsics, a.S, a.B, a.H, a.W);
     const int tiles = (int)tile_count(a.H, a.W);
     unsigned long long* fx = GEO ? (unsigned long long*)a.workspace : nullptr;
@@ -630,7 +655,8 @@ int window_bwd(const char* name, bool intrinsics, const WindowBwdArgs& a, hipStr
     const auto tile_pass = [&](int sums) {
         hipLaunchKernelGGL(bwd_kernel<GEO>(a.padding_mode == E2E_PADDING_BORDER, sums), tile_grid(a.B, a.H, a.W), dim3(TW, TH), 0, st, a.depth_tgt,
                            a.depth_src0, a.depth_src1, a.src0, a.src1, a.src_strides, a.tgt, a.tgt_strides, a.K, a.inv_K, a.T, a.synth, a.valid,
-                           a.select, a.geo_count, a.use_mask, a.terms, a.geo_min_valid, a.g_loss, a.g_depth_tgt, fx, partials, a.S, a.B, a.H, a.W);
+                           a.select, a.geo_count, a.use_mask, a.terms, a.geo_min_valid, a.g_loss, a.g_depth_tgt, fx, partials, a.S, a.B, a.H, a.W,
+                           a.B / a.groups);
     };
     tile_pass(a.g_T || intrinsics ? WP_SUMS_POSE : WP_SUMS_NONE);
     if (intrinsics) tile_pass(WP_SUMS_INTRINSICS);                  // the Q pass, always second
@@ -712,6 +738,30 @@ int e2e_warp_photo_geo_bwd(const float* depth_tgt, const float* depth_src0, cons
     a.synth = synth; a.valid = valid; a.select = select; a.g_loss = g_loss; a.g_depth_tgt = g_depth_tgt; a.g_T = g_T; a.workspace = workspace;
     a.geo_count = geo_count; a.g_depth_src = g_depth_src;
     return window_bwd<true>("e2e_warp_photo_geo_bwd", false, a, (hipStream_t)stream);
+}
+
+int e2e_warp_photo_geo_groups_fwd(const float* depth_tgt, const float* depth_src0, const float* depth_src1, const float* src0, const float* src1,
+                                  e2e_strides src_strides, const float* tgt, e2e_strides tgt_strides, const float* K, const float* inv_K,
+                                  const float* T, const float* tie_noise, float* synth, float* valid, int* select, float* pmap, int* geo_count,
+                                  int use_mask, int padding_mode, int terms, int geo_min_valid, float* loss_out, float* workspace, int S,
+                                  int groups, int B, int H, int W, void* stream) {
+    WindowFwdArgs a{{depth_tgt, depth_src0, depth_src1, src0, src1, src_strides, tgt, tgt_strides, K, inv_K, T, use_mask, padding_mode, terms,
+                      geo_min_valid, S, B, H, W, groups}};
+    a.tie_noise = tie_noise; a.synth = synth; a.valid = valid; a.select = select; a.pmap = pmap; a.loss_out = loss_out; a.workspace = workspace;
+    a.geo_count = geo_count;
+    return window_fwd<true>("e2e_warp_photo_geo_groups_fwd", a, (hipStream_t)stream);
+}
+
+int e2e_warp_photo_geo_groups_bwd(const float* depth_tgt, const float* depth_src0, const float* depth_src1, const float* src0, const float* src1,
+                                  e2e_strides src_strides, const float* tgt, e2e_strides tgt_strides, const float* K, const float* inv_K,
+                                  const float* T, const float* synth, const float* valid, const int* select, const int* geo_count, int use_mask,
+                                  int padding_mode, int terms, int geo_min_valid, const float* g_loss, float* g_depth_tgt, float* g_depth_src,
+                                  float* g_T, void* workspace, int S, int groups, int B, int H, int W, void* stream) {
+    WindowBwdArgs a{{depth_tgt, depth_src0, depth_src1, src0, src1, src_strides, tgt, tgt_strides, K, inv_K, T, use_mask, padding_mode, terms,
+                      geo_min_valid, S, B, H, W, groups}};
+    a.synth = synth; a.valid = valid; a.select = select; a.g_loss = g_loss; a.g_depth_tgt = g_depth_tgt; a.g_T = g_T; a.workspace = workspace;
+    a.geo_count = geo_count; a.g_depth_src = g_depth_src;
+    return window_bwd<true>("e2e_warp_photo_geo_groups_bwd", false, a, (hipStream_t)stream);
 }
 
 int64_t e2e_warp_photo_window_bwd_intrinsics_workspace_bytes(int S, int B, int H, int W) {

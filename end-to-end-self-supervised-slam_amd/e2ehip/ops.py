@@ -312,14 +312,19 @@ TERM_AUTO_MASKING, TERM_MIN_REPROJECTION = 2, 4                # E2E_TERM_* of i
 
 class _WarpPhotometricWindow(torch.autograd.Function):
     """the window (e2e_warp_photo_window_fwd / _bwd), or -- with geo_min_valid and one depth per source -- the window with the
-    geometric-consistency term (e2e_warp_photo_geo_fwd / _bwd); geo_min_valid None: dsrc0 / dsrc1 are None, and so are the outputs geo and count"""
+    geometric-consistency term (e2e_warp_photo_geo_fwd / _bwd); geo_min_valid None: dsrc0 / dsrc1 are None, and so are the outputs geo and count.
+    groups = G (not None, with the geometric term only): the batch is G scale groups and the term is reduced and gated per group
+    (e2e_warp_photo_geo_groups_fwd / _bwd); geo and count are then (S G,), indexed [s G + g]"""
 
     @staticmethod
-    def forward(ctx, depth_tgt, dsrc0, dsrc1, src0, src1, tgt, K, inv_K, T0, T1, tie_noise, pad, use_mask, terms, geo_min_valid, want_pmap):
+    def forward(ctx, depth_tgt, dsrc0, dsrc1, src0, src1, tgt, K, inv_K, T0, T1, tie_noise, pad, use_mask, terms, geo_min_valid, want_pmap,
+                groups):
         B, _, H, W = depth_tgt.shape
         S = 1 if src1 is None else 2
         geo = geo_min_valid is not None
+        G = 1 if groups is None else groups
         name = "e2e_warp_photo_geo" if geo else "e2e_warp_photo_window"
+        entry = name if groups is None else "e2e_warp_photo_geo_groups"
         dt = L.dev(depth_tgt, "depth_tgt").contiguous()
         ds0 = L.dev(dsrc0, "depth_src").contiguous() if geo else None
         ds1 = L.dev(dsrc1, "depth_src").contiguous() if geo and S == 2 else None
@@ -338,16 +343,18 @@ class _WarpPhotometricWindow(torch.autograd.Function):
         valid = torch.empty(S, B, 1, H, W, device=dev, dtype=torch.float32)
         select = torch.empty(B, 1, H, W, device=dev, dtype=torch.int32)
         pmap = torch.empty(B, 1, H, W, device=dev, dtype=torch.float32) if want_pmap else None
-        count = torch.empty(S, device=dev, dtype=torch.int32) if geo else None
-        loss = torch.zeros(1 + S if geo else 1, device=dev, dtype=torch.float32)
+        count = torch.empty(S * G, device=dev, dtype=torch.int32) if geo else None
+        loss = torch.zeros(1 + S * G if geo else 1, device=dev, dtype=torch.float32)
         ws = torch.empty(L.query(name + "_workspace_floats", S, B, H, W), device=dev, dtype=torch.float32)
         more = dict(depth_src0=L.ptr(ds0), depth_src1=L.ptr(ds1), geo_count=L.ptr(count), geo_min_valid=geo_min_valid) if geo else {}
-        L.call(name + "_fwd", depth_tgt=L.ptr(dt), src0=L.ptr(src0), src1=L.ptr(src1), src_strides=L.strides4(src0), tgt=L.ptr(tgt),
+        if groups is not None:
+            more["groups"] = groups
+        L.call(entry + "_fwd", depth_tgt=L.ptr(dt), src0=L.ptr(src0), src1=L.ptr(src1), src_strides=L.strides4(src0), tgt=L.ptr(tgt),
                tgt_strides=L.strides4(tgt), K=L.ptr(K), inv_K=L.ptr(inv_K), T=L.ptr(T), tie_noise=L.ptr(noise), synth=L.ptr(synth), valid=L.ptr(valid),
                select=L.ptr(select), pmap=L.ptr(pmap), use_mask=int(use_mask), padding_mode=pad, terms=terms, loss_out=L.ptr(loss),
                workspace=L.ptr(ws), S=S, B=B, H=H, W=W, stream=L.stream(), **more)
         ctx.save_for_backward(dt, ds0, ds1, src0, src1, tgt, K, inv_K, T, synth, valid, select, count)
-        ctx.cfg = (pad, int(use_mask), terms, geo_min_valid, S, B, H, W)
+        ctx.cfg = (pad, int(use_mask), terms, geo_min_valid, S, B, H, W, groups)
         ctx.mark_non_differentiable(*(t for t in (synth, valid, select, count, pmap) if t is not None))
         return loss[0], (loss[1:] if geo else None), synth, valid, select, count, pmap
 
@@ -355,13 +362,13 @@ class _WarpPhotometricWindow(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, g0, g1, *_):
         dt, ds0, ds1, src0, src1, tgt, K, inv_K, T, synth, valid, select, count = ctx.saved_tensors
-        pad, use_mask, terms, geo_min_valid, S, B, H, W = ctx.cfg
+        pad, use_mask, terms, geo_min_valid, S, B, H, W, groups = ctx.cfg
         geo = geo_min_valid is not None
         name = "e2e_warp_photo_geo" if geo else "e2e_warp_photo_window"
         dev = dt.device
         gl = (g0 if g0 is not None else torch.zeros((), device=dev)).reshape(1)
         if geo:
-            gl = torch.cat([gl, g1 if g1 is not None else torch.zeros(S, device=dev)])
+            gl = torch.cat([gl, g1 if g1 is not None else torch.zeros(S * (groups or 1), device=dev)])
         gl = gl.contiguous()
         gdt = torch.empty(B, 1, H, W, device=dev, dtype=torch.float32)
         gds = torch.empty(S, B, 1, H, W, device=dev, dtype=torch.float32) if geo else None
@@ -371,12 +378,16 @@ class _WarpPhotometricWindow(torch.autograd.Function):
         more = dict(depth_src0=L.ptr(ds0), depth_src1=L.ptr(ds1), geo_count=L.ptr(count), geo_min_valid=geo_min_valid,
                     g_depth_src=L.ptr(gds)) if geo else {}
         entry = name + "_bwd"
+        if groups is not None:                                  # the grouped pair has no intrinsics form: warp_photometric_multiscale refuses K / inv_K
+            more["groups"] = groups
         if ctx.needs_input_grad[6] or ctx.needs_input_grad[7]:  # an intrinsic is a parameter (intrinsics_grad=True): both gradients, summed over the sources
             entry = name + "_bwd_intrinsics"
             gK, giK = (torch.empty(B, 4, 4, device=dev, dtype=torch.float32) for _ in range(2))
             more.update(g_K=L.ptr(gK), g_inv_K=L.ptr(giK))
         if geo or gT is not None or gK is not None:            # the float64 sums; the geometric form's depth scatter always needs its scratch
             ws = torch.empty(L.query(entry + "_workspace_bytes", S, B, H, W), device=dev, dtype=torch.uint8)
+        if groups is not None:
+            entry = "e2e_warp_photo_geo_groups_bwd"             # the geo pair's workspace at the stacked batch
         L.call(entry, depth_tgt=L.ptr(dt), src0=L.ptr(src0), src1=L.ptr(src1), src_strides=L.strides4(src0), tgt=L.ptr(tgt),
                tgt_strides=L.strides4(tgt), K=L.ptr(K), inv_K=L.ptr(inv_K), T=L.ptr(T), synth=L.ptr(synth), valid=L.ptr(valid), select=L.ptr(select),
                use_mask=use_mask, padding_mode=pad, terms=terms, g_loss=L.ptr(gl), g_depth_tgt=L.ptr(gdt), g_T=L.ptr(gT), workspace=L.ptr(ws),
@@ -384,7 +395,7 @@ class _WarpPhotometricWindow(torch.autograd.Function):
         g_T0 = gT[0] if gT is not None and ctx.needs_input_grad[8] else None
         g_T1 = gT[1] if gT is not None and S == 2 and ctx.needs_input_grad[9] else None
         return (gdt, gds[0] if geo else None, gds[1] if geo and S == 2 else None) + (None,) * 3 + \
-            (gK if ctx.needs_input_grad[6] else None, giK if ctx.needs_input_grad[7] else None, g_T0, g_T1) + (None,) * 6
+            (gK if ctx.needs_input_grad[6] else None, giK if ctx.needs_input_grad[7] else None, g_T0, g_T1) + (None,) * 7
 
 
 def warp_photometric_window(depth_tgt, srcs, tgt, K, inv_K, Ts, padding_mode="border", use_mask=True, min_reprojection=False,
@@ -425,7 +436,7 @@ def warp_photometric_window(depth_tgt, srcs, tgt, K, inv_K, Ts, padding_mode="bo
         depth_srcs, geo_min_valid = [None, None], None
     p, geo, synth, valid, select, count, pmap = _WarpPhotometricWindow.apply(
         depth_tgt, depth_srcs[0], depth_srcs[1] if S == 2 else None, srcs[0], srcs[1] if S == 2 else None, tgt, K, inv_K, Ts[0],
-        Ts[1] if S == 2 else None, tie_noise, _padding(padding_mode), bool(use_mask), terms, geo_min_valid, bool(want_pmap))
+        Ts[1] if S == 2 else None, tie_noise, _padding(padding_mode), bool(use_mask), terms, geo_min_valid, bool(want_pmap), None)
     out = {"photometric": p, "synth": synth, "valid": valid, "select": select, "pmap": pmap}
     if geometric:
         out.update(geometric=geo, geo_count=count)
@@ -840,8 +851,14 @@ def disp_pyramid_depth(disps, size, min_depth, max_depth, scale=1.0):
     return _DispPyramidDepth.apply((H, W), min_depth, max_depth, scale, *disps)
 
 
+class MissingDispSrcs(ValueError, TypeError):
+    """warp_photometric_multiscale(geometric=True) without disp_srcs: an argument the call requires is absent, which Python reports as a
+    TypeError, and an unusable value of the keyword pair, which this package reports as a ValueError; callers may catch either"""
+
+
 def warp_photometric_multiscale(disps, srcs, tgt, K, inv_K, Ts, min_depth, max_depth, scale=1.0, padding_mode="border", use_mask=True,
-                                min_reprojection=False, auto_masking=False, tie_noise=None):
+                                min_reprojection=False, auto_masking=False, tie_noise=None, geometric=False, disp_srcs=None,
+                                geo_min_valid=10000):
     """monodepth2's multi-scale image-space loss: every scale's disparity is brought to the size of the frames and converted to depth
     (disp_pyramid_depth), the S scales are stacked along the batch, and ONE fused pair warps and compares them all at full resolution:
     warp_photometric for one source and no flags, warp_photometric_window otherwise.  The pair's mean over the stacked batch is
@@ -851,13 +868,37 @@ def warp_photometric_multiscale(disps, srcs, tgt, K, inv_K, Ts, min_depth, max_d
     source; tie_noise (B,len(srcs),H,W) or None, the same draw for every scale.  With B = 1 the frames are read in place by every scale
     (a batch stride of 0); with a larger batch they are copied once per scale, as the kernels address the batch by one stride.
     Returns dict(photometric, photometric_per_scale (S,) detached, depth (S,B,1,H,W)).  Differentiated: every disparity and every T
-    (stacked S times, so a pose with a graph gets the sum over the scales through e2e_warp_photo_bwd_pose / the window's backward)."""
+    (stacked S times, so a pose with a graph gets the sum over the scales through e2e_warp_photo_bwd_pose / the window's backward).
+
+    geometric=True adds the geometric-consistency term PER SCALE, as monodepth2's loss loop would take LOSS.geometric: disp_srcs holds one
+    list of disparities per source frame, each with the scales and shapes of `disps`; every source's pyramid goes through
+    disp_pyramid_depth exactly as the target's does, and ONE pair, e2e_warp_photo_geo_groups_fwd / _bwd with groups = len(disps), warps
+    every scale and reduces and gates the term per scale (n_{s,g} > geo_min_valid; the reference's 10000).  As under
+    warp_photometric_window(geometric=True) the source images are then sampled with align_corners=True.  The pyramids are one
+    disp_pyramid_depth call each rather than one call over target and sources stacked along the batch: each call's (G,B,1,H,W) result
+    IS the contiguous stacked batch the pair reads, whereas one stacked call would hand the pair strided slices and cost a copy of
+    every full-resolution depth (and of its gradient) per step, more than the len(srcs) small launches each way it saves.  The dict gains
+    geometric (len(srcs),) = mean_g G_{s,g}, differentiable; geometric_per_scale (G, len(srcs)), detached; geo_count (G, len(srcs)) int32.
+    Differentiated then: every target disparity, every source disparity and every T, through one autograd node for the pair.  K or inv_K
+    requiring grad raises NotImplementedError (the grouped pair has no intrinsics form)."""
     srcs, Ts = list(srcs), list(Ts)
     B, _, H, W = tgt.shape if torch.is_tensor(tgt) and tgt.dim() == 4 else (0, 0, 0, 0)
     if B == 0 or tgt.shape[1] != 3:
         raise ValueError(f"target_frame: expected (B,3,H,W), got {tuple(tgt.shape) if torch.is_tensor(tgt) else type(tgt).__name__}")
     if len(srcs) not in (1, 2) or len(Ts) != len(srcs):
         raise ValueError(f"warp_photometric_multiscale: expected 1 or 2 source frames and as many poses, got {len(srcs)} and {len(Ts)}")
+    if geometric:
+        if disp_srcs is None:
+            raise MissingDispSrcs("warp_photometric_multiscale: geometric=True needs disp_srcs, one list of disparities per source frame "
+                                  "with the scales and shapes of disps")
+        disps = list(disps)
+        disp_srcs = [list(p) for p in disp_srcs]
+        if len(disp_srcs) != len(srcs) or any(len(p) != len(disps) or any(not torch.is_tensor(d) or not torch.is_tensor(t) or d.shape != t.shape
+                                                                         for d, t in zip(p, disps)) for p in disp_srcs):
+            raise ValueError("warp_photometric_multiscale: geometric=True needs disp_srcs, one list of disparities per source frame with "
+                             "the scales and shapes of disps")
+        if int(geo_min_valid) < 0:
+            raise ValueError(f"geo_min_valid: {geo_min_valid} is negative")
     depth = disp_pyramid_depth(disps, (H, W), min_depth, max_depth, scale)
     S = depth.shape[0]
     if depth.shape[1] != B:
@@ -868,6 +909,21 @@ def warp_photometric_multiscale(disps, srcs, tgt, K, inv_K, Ts, min_depth, max_d
         frames = lambda t: t.repeat(S, 1, 1, 1)
     mats = lambda t: t.unsqueeze(0).expand(S, -1, -1, -1).reshape(S * B, 4, 4)
     stacked = depth.view(S * B, 1, H, W)
+    if geometric:
+        n = len(srcs)
+        fs, ft = [frames(s) for s in srcs], frames(tgt)
+        _check_warp_inputs("warp_photometric_multiscale", stacked, fs, ft, K, inv_K, n_poses=n)
+        if tie_noise is not None and tuple(tie_noise.shape) != (B, n, H, W):
+            raise ValueError(f"tie_noise: expected ({B},{n},{H},{W}), got {tuple(tie_noise.shape)}")
+        dsrc = [disp_pyramid_depth(p, (H, W), min_depth, max_depth, scale).view(S * B, 1, H, W) for p in disp_srcs]
+        noise = tie_noise.repeat(S, 1, 1, 1) if tie_noise is not None else None
+        terms = (TERM_AUTO_MASKING if auto_masking else 0) | (TERM_MIN_REPROJECTION if min_reprojection else 0)
+        p, geo, _synth, _valid, _select, count, pmap = _WarpPhotometricWindow.apply(
+            stacked, dsrc[0], dsrc[1] if n == 2 else None, fs[0], fs[1] if n == 2 else None, ft, mats(K), mats(inv_K), mats(Ts[0]),
+            mats(Ts[1]) if n == 2 else None, noise, _padding(padding_mode), bool(use_mask), terms, int(geo_min_valid), True, S)
+        per = geo.view(n, S)                                     # [s G + g]
+        return {"photometric": p, "photometric_per_scale": pmap.view(S, -1).mean(1), "depth": depth, "geometric": per.mean(1),
+                "geometric_per_scale": per.detach().t(), "geo_count": count.view(n, S).t()}
     if len(srcs) == 1 and not (min_reprojection or auto_masking):
         out = warp_photometric(stacked, frames(srcs[0]), frames(tgt), mats(K), mats(inv_K), mats(Ts[0]), padding_mode=padding_mode,
                                use_mask=use_mask, want_pmap=True)

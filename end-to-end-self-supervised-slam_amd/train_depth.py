@@ -32,6 +32,12 @@ and averages, on the same fused pair with the scales stacked along the batch; ev
 `DATA.scales` as monodepth2 does: each scale's mean-normalised disparity of frame 0 against the target image box-averaged to that scale's
 resolution (F.avg_pool2d; monodepth2's dataloader resizes with an antialiasing filter instead), weighted 1 / (2^s S) -- its
 `smooth_loss / 2**scale` followed by `/ num_scales` -- in one call of e2e_disp_pyramid_smoothness_lossgrad (ops.disp_pyramid_smoothness).
+`LOSS.multiscale_geometric: True` (absent = False; needs LOSS.multiscale and LOSS.geometric, which without it refuse each other) takes the
+geometric-consistency term on every scale of `DATA.scales` as well: every source frame's disparity pyramid is upsampled and converted as the
+target's, and one grouped pair, e2e_warp_photo_geo_groups_fwd / _bwd, counts, gates (`mask.sum() > 10000`) and averages the term per scale and
+source; the loss adds mean over sources of mean over scales times LOSS.geometric_weight.  This is the one term that gives the coarse heads of
+the source frames a gradient.  As with LOSS.geometric on one scale, the photometric part of such a step is the geo kernel's, whose image
+sample is align_corners=True.
 
     python train_depth.py --config_path configs/config_train_depth.yaml
 """
@@ -80,11 +86,18 @@ class Depth_Estimation:
         # disparity upsampled to the input resolution, and averaged (ops.warp_photometric_multiscale), which is what trains the heads of
         # the coarse scales.  It exists on the fused route only.
         self.multiscale = bool(getattr(self.args.LOSS, "multiscale", False))
+        # LOSS.multiscale_geometric (absent = False): the geometric-consistency term on every scale of DATA.scales too, each scale with its
+        # own valid-projection count, gate and mean (ops.warp_photometric_multiscale(geometric=True)): the one term that reaches the coarse
+        # heads of the SOURCE frames
+        self.multiscale_geometric = bool(getattr(self.args.LOSS, "multiscale_geometric", False))
+        if self.multiscale_geometric and not (self.multiscale and self.args.LOSS.geometric):
+            raise ValueError("LOSS.multiscale_geometric needs LOSS.multiscale: True and LOSS.geometric: True")
         if self.multiscale:
             if self.args.MODEL.depth_network != "monodepth2":
                 raise ValueError("LOSS.multiscale needs MODEL.depth_network: monodepth2 (the indoor network predicts scale 0 only)")
-            if self.args.LOSS.geometric:
-                raise NotImplementedError("LOSS.multiscale with LOSS.geometric: the geometric-consistency term has no multi-scale form")
+            if self.args.LOSS.geometric and not self.multiscale_geometric:
+                raise NotImplementedError("LOSS.multiscale with LOSS.geometric: the geometric-consistency term has no multi-scale form "
+                                          "unless LOSS.multiscale_geometric: True takes it on every scale")
             if not fused_losses or self.args.LOSS.photometric_mask is None:
                 raise NotImplementedError("LOSS.multiscale with fused_losses=False (or LOSS.photometric_mask: None): the multi-scale loss "
                                           "runs on the fused warp-photometric pair only")
@@ -357,19 +370,19 @@ class Depth_Estimation:
             inputs["source_disp", -1], inputs["target_disp"], inputs["source_disp", 1] = inputs["disp", 0, 0], inputs["disp", 1, 0], inputs["disp", 2, 0]
             inputs["T", -1] = poses[:, 1].contiguous()
             inputs["T", 1] = inverse_T_matrix(poses[:, 2]).contiguous()
-            self._tgt_index = 1
+            self._tgt_index, self._src_index = 1, {-1: 0, 1: 2}
         elif a.DATA.frames[1] < 0:
             inputs["source_frame", -1], inputs["target_frame"] = nhwc(0), nhwc(1)
             inputs["source_depth", -1], inputs["target_depth"] = inputs["depth", 0, 0], inputs["depth", 1, 0]
             inputs["source_disp", -1], inputs["target_disp"] = inputs["disp", 0, 0], inputs["disp", 1, 0]
             inputs["T", -1] = poses[:, 1].contiguous()
-            self._tgt_index = 1
+            self._tgt_index, self._src_index = 1, {-1: 0}
         else:
             inputs["target_frame"], inputs["source_frame", 1] = nhwc(0), nhwc(1)
             inputs["target_depth"], inputs["source_depth", 1] = inputs["depth", 0, 0], inputs["depth", 1, 0]
             inputs["target_disp"], inputs["source_disp", 1] = inputs["disp", 0, 0], inputs["disp", 1, 0]
             inputs["T", 1] = inverse_T_matrix(poses[:, 1]).contiguous()
-            self._tgt_index = 0
+            self._tgt_index, self._src_index = 0, {1: 1}
         if a.LOSS.supervise_depth:
             for index in range(self.sequence_length):
                 inputs[("sparse_gt_depth", index, 0)], inputs[("sparse_mask", index, 0)] = sparse_sampling(
@@ -411,7 +424,9 @@ class Depth_Estimation:
         reference's default flag set on a two-frame window is e2e_warp_photo_fwd / _bwd; the three-frame window, LOSS.min_reprojection and
         LOSS.auto_masking are e2e_warp_photo_window_fwd / _bwd (candidates and per-pixel minimum of train_depth.py:621-662 in the
         kernel); LOSS.geometric, on any window, is e2e_warp_photo_geo_fwd / _bwd, which adds the geometric-consistency term of every
-        source.  Then the remaining terms."""
+        source.  LOSS.multiscale stacks the scales along the batch of the same pairs; with LOSS.multiscale_geometric it is the grouped geo
+        pair (e2e_warp_photo_geo_groups_fwd / _bwd), the term reduced and gated per scale, and the photometric part is then that kernel's,
+        with its align_corners=True image sample.  Then the remaining terms."""
         a = self.args
         frames = a.DATA.frames[1:]
         self.optimizer.zero_grad()
@@ -422,12 +437,15 @@ class Depth_Estimation:
             if a.LOSS.min_reprojection and a.LOSS.auto_masking:
                 B, _, H, W = inputs["target_depth"].shape
                 noise = torch.randn((B, len(frames), H, W), device=inputs["target_depth"].device) * 0.00001     # "Break tie's" (:650)
+            more = {}
+            if self.multiscale_geometric:                 # the term on every scale: one grouped geo pair, every source's pyramid a leaf
+                more = dict(geometric=True, disp_srcs=[[inputs["disp", self._src_index[f], s] for s in sorted(a.DATA.scales)] for f in frames])
             out = ops.warp_photometric_multiscale([inputs["disp", self._tgt_index, s] for s in sorted(a.DATA.scales)],
                                                   [inputs["source_frame", f] for f in frames], inputs["target_frame"], inputs["K"],
                                                   inputs["Inverse_K"], [inputs["T", f] for f in frames], a.DATA.min_depth, a.DATA.max_depth,
                                                   self._depth_scale, padding_mode=a.MODEL.padding_mode, use_mask=bool(a.LOSS.photometric_mask),
                                                   min_reprojection=bool(a.LOSS.min_reprojection), auto_masking=bool(a.LOSS.auto_masking),
-                                                  tie_noise=noise)
+                                                  tie_noise=noise, **more)
         elif len(frames) == 2 or a.LOSS.min_reprojection or a.LOSS.auto_masking or a.LOSS.geometric:
             noise = None
             if a.LOSS.min_reprojection and a.LOSS.auto_masking:

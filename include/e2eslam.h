@@ -405,6 +405,37 @@ int e2e_warp_photo_geo_bwd(const float* depth_tgt, const float* depth_src0, cons
                            int geo_min_valid, const float* g_loss, float* g_depth_tgt, float* g_depth_src, float* g_T,
                            void* workspace, int S, int B, int H, int W, void* stream);
 
+/* e2e_warp_photo_geo_fwd / _bwd over SCALE GROUPS of the batch: monodepth2's disparity pyramid with the scales stacked along the batch
+ * (ops.warp_photometric_multiscale(geometric=True)), where the reference's gate and mean of the geometric term are per scale.
+ *   B is the stacked batch, groups = G in 1..4 with B % G == 0; group g is the batch items g B/G ... (g + 1) B/G - 1 (scale-major).
+ *   Everything of the geo pair holds per item and per source: the candidates, select, pmap, tie_noise, align_corners=True for the image
+ *     and False for the depth sample, the fixed-point scatter into g_depth_src, g_T per stacked item, bitwise reproducibility.
+ *   Only the geometric term's reduction and gate change.  geo_count int32 [S G] and loss_out float [1 + S G], indexed [s G + g] and
+ *     [1 + s G + g]:  n_{s,g} = the valid projections of source s over group g;  G_{s,g} = sum(diff valid over group g) / n_{s,g} if
+ *     n_{s,g} > geo_min_valid, else 0;  loss_out[0] stays the photometric mean over the whole stacked batch.  The second stage adds group g's
+ *     workgroup partials in the order a call of e2e_warp_photo_geo_fwd on that group's slice adds them: geo_count[s G + g] and
+ *     loss_out[1 + s G + g] have that call's bits, and so have synth, valid, select and pmap.
+ *   Backward: g_loss float [1 + S G]; a valid pixel of item b in group g uses e = g_loss[1 + s G + g] / n_{s,g} under that group's gate.  A closed
+ *     gate, n_{s,g} == 0 or g_loss[1 + s G + g] == 0 skips the piece for that group's items only: their g_depth_src planes are 0, their
+ *     g_depth_tgt and g_T have the bits of the photometric part.  The poison word of the scatter stays one per source: a contribution out of
+ *     range turns that source's g_depth_src into NaN for every group.
+ *   groups = 1 is e2e_warp_photo_geo_fwd / _bwd bit for bit.  There is no intrinsics form.
+ *   workspace: e2e_warp_photo_geo_workspace_floats and e2e_warp_photo_geo_bwd_workspace_bytes at the stacked B; the layouts are unchanged.
+ *   A refused call (what the geo pair refuses, in its order; then groups outside 1..4; then B % groups != 0) returns E2E_ERR_ARG before any
+ *     launch and writes nothing. */
+int e2e_warp_photo_geo_groups_fwd(const float* depth_tgt, const float* depth_src0, const float* depth_src1, const float* src0,
+                                  const float* src1, e2e_strides src_strides, const float* tgt, e2e_strides tgt_strides,
+                                  const float* K, const float* inv_K, const float* T, const float* tie_noise, float* synth,
+                                  float* valid, int* select, float* pmap, int* geo_count, int use_mask, int padding_mode,
+                                  int terms, int geo_min_valid, float* loss_out, float* workspace, int S, int groups, int B, int H,
+                                  int W, void* stream);
+int e2e_warp_photo_geo_groups_bwd(const float* depth_tgt, const float* depth_src0, const float* depth_src1, const float* src0,
+                                  const float* src1, e2e_strides src_strides, const float* tgt, e2e_strides tgt_strides,
+                                  const float* K, const float* inv_K, const float* T, const float* synth, const float* valid,
+                                  const int* select, const int* geo_count, int use_mask, int padding_mode, int terms,
+                                  int geo_min_valid, const float* g_loss, float* g_depth_tgt, float* g_depth_src, float* g_T,
+                                  void* workspace, int S, int groups, int B, int H, int W, void* stream);
+
 /* e2e_warp_photo_window_bwd and e2e_warp_photo_geo_bwd with the gradient with respect to the intrinsics: the rule of
  * e2e_warp_photo_bwd_intrinsics with one (Pbar_s, Q_s) per source, added in the order s = 0, 1.
  *   g_K, g_inv_K (B,4,4)   both required;   g_T (S,B,4,4) or NULL: NULL skips the pose final stage, otherwise the bits of the form above;
